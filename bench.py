@@ -3,7 +3,7 @@
 bench.py — headline benchmark: MCMC steps/s x walkers (walker log-posterior evaluations per second)
 on BASELINE config 4 (2048 design points x 20 parameters x 64 observables, 10 GPs, 4096 walkers).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,11 @@ re-seeding at its best points, src/mcmc.py:392-405), so that every proposal row 
 evaluated (asserted: >= 95 % over the timed region) — `value` counts only work that was done.  The run from walkers
 spread uniformly over the box, where about half of the proposals leave the box and cost nothing (here as in the
 reference, src/mcmc.py:275-283), is reported beside it as extras.uniform_start.
+
+A plain run times the headline alone: set-up, pre-heat, warm-up, the --steps timed steps, the line.  --full adds everything else
+the line has carried: extras.uniform_start, the other extras (N = 1), the all-gather probe (N > 1) and the CPU baseline (N = 1).
+--dump-outputs DIR writes the ensemble the last timed step left (positions.npy, log_prob.npy, acceptance_fraction.npy; float64):
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -726,6 +731,12 @@ def main():
     ap.add_argument("--sliced", action="store_true",
                     help="NOT the headline: the whole run with the int8 predict kernel (option key 51, csrc/gpb_sliced.hip) switched on; "
                          "the line says so in config.variant and prices its roofline against the dense int8 MFMA peak")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures: the run from the uniform start, extras, the "
+                         "all-gather probe (N > 1) and the CPU baseline (--no-uniform / --no-extras / --no-cpu-baseline drop parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (final walker positions, their log-posteriors, the "
+                         "acceptance fractions) as DIR/<name>.npy in float64")
     args = ap.parse_args()
     if args.sliced:
         os.environ["GPB_PREDICT_SLICED"] = "1"
@@ -898,18 +909,17 @@ def main():
         consistent = bool(torch.equal(lo, hi))
     import hashlib
     checksum = hashlib.sha256(sampler.pos.cpu().numpy().tobytes() + sampler.lp.cpu().numpy().tobytes()).hexdigest()[:16]
-    # the proposal rows of the half-step that FOLLOWS the timed region (the sampler's own proposal kernel on the final
-    # ensemble): what the CPU baseline is timed on — the same inside / outside mix as the timed batches
-    Xnext = torch.empty((nwalkers // 2, d), dtype=torch.float64, device=sampler.pos.device)
-    fnext = torch.empty(nwalkers // 2, dtype=torch.float64, device=sampler.pos.device)
-    from gpbayestools_hic_amd import _native as nat
-    eng._ck(eng.lib.gpb_stretch_propose(eng.h, nat.ptr(sampler.pos), nwalkers, d, 0, sampler.seed, sampler._step_counter,
-                                        sampler.a, nat.ptr(Xnext), nat.ptr(fnext), sampler.randomize_split))
-    Xnext = Xnext.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: StretchSampler.run's final positions, the log-posterior
+        # of every walker and the acceptance fractions (every rank holds the same ensemble)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("positions", sampler.pos.cpu().numpy()), ("log_prob", sampler.lp.cpu().numpy()),
+                          ("acceptance_fraction", sampler.acceptance_fraction)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
     # the same loop from walkers spread uniformly over the box (round 1/2's timed region): about half of the proposals
     # leave the 20-dimensional box and are not evaluated
     uni = None
-    if not args.no_uniform:
+    if args.full and not args.no_uniform:
         phase(0.375, "timed run from the uniform start")
         su, dtu, lu, kmsu, unitsu, units_all_u = timed_run(X0_uniform, 4242)
         uni = {"value": nwalkers * args.steps / dtu, "unit": "walker-evals/s (proposals outside the box counted, not evaluated)",
@@ -925,7 +935,7 @@ def main():
     # the wire, measured: what ONE all-gather of a batch's shares costs on the kernels' stream (twice per step) — the number the
     # expected 8-GPU rate hangs on; a failure here must not cost the line that was just timed
     wire = None
-    if sharded:
+    if sharded and args.full:
         phase(0.25, "all-gather probe")
         try:
             us = sharding.time_allgather(max(nwalkers // 2 // world, 1))
@@ -1021,13 +1031,21 @@ def main():
                 out["roofline"]["traffic_note"] = note
         except Exception as e:      # noqa: BLE001
             out["roofline"]["traffic_note"] = "%s: %s" % (type(e).__name__, e)
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             out["extras"] = extras(chain, emu, info, args.sustain, args.only_sustained)
         if uni is not None:
             out.setdefault("extras", {})["uniform_start"] = uni
         if wire is not None:
             out.setdefault("extras", {})["allgather_probe"] = wire
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
+            # the proposal rows of the half-step that FOLLOWS the timed region (the sampler's own proposal kernel on the final
+            # ensemble): what the CPU baseline is timed on — the same inside / outside mix as the timed batches
+            Xnext = torch.empty((nwalkers // 2, d), dtype=torch.float64, device=sampler.pos.device)
+            fnext = torch.empty(nwalkers // 2, dtype=torch.float64, device=sampler.pos.device)
+            from gpbayestools_hic_amd import _native as nat
+            eng._ck(eng.lib.gpb_stretch_propose(eng.h, nat.ptr(sampler.pos), nwalkers, d, 0, sampler.seed, sampler._step_counter,
+                                                sampler.a, nat.ptr(Xnext), nat.ptr(fnext), sampler.randomize_split))
+            Xnext = Xnext.cpu().numpy()
             rows = min(args.cpu_rows or Xnext.shape[0], Xnext.shape[0])
             cb, lp_cpu = cpu_baseline(info, np.ascontiguousarray(Xnext[:rows]),
                                       "the proposal rows of the half-step that follows the GPU's timed region "

@@ -16,7 +16,7 @@ from conftest import REPO
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ["--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline"]
+ARGS = ["--steps", "4", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"]      # --full: uniform start, all-gather probe
 
 
 def _free_port():

@@ -10,7 +10,7 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 summ() { f=$(find "$1" -name '*kernel_trace.csv' | head -1); python3 "$R/tools/kernel_trace_summary.py" "$f" 25 > "$2"; }
 echo "== full bench under rocprofv3"; date
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/full" -o run -- python3 "$R/bench.py" > "$O/full_bench.json" 2> "$O/full_bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/full" -o run -- python3 "$R/bench.py" --full > "$O/full_bench.json" 2> "$O/full_bench.err"
 cp "$(find "$O/full" -name '*kernel_stats.csv' | head -1)" "$O/full_kernel_stats.csv"; summ "$O/full" "$O/full_kernel_trace_summary.csv"
 echo "== timed region alone"; date
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/timed" -o run -- python3 "$R/bench.py" --preheat 0 --no-extras --no-uniform --no-cpu-baseline > "$O/timed_bench.json" 2> "$O/timed_bench.err"
