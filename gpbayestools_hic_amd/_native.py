@@ -47,6 +47,8 @@ BOUNDARY = {
     "gpb_gp_lml": (C.c_int, [VP, VP, VP, VP, VP]),
     "gpb_gp_predict": (C.c_int, [VP, VP, c_i64, C.c_int, VP, VP]),
     "gpb_gp_predict_cov": (C.c_int, [VP, VP, c_i64, C.c_int, VP, VP]),
+    "gpb_gp_predict_grad": (C.c_int, [VP, VP, c_i64, C.c_int, VP, VP]),
+    "gpb_emu_predict_jac": (C.c_int, [VP, VP, c_i64, C.c_int, VP]),
     "gpb_emu_set_transform": (C.c_int, [VP, C.c_int, c_i64, VP, VP, VP, VP]),
     "gpb_emu_predict": (C.c_int, [VP, VP, c_i64, C.c_int, VP, VP, VP]),
     "gpb_like_set": (C.c_int, [VP, VP, VP]),
@@ -66,6 +68,7 @@ BOUNDARY = {
     "gpb_chain_emcee_run": (C.c_int, [VP, C.c_int, VP, VP, c_i64, c_i64, c_u64, c_u64, C.c_double, C.c_int, VP, VP,
                                       C.c_double, C.c_double, VP, VP, VP]),
     "gpb_chain_emcee_prepare": (C.c_int, [VP, C.c_int, c_i64]),
+    "gpb_chain_logpost_grad": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, VP, C.c_double, C.c_double]),
     "gpb_dist_available": (C.c_int, []),
     "gpb_dist_uid": (C.c_int, [VP]),
     "gpb_dist_init": (C.c_int, [VP, C.c_int, C.c_int, VP]),

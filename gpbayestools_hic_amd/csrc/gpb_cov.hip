@@ -83,16 +83,27 @@ __global__ void k_cov_pack(const double* __restrict__ src, double* __restrict__ 
     if (j < W) dst[((int64_t)p * W + i) * W + j] = src[((int64_t)p * Wld + i) * Wld + j];
 }
 
-int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* cov_dev /*[P][W][W]*/) {
-    // Wld: leading dimension of K*^T / V (workspace capacity); Wc: padded extent of this batch (cov's own ld)
-    const int64_t P = ctx->P, Np = ctx->Np, Wc = round_up(W, WPAD), Wld = Wc;   // launch_predict lays the batch out with ld = Wc
-    const int64_t need_v = P * Np * Wld, need_c = P * Wc * Wc;
+// vbuf[p] = V_p = L_p^-1 K*_p^T of the current batch (fp64 K*^T: the caller of launch_predict set want_kst), ld = ctx->Wld
+int launch_vmat(gpb_ctx* ctx) {
+    const int64_t P = ctx->P, Np = ctx->Np, Wld = ctx->Wld;
+    const int64_t need_v = P * Np * Wld;
     if (need_v > ctx->vbuf_cap) {
         GPB_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->vbuf) pool_free(ctx->vbuf);
+        ctx->vbuf_cap = 0;
         GPB_HIP(pool_malloc_t(&ctx->vbuf, need_v * sizeof(double)));
         ctx->vbuf_cap = need_v;
     }
+    dim3 gv((unsigned)(Wld / 128), (unsigned)((Np + 127) / 128), (unsigned)P);
+    hipLaunchKernelGGL(k_vmat, gv, dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, ctx->vbuf, Np, Wld);
+    GPB_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* cov_dev /*[P][W][W]*/) {
+    // Wc: padded extent of this batch (cov's own ld); launch_predict lays the batch out with ld = Wc
+    const int64_t P = ctx->P, Np = ctx->Np, Wc = round_up(W, WPAD);
+    const int64_t need_c = P * Wc * Wc;
     if (need_c > ctx->covbuf_cap) {
         GPB_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->covbuf) pool_free(ctx->covbuf);
@@ -103,8 +114,8 @@ int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* co
     int rc = launch_predict(ctx, Xs_dev, W, false);          // K*^T and the mean
     ctx->want_kst = false;
     if (rc) return rc;
-    dim3 gv((unsigned)(Wc / 128), (unsigned)((Np + 127) / 128), (unsigned)P);
-    hipLaunchKernelGGL(k_vmat, gv, dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, ctx->vbuf, Np, Wld);
+    const int64_t Wld = ctx->Wld;
+    if ((rc = launch_vmat(ctx))) return rc;
     dim3 gk((unsigned)((Wc + 15) / 16), (unsigned)((Wc + 15) / 16), (unsigned)P);
 #define GPB_KSS(KIND)                                                                                        \
     hipLaunchKernelGGL(k_kss<KIND>, gk, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, ctx->ls, (int)ctx->dpad, \

@@ -130,6 +130,8 @@ struct gpb_ctx {
     bool prof_compacted = false;
     double* vbuf = nullptr;        // [P][Np][Wcap] V = L^-1 K*^T (covariance path only)
     int64_t vbuf_cap = 0;
+    double* gbuf = nullptr;        // gradient path (gpb_grad.hip): beta^T = (K^-1 K*^T)^T [P][Wld][Np], then per-row pieces
+    int64_t gbuf_cap = 0;
     double* covbuf = nullptr;      // [P][Wc][Wc]
     int64_t covbuf_cap = 0;
     double* out_stage = nullptr;   // staging for host outputs
@@ -272,6 +274,7 @@ void sliced_free(gpb_ctx* ctx);
 int sliced_read_kstar(gpb_ctx* ctx, int64_t p, int64_t pad, int64_t N, int64_t W, double* out);
 constexpr int GPB_MAX_MULTI_GP = 96;      // GPs one batched launch can address (its table is a kernel argument)
 int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* cov_dev);
+int launch_vmat(gpb_ctx* ctx);     // gpb_cov.hip: vbuf = L^-1 K*^T of the current (fp64) batch
 // likelihood (gpb_like.hip)
 int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev, double* cov_dev);
 // true when launch_loglike will take the block log-likelihood kernels that sum the partials themselves

@@ -647,6 +647,29 @@ class Emulator:
                 mean[sl] = part
         return (mean, cov) if return_cov else mean
 
+    def predict_jacobian(self, X):
+        """d mean / d X [W, nobs, ndim] at X[W, ndim], in the original parameters: the derivative of predict(X,
+        return_cov=False) through the GPs' closed-form derivatives, the PC -> observable transform, the exp of
+        exp_and_cov_diagonal and the parameterTrafoPCA map (gpb_emu_predict_jac; no finite differences).
+
+        The observable-by-parameter response matrix of examples/SensitivityAnalysis.ipynb (central differences at a step of
+        10 % of each parameter, 2 d predictions per point) follows as, e.g. for relative responses at a point x0:
+
+            J = emu.predict_jacobian(x0[None, :])[0]                  # [nobs, ndim]
+            S = J * (0.1 * x0)[None, :] / emu.predict(x0[None, :], return_cov=False)[0][:, None]
+        """
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        eng = self._engine_ready()
+        W = X.shape[0]
+        per_row = 8 * self._ngp * (self._X_train.shape[0] + X.shape[1])
+        slab = int(min(max((8 << 30) // per_row, 1024), 1 << 15)) // 128 * 128
+        if W <= slab:
+            return eng.emu_predict_jac(np.ascontiguousarray(X))
+        out = np.empty((W, self.nobs, X.shape[1]))
+        for i0 in range(0, W, slab):
+            out[i0:i0 + slab] = eng.emu_predict_jac(np.ascontiguousarray(X[i0:i0 + slab]))
+        return out
+
     def sample_y(self, X, n_samples=1, random_state=None):
         """Sample model output at X -> [n_samples_X, n_samples, nobs] (src/emulator.py:608-633): one
         posterior draw per emulated PC (each GP is handed the same `random_state`, as the reference does),

@@ -261,6 +261,25 @@ class GPEngine:
         self._ck(self.lib.gpb_gp_predict_cov(self.h, nat.ptr(Xs), W, 0, nat.ptr(mean), nat.ptr(cov)))
         return mean, cov
 
+    def predict_grad(self, Xs, return_var=True):
+        """d mean / d x [W,P,d] (and d var / d x [W,P,d]) of every GP at the rows Xs (gpb_gp_predict_grad, fp64);
+        numpy in -> numpy out, torch(cuda) in -> torch out."""
+        self._need_data()
+        if _is_torch(Xs):
+            import torch
+            Xs = self._check_cols(Xs, "Xs")
+            W = Xs.shape[0]
+            dm = torch.empty((W, self.P, self.d), dtype=torch.float64, device=Xs.device)
+            dv = torch.empty((W, self.P, self.d), dtype=torch.float64, device=Xs.device) if return_var else None
+            self._ck(self.lib.gpb_gp_predict_grad(self.h, nat.ptr(Xs), W, 1, nat.ptr(dm), nat.ptr(dv)))
+            return (dm, dv) if return_var else dm
+        Xs = nat.f64(Xs).reshape(-1, self.d)
+        W = Xs.shape[0]
+        dm = nat.host_empty((W, self.P, self.d))
+        dv = nat.host_empty((W, self.P, self.d)) if return_var else None
+        self._ck(self.lib.gpb_gp_predict_grad(self.h, nat.ptr(Xs), W, 0, nat.ptr(dm), nat.ptr(dv)))
+        return (dm, dv) if return_var else dm
+
     # ------------------------------------------------------------------ emulator transform
     def set_transform(self, mode, mu, A=None, cov_trunc=None, scale=None):
         mu = nat.f64(mu)
@@ -289,6 +308,17 @@ class GPEngine:
         cov = nat.host_empty((W, self.M, self.M)) if return_cov else None
         self._ck(self.lib.gpb_emu_predict(self.h, nat.ptr(Xs), W, 0, nat.ptr(es), nat.ptr(mean), nat.ptr(cov)))
         return (mean, cov) if return_cov else mean
+
+    def emu_predict_jac(self, Xs):
+        """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
+        the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""
+        self._need_data()
+        din = self.pmap_d_in if getattr(self, "pmap_d_in", -1) > 0 else self.d
+        Xs = nat.f64(Xs).reshape(-1, din)
+        W = Xs.shape[0]
+        jac = nat.host_empty((W, self.M, din))
+        self._ck(self.lib.gpb_emu_predict_jac(self.h, nat.ptr(Xs), W, 0, nat.ptr(jac)))
+        return jac
 
     # ------------------------------------------------------------------ likelihood block
     def set_likelihood(self, yexp, cov_exp):

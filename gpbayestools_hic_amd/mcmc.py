@@ -346,13 +346,86 @@ class Chain:
             lp[inside] += EXTRA_STD_CONST
         return lp
 
-    def log_likelihood(self, X, extra_std_prior_scale=0.001, finite=False):
-        """src/mcmc.py:188-222 (pocoMC calls it with finite=True)."""
-        return self._log_prob(X, -1e300 if finite else -np.inf)
+    grad_slab_rows = 1 << 14                     # most rows of one gradient evaluation (a row's numbers do not depend on it)
 
-    def log_posterior(self, X, extra_std_prior_scale=.05):
-        """src/mcmc.py:261-299 (the function emcee samples)."""
+    def _log_prob_grad(self, X, outside):
+        """(lp[m], grad[m, ndim]): lp bit for bit what _log_prob gives, grad in fp64 (gpb_chain_logpost_grad); rows outside the
+        prior box get a zero gradient, rows whose covariance block is not positive definite NaN in both."""
+        if not self._native():
+            raise NotImplementedError("log-posterior gradients need every emulator of the chain to be this package's Emulator "
+                                      "(foreign emulators have no device derivatives)")
+        import torch
+        from . import _native as nat
+        X = np.array(X, ndmin=2, dtype=np.float64)
+        if X.shape[1] != self.ndim:
+            raise ValueError("X has %d columns, the chain has %d parameters" % (X.shape[1], self.ndim))
+        dev = torch.device("cuda", self.device)
+        self._prepare_blocks()
+        engs = [e._engine_ready() for e in self.emuList]
+        for g in engs:
+            g._need_data()
+            g._track_stream()
+        arr = (nat.C.c_void_p * len(engs))(*[g.h for g in engs])
+        e0 = engs[0]
+        lo_dev, hi_dev = self._box(dev)
+        # slabs: the gradient keeps beta = K^-1 k* ([P, rows, N] doubles) per emulator besides the predict workspaces
+        per_row = max(8 * e._ngp * e._X_train.shape[0] for e in self.emuList)
+        slab = int(min(max((4 << 30) // per_row, 1024), self.grad_slab_rows)) // 128 * 128
+        lp = np.empty(X.shape[0])
+        grad = np.empty(X.shape)
+        for i0 in range(0, X.shape[0], slab):
+            Xd = torch.as_tensor(np.ascontiguousarray(X[i0:i0 + slab]), device=dev)
+            n = Xd.shape[0]
+            ll = torch.empty(n, dtype=torch.float64, device=dev)
+            gd = torch.empty((n, self.ndim), dtype=torch.float64, device=dev)
+            e0._ck(e0.lib.gpb_chain_logpost_grad(arr, len(engs), nat.ptr(Xd), n, nat.ptr(ll), nat.ptr(gd), nat.ptr(lo_dev),
+                                                 nat.ptr(hi_dev), float(outside), EXTRA_STD_CONST))
+            if not self.use_chain_call:              # (the A/B switch: the value from the per-emulator sequence)
+                ll = self.log_prob_device(Xd, outside=outside)
+            lp[i0:i0 + n] = ll.cpu().numpy()
+            grad[i0:i0 + n] = gd.cpu().numpy()
+        return lp, grad
+
+    def log_likelihood(self, X, extra_std_prior_scale=0.001, finite=False, return_grad=False):
+        """src/mcmc.py:188-222 (pocoMC calls it with finite=True).  return_grad=True: (lp[m], grad[m, ndim]), the tuple the
+        reference's PTLMC takes from a logpostfunc (src/mcmc.py:446-453)."""
+        outside = -1e300 if finite else -np.inf
+        if return_grad:
+            return self._log_prob_grad(X, outside)
+        return self._log_prob(X, outside)
+
+    def log_posterior(self, X, extra_std_prior_scale=.05, return_grad=False):
+        """src/mcmc.py:261-299 (the function emcee samples).  return_grad=True: (lp[m], grad[m, ndim]) — hand
+        functools.partial(chain.log_posterior, return_grad=True) to a gradient-based sampler (PTLMC, src/mcmc.py:446-453)."""
+        if return_grad:
+            return self._log_prob_grad(X, -np.inf)
         return self._log_prob(X, -np.inf)
+
+    def find_map(self, nstarts=32, seed=None, X0=None):
+        """Maximum a posteriori search: nstarts L-BFGS-B minimisations of -log_posterior from uniform draws in the prior box
+        (or from the rows of X0), run in lock-step — every round of objective calls is ONE batched device evaluation of
+        value and gradient for all searches still running (emulator._batched_lbfgsb, the driver of the hyper-parameter
+        searches; each search is scipy.optimize.minimize(method="L-BFGS-B", jac=True) bit for bit).  The box is open and
+        L-BFGS-B evaluates on its bounds: the bounds are the box shrunk by 1e-9 (max - min).
+        Returns (X_opt[n, ndim], lp_opt[n]) sorted by descending lp."""
+        from .emulator import _batched_lbfgsb
+        if X0 is None:
+            rng = np.random.default_rng(seed)
+            X0 = rng.uniform(self.min, self.max, (int(nstarts), self.ndim))
+        X0 = np.array(X0, ndmin=2, dtype=np.float64)
+        eps = 1e-9 * (self.max - self.min)
+        bounds = np.stack([self.min + eps, self.max - eps], axis=1)
+        chain = self
+
+        class _Objective:             # the interface _batched_lbfgsb drives: maximises .lml, i.e. minimises -lp
+            @staticmethod
+            def lml(x, eval_gradient=True):
+                return chain.log_posterior(x, return_grad=True)
+
+        x, f = _batched_lbfgsb(_Objective, X0, bounds)
+        lp = -np.asarray(f, dtype=np.float64)
+        order = np.argsort(-lp, kind="stable")
+        return x[order], lp[order]
 
     def log_likelihood_point_by_point(self, X, extra_std_prior_scale=0.001):
         """Same values as the reference's per-row loop (src/mcmc.py:225-258), in one batch."""

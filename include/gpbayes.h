@@ -127,6 +127,14 @@ GPB_API int gpb_gp_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on_dev
 GPB_API int gpb_gp_predict_cov(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device,
                        double* mean /*[W,P]*/, double* cov /*[P,W,W]*/);
 
+/* Gradient of the per-GP predictions with respect to the query point (the reference has none; closed form of
+ * GPR.predict's mean k*^T alpha_ and variance k** - k*^T K^-1 k*, sk:_gpr.py:443,454-460, differentiated in x*):
+ *   dmean[w,p,j] = sum_i alpha_i dk(x_w, x_i)/dx_j,  dvar[w,p,j] = -2 sum_i beta_i dk(x_w, x_i)/dx_j,  beta = K^-1 k*(x_w).
+ * dvar may be NULL (the mean alone skips beta, one GEMM of the size of the predict call).  fp64 whatever gpb_ctx_option 51
+ * selects; a row's bits do not depend on the batch it is evaluated in.  Needs a factorisation (gpb_gp_factor). */
+GPB_API int gpb_gp_predict_grad(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device,
+                        double* dmean /*[W,P,d]*/, double* dvar /*[W,P,d] or NULL*/);
+
 /* ---- emulator transform: replaces Emulator.predict after the per-GP calls -------- *
  * gpb_emu_set_transform <- _trans_matrix[:npc], scaler.mean_, _cov_trunc, scaler.scale_  src/emulator.py:335-363
  * gpb_emu_predict       <- Emulator.predict(X, return_cov, extra_std)                   src/emulator.py:465-605
@@ -139,6 +147,12 @@ GPB_API int gpb_emu_set_transform(gpb_ctx* ctx, int mode, int64_t M,
 GPB_API int gpb_emu_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device,
                     const double* extra_std /*[W] or NULL (=0), same memory space as Xs*/,
                     double* mean /*[W,M]*/, double* cov /*[W,M,M] or NULL*/);
+
+/* gpb_emu_predict_jac: Jacobian of the emulator's mean in observable space (Emulator.predict(X, return_cov=False),
+ * src/emulator.py:465-605) with respect to the input, through the transform, the exp of the EXPDIAG modes and, when one is
+ * set, the parameter map: Xs is then [W, d_in] in the original parameters (gpb_param_map_set) and jac [W, M, d_in].
+ * The response matrix the reference's SensitivityAnalysis notebook builds from 2 d finite-difference predictions. */
+GPB_API int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device, double* jac /*[W,M,d_in]*/);
 
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
@@ -240,6 +254,16 @@ GPB_API int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev, do
                         uint64_t seed, uint64_t step0, double a, int randomize_split,
                         const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
                         double* chain_dev, double* lpchain_dev, int64_t* naccept_dev);
+/* gpb_chain_logpost_grad <- Chain.log_posterior / log_likelihood together with the gradient in the chain's parameters,
+ *   the (lp, grad) tuple the reference's PTLMC sampler takes from its logpostfunc (src/mcmc.py:446-453, 499-528, 545-569).
+ *   ll_dev receives bit for bit what gpb_chain_logpost writes (or, for contexts it does not accept, what the per-emulator
+ *   sequence gpb_loglike ... gpb_logpost writes), under whichever predict arithmetic is selected; grad_dev [W, ndim] is fp64:
+ *   per emulator the block's d lp / d (mean, variance) of every GP (all four transform modes), folded with the GP
+ *   derivatives of gpb_gp_predict_grad and the parameter map's Jacobian.  Rows outside the box: outside_value and a zero
+ *   gradient.  Rows whose block is not positive definite: NaN in both.  Asynchronous, all pointers device memory. */
+GPB_API int gpb_chain_logpost_grad(gpb_ctx* const* ctxs, int E, const double* Xs_dev /*[W,ndim]*/, int64_t W, double* ll_dev /*[W]*/,
+                           double* grad_dev /*[W,ndim]*/, const double* lo_dev, const double* hi_dev, double outside_value,
+                           double inside_const);
 /* gpb_chain_emcee_prepare: everything of gpb_chain_emcee_run that can fail on one rank alone — argument and state checks,
  * workspace allocation — and nothing that is enqueued.  A sharded caller runs it on every rank and lets the ranks agree on
  * the outcome (an all-reduce of the return codes) BEFORE any rank calls gpb_chain_emcee_run: a rank that failed there
