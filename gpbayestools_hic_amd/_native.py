@@ -69,6 +69,8 @@ BOUNDARY = {
                                       C.c_double, C.c_double, VP, VP, VP]),
     "gpb_chain_emcee_prepare": (C.c_int, [VP, C.c_int, c_i64]),
     "gpb_chain_logpost_grad": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, VP, C.c_double, C.c_double]),
+    "gpb_chain_ptlmc_run": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_i64, c_u64, c_u64, c_i64, C.c_double, VP, VP, VP, VP,
+                                      VP, VP, VP, VP, VP, VP, C.c_double, C.c_double, VP, c_i64, VP, VP]),
     "gpb_dist_available": (C.c_int, []),
     "gpb_dist_uid": (C.c_int, [VP]),
     "gpb_dist_init": (C.c_int, [VP, C.c_int, C.c_int, VP]),
@@ -84,6 +86,7 @@ DEBUG = {
     "gpb_test_split_perm": (C.c_int, [VP, c_i64, c_u64, c_u64, VP]),
     "gpb_test_philox": (C.c_int, [VP, c_i64, VP, VP]),
     "gpb_test_stretch_draws": (C.c_int, [VP, c_i64, C.c_int, c_u64, c_u64, C.c_int, VP, VP, VP, VP]),
+    "gpb_test_ptlmc_draws": (C.c_int, [VP, c_i64, c_i64, c_u64, c_u64, VP, VP, VP, VP]),
     "gpb_test_gemm": (C.c_int, [VP, c_i64, c_i64, c_i64, VP, VP, VP, C.c_int]),
     "gpb_debug_loopback_group": (C.c_int, [VP, C.c_int]),
     "gpb_debug_loopback_release": (C.c_int, [VP]),

@@ -165,6 +165,8 @@ struct gpb_ctx {
     long long* n_nan = nullptr;    // device counter: NaN log-probabilities seen by the stretch move's accept step
     double* mc_ws = nullptr;       // gpb_emcee_run: proposals q[nh][d], factor[nh], log-probabilities lpq[nh]
     int64_t mc_cap = 0;
+    double* ptl_ws = nullptr;      // gpb_chain_ptlmc_run: draws, proposals, their lp / gradient, the other state buffers
+    int64_t ptl_cap = 0;
     int sim_ranks = 0;             // measurement hook: gpb_emcee_run evaluates 1/sim_ranks of every batch (one rank's share)
     int num_cu = 256;               // multiprocessor count of the device
     int64_t narrow_switch = 1280;   // 64x64 tiles when at least this many of them exist per 256 CUs, else 64x32

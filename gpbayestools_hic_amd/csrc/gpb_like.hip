@@ -5,6 +5,7 @@
 //   k_box       strict prior box + constant                        src/mcmc.py:194-198,275-276,296-297
 //   k_propose / k_accept   emcee StretchMove (a=2) as driven by     src/mcmc.py:68-92,372-412
 #include "gpb_internal.h"
+#include "philox.h"
 #include <math.h>
 
 namespace gpb {
@@ -1030,30 +1031,6 @@ __global__ void k_box(const double* __restrict__ X, int64_t W, int d, const doub
         in = in && (x > lo[k]) && (x < hi[k]);      // strict (src/mcmc.py:275)
     }
     ll[w] = in ? (ll[w] + inside_const) : outside;
-}
-
-// ------------------------------------------------------------------ Philox4x32-10
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    U4 c = {c0, c1, c2, c3};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        U4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-__device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {   // 53-bit uniform in [0,1)
-    const uint64_t b = (((uint64_t)hi << 32) | lo) >> 11;
-    return (double)b * (1.0 / 9007199254740992.0);
 }
 
 // ---- red/blue split ----------------------------------------------------------------------------------

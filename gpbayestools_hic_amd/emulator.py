@@ -871,17 +871,21 @@ class _SearchEngine:
         self.eng.close()
 
 
-def _batched_lbfgsb(eng, start, bounds):
+def _batched_lbfgsb(eng, start, bounds, return_hess_inv=False):
     """P independent L-BFGS-B minimisations of -LML_p(theta_p) in LOCK-STEP: every round of objective calls is served by one
     batched device evaluation — of the searches still running when the engine can evaluate a subset (`lml_active`), else of all
     P (`lml`; a finished search's theta stays where it ended).  Each search is scipy's own (sk:_gpr.py:654-670 calls
     scipy.optimize.minimize(method="L-BFGS-B", jac=True, bounds=...)): driven either by ONE thread that steps scipy's
     reverse-communication routine for all searches in turn (_lockstep_setulb: no thread switches, no GIL hand-overs — 63 scipy
     threads cost more per round than the device evaluation they wait for), or, where this scipy does not offer that routine in the
-    form known here, by one scipy.optimize.minimize thread per search (_lockstep_threads).  Same theta*, bit for bit."""
+    form known here, by one scipy.optimize.minimize thread per search (_lockstep_threads).  Same theta*, bit for bit.
+    return_hess_inv=True: a third element, each search's inverse-Hessian operator as scipy.optimize.minimize returns it
+    (OptimizeResult.hess_inv, a LbfgsInvHessProduct of the last corrections)."""
     if _setulb_usable():
-        return _lockstep_setulb(eng, start, bounds)
-    return _lockstep_threads(eng, start, bounds)
+        out = _lockstep_setulb(eng, start, bounds, return_hess_inv)
+    else:
+        out = _lockstep_threads(eng, start, bounds, return_hess_inv)
+    return out if return_hess_inv else out[:2]
 
 
 def _evaluate_round(eng, cur, ids):
@@ -993,7 +997,7 @@ def _setulb_usable():
     return _setulb_ok
 
 
-def _lockstep_setulb(eng, start, bounds):
+def _lockstep_setulb(eng, start, bounds, hess_inv=False):
     from scipy.optimize import _lbfgsb_py
     setulb = _lbfgsb_py._lbfgsb.setulb
     P = start.shape[0]
@@ -1012,10 +1016,24 @@ def _lockstep_setulb(eng, start, bounds):
             if (s.advance() if first else s.resume()):
                 nxt.append(p)
         ids, first = nxt, False
-    return np.array([s.x for s in searches]), np.array([float(s.f) for s in searches])
+    x, f = np.array([s.x for s in searches]), np.array([float(s.f) for s in searches])
+    if not hess_inv:
+        return x, f
+    return x, f, [_setulb_hess_inv(s) for s in searches]
 
 
-def _lockstep_threads(eng, start, bounds):
+def _setulb_hess_inv(s):
+    """the inverse-Hessian operator of a finished search, built as scipy 1.15's _minimize_lbfgsb builds it: the corrections
+    s_k, y_k of the work array, as many as the routine has made (isave[30]), at most m"""
+    from scipy.optimize import LbfgsInvHessProduct
+    n, m = s.x.shape[0], s.m
+    sk = s.wa[0:m * n].reshape(m, n)
+    yk = s.wa[m * n:2 * m * n].reshape(m, n)
+    n_corrs = min(int(s.isave[30]), m)
+    return LbfgsInvHessProduct(sk[:n_corrs].copy(), yk[:n_corrs].copy())
+
+
+def _lockstep_threads(eng, start, bounds, hess_inv=False):
     """one scipy.optimize.minimize thread per search, meeting at every objective call (see _batched_lbfgsb)"""
     P = start.shape[0]
     cur = start.copy()
@@ -1051,7 +1069,7 @@ def _lockstep_threads(eng, start, bounds):
         try:
             res = scipy.optimize.minimize(lambda th: objective(p, th), start[p], method="L-BFGS-B",
                                           jac=True, bounds=bounds[p] if bounds.ndim == 3 else bounds)
-            results[p] = (res.x, res.fun)
+            results[p] = (res.x, res.fun, res.hess_inv)
         except Exception as e:
             results[p] = e
         finally:
@@ -1069,4 +1087,5 @@ def _lockstep_threads(eng, start, bounds):
     for r in results:
         if isinstance(r, Exception):
             raise r
-    return np.array([r[0] for r in results]), np.array([r[1] for r in results])
+    x, f = np.array([r[0] for r in results]), np.array([r[1] for r in results])
+    return (x, f, [r[2] for r in results]) if hess_inv else (x, f)

@@ -1,7 +1,8 @@
 """
 Drop-in replacement for the reference's `src/mcmc.py` log-posterior path and emcee driver
 (B2 protocol): `mvn_loglike`, `Chain` with `log_prior / log_likelihood /
-log_posterior / _predict / run_mcmc / run_pocoMC / compute_log_likelihood_for_chain`.
+log_posterior / _predict / run_mcmc / run_MCMC_PTLMC / samplerPTLMC / tempexchange / run_pocoMC /
+compute_log_likelihood_for_chain`.
 
 Every emulator prediction, covariance assembly, Cholesky and quadratic form runs in the HIP
 engine.  When all emulators in `emuList` are this package's `Emulator`, a log-probability call
@@ -517,6 +518,51 @@ class Chain:
             failed = share(failed)
             if failed:
                 raise RuntimeError("run_mcmc: rank 0 could not write %s (%s)" % (self.mcmc_path, failed))
+
+    def samplerPTLMC(self, logpostfunc, draw_func, theta0=None, numtemps=32, numchain=16, sampperchain=400, maxtemp=30,
+                     nstartparameters=1000, seed=None):
+        """Parallel-tempered Langevin Monte Carlo (surmise 0.2.1's PTLMC as the reference carries it, src/mcmc.py:431-676),
+        with the step loop resident on the device (ptlmc.PTLMCSampler, gpb_chain_ptlmc_run).  `logpostfunc` must be this
+        chain's log_posterior or log_likelihood, or a functools.partial of either setting return_grad (and finite): the loop
+        evaluates the chain itself.  A tuple return selects the Langevin branch (target acceptance 0.60), otherwise the
+        random-walk branch (0.25).  Returns {'theta': [numchain, sampperchain, ndim]}, the untempered rungs.  `seed` keys
+        np.random.default_rng for the host draws and the device's Philox streams; the deviations from the reference are
+        listed in gpbayestools_hic_amd/ptlmc.py.  Raises TypeError for any other logpostfunc, ValueError when there are fewer
+        start rows than rungs, NotImplementedError for foreign emulators or a sharded chain."""
+        from .ptlmc import sampler_ptlmc
+        return sampler_ptlmc(self, logpostfunc, draw_func, theta0=theta0, numtemps=numtemps, numchain=numchain,
+                             sampperchain=sampperchain, maxtemp=maxtemp, nstartparameters=nstartparameters, seed=seed)
+
+    def tempexchange(self, lpostf, temps, iters=1):
+        """The temperature exchange of surmise's PTLMC (src/mcmc.py:679-692) on the host with numpy's global generator: iters
+        sweeps of len(lpostf) random neighbour picks rt in [1, T), each swapping rungs rt - 1 and rt by the parallel-tempering
+        rule.  Returns the new order.  (The device loop runs the same rule on Philox draws, csrc/gpb_ptlmc.hip.)"""
+        n = lpostf.shape[0]
+        order = np.arange(0, n)
+        for _ in range(iters):
+            for rt in np.random.choice(range(1, n), n):
+                dtemp = 1 / temps[rt - 1] - 1 / temps[rt]
+                if (lpostf[order[rt]] - lpostf[order[rt - 1]]) * dtemp > np.log(np.random.uniform(size=1)):
+                    order[rt - 1], order[rt] = order[rt], order[rt - 1]
+        return order
+
+    def run_MCMC_PTLMC(self, nsteps=500, nwalkers=16, ntemps=50, maxtemp=100, nstartparameters=1000, *, seed=None,
+                       gradient=False):
+        """src/mcmc.py:696-726: samplerPTLMC with numchain = nwalkers, numtemps = ntemps, sampperchain = nsteps and start rows
+        drawn uniformly in the prior box; writes {'chain': [nwalkers, nsteps, ndim]} to mcmc_path and sets self.chain.
+        gradient=False samples log_posterior as the reference does; gradient=True takes the Langevin branch
+        (functools.partial(self.log_posterior, return_grad=True))."""
+        import functools
+        log.info("Starting MCMC ...")
+        draws = np.random.default_rng(None if seed is None else [int(seed), 1])
+        result = self.samplerPTLMC(functools.partial(self.log_posterior, return_grad=True) if gradient else self.log_posterior,
+                                   lambda n: draws.uniform(self.min, self.max, (n, self.ndim)), theta0=None, numtemps=ntemps,
+                                   numchain=nwalkers, sampperchain=nsteps, maxtemp=maxtemp,
+                                   nstartparameters=nstartparameters, seed=seed)
+        self.chain = result["theta"].reshape((nwalkers, nsteps, self.ndim))
+        log.info("Writing MCMC chains to file ...")
+        with open(self.mcmc_path, "wb") as f:
+            pickle.dump({"chain": self.chain}, f)
 
     def run_pocoMC(self, n_effective=1000, n_active=250, n_prior=2000, sample="tpcn", n_max_steps=200,
                    random_state=42, n_total=5000, n_evidence=5000, pool=None, prior=None):

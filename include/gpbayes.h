@@ -264,6 +264,27 @@ GPB_API int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev, do
 GPB_API int gpb_chain_logpost_grad(gpb_ctx* const* ctxs, int E, const double* Xs_dev /*[W,ndim]*/, int64_t W, double* ll_dev /*[W]*/,
                            double* grad_dev /*[W,ndim]*/, const double* lo_dev, const double* hi_dev, double outside_value,
                            double inside_const);
+/* gpb_chain_ptlmc_run <- Chain.samplerPTLMC's step loop (surmise's parallel-tempered Langevin sampler, src/mcmc.py:623-670,
+ *   with tempexchange, src/mcmc.py:679-692) for the chain of ctxs (the contexts gpb_chain_logpost_grad accepts; for
+ *   contexts gpb_chain_supported rejects, the per-emulator sequence gpb_loglike ... gpb_logpost evaluates the rows).
+ *   nsteps steps numbered step0, step0 + 1, ... (global step k), enqueued back to back on the contexts' stream, no host
+ *   synchronisation; one call of n steps gives the bits of n calls of one step.  T = numtemps + numchain rungs (2 .. 4096),
+ *   temps_dev [T] the ladder, temps13_dev [T] its cube roots, hc_dev / covmat0_dev [d, d] the proposal factor and
+ *   covariance (src/mcmc.py:604-615).  State, device memory in and out: theta [T, d], fval [T] (lp / temps), dfval [T, d]
+ *   (grad / temps; NULL: the branch without a gradient), tune [2] = (tau, numtimes).  One step: N(0, 1) draws and the
+ *   proposal, its lp (and gradient), the accept test log u < fvalp - fval + qadj per rung, five sweeps of T exchange picks
+ *   in one lane, numtimes += accepted / T, at tuning steps (k < samptunning, k % 10 == 0) the tau update towards taracc,
+ *   at production steps the numchain untempered rungs written to save_dev [numchain, nsave, d] at k - samptunning (when
+ *   below nsave; save_dev may be NULL).  naccept_dev [T] (accepted proposals per rung) and nswap_dev [T - 1] (exchanges
+ *   between rungs i and i + 1) are incremented; either may be NULL.  Philox4x32-10 keyed by seed, counters
+ *   (rung, k, pair, 2) for the normals, (rung, k, 0, 3) for the accept draw, (pick, k, 0, 4) for the exchange.
+ *   Asynchronous. */
+GPB_API int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps, int64_t numchain, int64_t nsteps, uint64_t step0,
+                        uint64_t seed, int64_t samptunning, double taracc, double* theta_dev, double* fval_dev,
+                        double* dfval_dev, double* tune_dev, const double* temps_dev, const double* temps13_dev,
+                        const double* hc_dev, const double* covmat0_dev, const double* lo_dev, const double* hi_dev,
+                        double outside_value, double inside_const, double* save_dev, int64_t nsave, int64_t* naccept_dev,
+                        int64_t* nswap_dev);
 /* gpb_chain_emcee_prepare: everything of gpb_chain_emcee_run that can fail on one rank alone — argument and state checks,
  * workspace allocation — and nothing that is enqueued.  A sharded caller runs it on every rank and lets the ranks agree on
  * the outcome (an all-reduce of the return codes) BEFORE any rank calls gpb_chain_emcee_run: a rank that failed there

@@ -29,6 +29,12 @@ GPB_API int gpb_test_stretch_draws(gpb_ctx* ctx, int64_t nwalkers, int half, uin
                            int randomize_split, double* u_z_dev /*[nw/2]*/, int64_t* j_dev /*[nw/2]*/,
                            double* u_acc_dev /*[nw/2]*/, int64_t* perm_dev /*[nw]*/);
 
+/* test hook: every random number of gpb_chain_ptlmc_run's step `step` for T rungs of d parameters: normals [T, d] (the
+ * proposal's rvalo), logu_accept [T] (the accept test's log u), picks [5T] (the exchange's rt in 1 .. T - 1, in the order
+ * the serial lane takes them) and logu_swap [5T].  Device outputs. */
+GPB_API int gpb_test_ptlmc_draws(gpb_ctx* ctx, int64_t T, int64_t d, uint64_t seed, uint64_t step, double* normals_dev,
+                         double* logu_accept_dev /*[T]*/, int64_t* picks_dev /*[5T]*/, double* logu_swap_dev /*[5T]*/);
+
 /* ---- micro-benchmarks / self-tests (device) --------------------------------------- */
 /* C[M,N] = A*B through the f64 MFMA tile engine (K%16==0).  b_trans bits 0-1: 0 = A[M,K] B[K,N],
  * 1 = A[M,K] B[N,K]^T, 2 = A[K,M]^T B[K,N]; bit 2: 64x64 tiles instead of 128x128. */
