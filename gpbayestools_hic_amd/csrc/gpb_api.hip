@@ -1117,8 +1117,9 @@ extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
         case 47: if (value < 0 || value > 2) return GPB_E_ARG; ctx->chol_pair = value; break;
         case 49: if (value < 0 || value > 1) return GPB_E_ARG; ctx->lr_split = value; break;
         case 50: if (value != 0 && value != 64 && value != 128) return GPB_E_ARG; ctx->kinv_tile = value; break;
-        case 51:        // V = L^-1 K*^T on the int8 matrix pipe (gpb_sliced.hip): 0 = never (default), 1 = where the rule admits, 2 = rule off
-            if (value < 0 || value > 2) return GPB_E_ARG;
+        case 51:        // V = L^-1 K*^T on the int8 matrix pipe (gpb_sliced.hip): 0 = never, 1 = six planes where their rule admits,
+                        // 2 = six planes, rule off, 3 = seven planes (default)
+            if (value < 0 || value > 3) return GPB_E_ARG;
             ctx->predict_sliced = value;
             break;
         case 44: if (value < 0) return GPB_E_ARG; ctx->tile_switch = value > 0 ? value : 960; break;

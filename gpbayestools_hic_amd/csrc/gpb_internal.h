@@ -85,13 +85,16 @@ struct gpb_ctx {
     double* Linv = nullptr;        // [P][Np][Np]
     // sliced-integer predict (gpb_sliced.hip, option key 51): int8 digit planes of L^-1 (made on first use after a factorisation)
     // and of the current K*^T batch, row / column scales
-    int predict_sliced = 0;        // 0 = fp64 kernel always; 1 = the int8 kernel where its rule admits the context; 2 = rule off (tests)
-    int8_t* slA = nullptr;         // [P][6][Np/16][Np128][16]
-    int8_t* slB = nullptr;         // [P][6][Np/16][Wcap][16] (leading dimension of a batch: Wld)
+    // 0 = fp64 kernel always; 1 = six digit planes where their rule admits the context; 2 = six, rule off (tests);
+    // 3 (default) = seven digit planes (fp64-accurate) wherever the int32 sums stay exact (Np <= 16384)
+    int predict_sliced = 3;
+    int8_t* slA = nullptr;         // [P][D][Np/16][Np128][16], room for D = 7 planes per GP
+    int8_t* slB = nullptr;         // [P][D][Np/16][Wcap][16] (leading dimension of a batch: Wld), room for D = 7
     double* sl_scale = nullptr;    // rowscale [P][Np128] | colscale [P] | rowexp (int) [P][Np128]
     bool slA_valid = false;
+    int slA_depth = 0;             // digit planes per operand of the planes in slA (6 or 7)
     int64_t slB_cap = 0;
-    bool batch_sliced = false;     // the current batch's K*^T exists as digit planes (launch_kcross), not as fp64
+    int batch_sliced = 0;          // the current batch's K*^T exists as this many digit planes (launch_kcross), 0: as fp64
     bool want_kst = false;         // the caller of launch_kcross needs the fp64 K*^T itself (joint covariance)
     double* T = nullptr;           // [P][Np][Np]  workspace (trtri / K^-1)
     double* yv = nullptr;          // [P][Np]      L^-1 z
@@ -267,8 +270,8 @@ int launch_param_maps(gpb_ctx* const* ctxs, int n, const double* X_dev, int64_t 
 int launch_vsq(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev);
 int launch_finalize(gpb_ctx* ctx, int64_t W, bool need_var);
 // gpb_sliced.hip: the int8 form of launch_vsq's 128 x 128 launch for ONE context (rule: sliced_applies)
-bool sliced_applies(const gpb_ctx* ctx);
-int sliced_prepare(gpb_ctx* ctx);                    // buffers, and the planes of L^-1 after a new factorisation
+int sliced_applies(const gpb_ctx* ctx);             // digit planes per operand (6, 7) the context's batches take, 0: the fp64 kernel
+int sliced_prepare(gpb_ctx* ctx, int depth);         // buffers, and the planes of L^-1 after a new factorisation or depth
 const double* sliced_colscale(const gpb_ctx* ctx);   // device [P]: the power-of-two scale of each GP's K*^T digits
 int launch_vsq_sliced(gpb_ctx* ctx, int64_t W, const int* nrows_dev, int kskip);
 int launch_vsq_sliced_multi(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev, int kskip);   // the GPs of E contexts, one launch

@@ -57,11 +57,11 @@ struct KxLds {
     double sal[KX_CHUNK];
 };
 
-// SLICE (option key 51, gpb_sliced.hip): K*^T leaves the kernel as the six int8 digit planes the int8 predict kernel reads —
-// plane[p][t][k / 16][walker][16 bytes] — instead of fp64 (6 bytes per element instead of 8, no second pass over the batch).  A
-// wave then owns 16 CONSECUTIVE design points of the chunk (one 16-byte granule per plane and walker) instead of every fourth,
-// so the four mean partials of a chunk group the points differently: the mean's last bits differ from the fp64 form's.
-template <int KIND, int DPAD, bool DOT, int WPL, bool SLICE = false>
+// SLICE = D (option key 51, gpb_sliced.hip): K*^T leaves the kernel as the D = 6 or 7 int8 digit planes the int8 predict kernel
+// reads — plane[p][t][k / 16][walker][16 bytes] — instead of fp64 (D bytes per element instead of 8, no second pass over the
+// batch).  A wave then owns 16 CONSECUTIVE design points of the chunk (one 16-byte granule per plane and walker) instead of every
+// fourth, so the four mean partials of a chunk group the points differently: the mean's last bits differ from the fp64 form's.
+template <int KIND, int DPAD, bool DOT, int WPL, int SLICE = 0>
 __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* __restrict__ Xs, int64_t W, int d,
                                             const double* __restrict__ Xsc, const double* __restrict__ ls,
                                             const double* __restrict__ amp, const double* __restrict__ alpha,
@@ -150,8 +150,9 @@ __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* _
     }
     const double c = amp[p];
     double* Kp = KsT + (int64_t)p * Np * Wld;
-    // SLICE: x 2^47 / 2^e_c and + 2^52 leave the rounded 47-bit integer in the mantissa (K* in [0, c] <= 0.99 2^e_c)
-    const double slice_sc = SLICE ? 140737488355328.0 / colscale[p] : 0.0;
+    // SLICE: K* in [0, c] <= 0.99 2^e_c times 2^(8D - 1) / 2^e_c, rounded to an integer (exact scaling by a power of two).  D = 6:
+    // + 2^52 leaves the 47-bit integer in the mantissa; D = 7: 55 bits do not fit there, the integer comes from the conversion
+    const double slice_sc = SLICE ? ldexp(1.0, 8 * SLICE - 1) / colscale[p] : 0.0;
     const int64_t plane_sz = (Np / 16) * Wld * 16;
     for (int64_t chunk = chunk0; chunk < chunk1; ++chunk) {
         const int64_t nbeg = chunk * KX_CHUNK;
@@ -170,12 +171,12 @@ __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* _
         double msum[WPL];
 #pragma unroll
         for (int u = 0; u < WPL; ++u) msum[u] = 0.0;
-        unsigned pw[SLICE ? WPL : 1][SLICE ? 6 : 1][SLICE ? 4 : 1];     // SLICE: this wave's granule of every plane, per walker
+        unsigned pw[SLICE ? WPL : 1][SLICE ? SLICE : 1][SLICE ? 4 : 1];     // SLICE: this wave's granule of every plane, per walker
         if (SLICE) {
 #pragma unroll
             for (int u = 0; u < WPL; ++u)
 #pragma unroll
-                for (int tp = 0; tp < 6; ++tp)
+                for (int tp = 0; tp < SLICE; ++tp)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) pw[u][tp][g] = 0u;
         }
@@ -224,11 +225,14 @@ __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* _
             if (SLICE) {
 #pragma unroll
                 for (int u = 0; u < WPL; ++u) {
-                    // the six signed radix-256 digits: bytes of (a + 0x808080808080) ^ 0x808080808080, byte t & 3 of word t >> 2
-                    const unsigned long long a = (unsigned long long)__double_as_longlong(fma(kv[u], slice_sc, 4503599627370496.0)) & 0xfffffffffffffull;
-                    const unsigned long long dg = (a + 0x808080808080ull) ^ 0x808080808080ull;
+                    // the D signed radix-256 digits: bytes of (a + 0x80...80) ^ 0x80...80, byte t & 3 of word t >> 2
+                    constexpr unsigned long long HALF = 0x8080808080808080ull >> (64 - 8 * (SLICE ? SLICE : 1));
+                    const unsigned long long a = SLICE == 7
+                        ? (unsigned long long)__double2ll_rn(kv[u] * slice_sc)
+                        : (unsigned long long)__double_as_longlong(fma(kv[u], slice_sc, 4503599627370496.0)) & 0xfffffffffffffull;
+                    const unsigned long long dg = (a + HALF) ^ HALF;
 #pragma unroll
-                    for (int tp = 0; tp < 6; ++tp)
+                    for (int tp = 0; tp < SLICE; ++tp)
                         pw[u][tp][t >> 2] |= (unsigned)((dg >> (8 * tp)) & 0xffull) << (8 * (t & 3));
                 }
             } else {
@@ -237,11 +241,11 @@ __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* _
             }
         }
         if (SLICE) {
-            int8_t* dst = planes + (int64_t)p * 6 * plane_sz + ((chunk * 4 + wave) * Wld + w0 + lane) * 16;
+            int8_t* dst = planes + (int64_t)p * SLICE * plane_sz + ((chunk * 4 + wave) * Wld + w0 + lane) * 16;
 #pragma unroll
             for (int u = 0; u < WPL; ++u)
 #pragma unroll
-                for (int tp = 0; tp < 6; ++tp)
+                for (int tp = 0; tp < SLICE; ++tp)
                     *reinterpret_cast<uint4*>(dst + tp * plane_sz + (int64_t)u * 64 * 16) = make_uint4(pw[u][tp][0], pw[u][tp][1], pw[u][tp][2], pw[u][tp][3]);
         }
         // red: written here, read by wave 0 below; the next write is behind the two barriers at the top of the loop
@@ -258,7 +262,7 @@ __device__ __forceinline__ void kcross_body(KxLds<DPAD, WPL>& L, const double* _
     }
 }
 
-template <int KIND, int DPAD, bool DOT, int WPL, bool SLICE = false>
+template <int KIND, int DPAD, bool DOT, int WPL, int SLICE = 0>
 __global__ __launch_bounds__(256) void k_kcross(const double* __restrict__ Xs, int64_t W, int d,
                                                 const double* __restrict__ Xsc, const double* __restrict__ ls,
                                                 const double* __restrict__ amp, const double* __restrict__ alpha,
@@ -290,7 +294,7 @@ struct KxCtx {
 };                               // d: the context's own input count (contexts of one launch share the padded count only)
 struct KxTable { KxCtx c[MAX_KX_CTX]; int E; };
 
-template <int DPAD, int WPL, bool SLICE = false>
+template <int DPAD, int WPL, int SLICE = 0>
 __global__ __launch_bounds__(256) void k_kcross_multi(const KxTable tab, int64_t W, int d, int64_t Np, int64_t Wld,
                                                       int chunks_per_wg, const int* __restrict__ nrows) {
     __shared__ KxLds<DPAD, WPL> lds;
@@ -687,7 +691,7 @@ int ensure_wcap(gpb_ctx* ctx, int64_t W) {
 }
 
 template <int KIND>
-static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, bool planes) {
+static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, int planes) {
     const int nchunk = (int)((ctx->Np + KX_CHUNK - 1) / KX_CHUNK);
     // chunks per workgroup: as many as still leave >= 4 workgroups per CU (a geometry choice: the per-chunk
     // partials and their order do not depend on it; measured, cfg 4: 1 / 2 / 4 chunks at 512 / 1024 / 2048+ walkers)
@@ -715,8 +719,12 @@ static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int
     const double* const slcs = planes ? sliced_colscale(ctx) : nullptr;
 #define GPB_KX_LAUNCH(DP, DOT_, WPL_, XD)                                                                         \
     do {                                                                                                          \
-        if (planes)                                                                                               \
-            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_, true>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
+        if (planes == 7)                                                                                          \
+            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_, 7>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
+                               XD, ctx->ls, ctx->amp, ctx->alpha, ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld,       \
+                               (int)ctx->P, ctx->dnorm, ctx->muS, cpw, nrows_dev, form, slB, slcs);               \
+        else if (planes)                                                                                          \
+            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_, 6>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
                                XD, ctx->ls, ctx->amp, ctx->alpha, ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld,       \
                                (int)ctx->P, ctx->dnorm, ctx->muS, cpw, nrows_dev, form, slB, slcs);               \
         else                                                                                                      \
@@ -757,10 +765,10 @@ int launch_kcross(gpb_ctx* ctx, const double* Xs_dev, int64_t W, const int* nrow
     // option key 51 (gpb_sliced.hip): the batch leaves this kernel as int8 digit planes for the int8 predict kernel — for EVERY
     // batch size once the rule admits the context (a walker's bits must not depend on the batch it arrives in) — unless the
     // caller needs K*^T itself (the joint covariance, gpb_gp_get) or shares the predict launch with other contexts
-    const bool planes = allow_planes && !ctx->want_kst && sliced_applies(ctx);
+    const int planes = (allow_planes && !ctx->want_kst) ? sliced_applies(ctx) : 0;     // digit planes per operand, 0: fp64
     ctx->batch_sliced = planes;
     if (planes) {
-        const int rc = sliced_prepare(ctx);
+        const int rc = sliced_prepare(ctx, planes);
         if (rc) return rc;
     }
     // leading dimension of this batch's workspaces (K*^T, partials, per-GP means / variances): the padded batch, not the
@@ -789,11 +797,15 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
     for (int e = 0; e < E && ok; ++e)           // (the shared launch is the Gram form's: a context with a difference-form GP takes its own)
         ok = ctxs[e]->n_diff == 0 && ctxs[e]->Np == ctx->Np && ctxs[e]->dpad == ctx->dpad && ctxs[e]->stream == ctx->stream;
     // option key 51: an emulator's bits must not depend on the company it is evaluated in.  A group whose contexts the int8 rule ALL
-    // admits shares the SLICE form of this launch (digit planes out) and the int8 predict launch (launch_vsq); a mixed group falls
-    // back to one launch per context, each in its own form
+    // admits at ONE depth shares the SLICE form of this launch (digit planes out) and the int8 predict launch (launch_vsq); a mixed
+    // group falls back to one launch per context, each in its own form
     int nsl = 0;
-    for (int e = 0; e < E; ++e) nsl += (!ctxs[e]->want_kst && sliced_applies(ctxs[e])) ? 1 : 0;
-    const bool planes = ok && nsl == E;
+    const int depth0 = ctxs[0]->want_kst ? 0 : sliced_applies(ctxs[0]);
+    for (int e = 0; e < E; ++e) {
+        const int de = ctxs[e]->want_kst ? 0 : sliced_applies(ctxs[e]);
+        nsl += (de != 0 && de == depth0) ? 1 : (de != 0 ? E + 1 : 0);           // (a second depth: never all)
+    }
+    const int planes = (ok && nsl == E) ? depth0 : 0;
     if (nsl > 0 && !planes) ok = false;
     if (!ok) {
         for (int e = 0; e < E; ++e) {
@@ -813,7 +825,7 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
         c->last_W = W;
         c->batch_sliced = planes;
         if (planes) {
-            const int rc = sliced_prepare(c);
+            const int rc = sliced_prepare(c, planes);
             if (rc) { ctx->err = c->err; return rc; }
         }
         tab.c[e] = KxCtx{Xs[e], c->Xc, c->ls, c->amp, c->alpha, c->dnorm, c->muS, c->KsT, c->mpart, planes ? c->slB : nullptr,
@@ -834,14 +846,20 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
     dim3 grid((unsigned)((nchunk + cpw - 1) / cpw), (unsigned)G, (unsigned)(Wuse / (64 * wpl)));
 #define GPB_KXM(DP)                                                                                              \
     do {                                                                                                         \
-        if (wpl == 2 && planes)                                                                                  \
-            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1), true>), grid, dim3(256), 0, ctx->stream, tab, W, \
+        if (wpl == 2 && planes == 7)                                                                             \
+            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1), 7>), grid, dim3(256), 0, ctx->stream, tab, W, \
+                               (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
+        else if (wpl == 2 && planes)                                                                             \
+            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1), 6>), grid, dim3(256), 0, ctx->stream, tab, W, \
                                (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
         else if (wpl == 2)                                                                                       \
             hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1)>), grid, dim3(256), 0, ctx->stream, tab, W, \
                                (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
+        else if (planes == 7)                                                                                    \
+            hipLaunchKernelGGL((k_kcross_multi<DP, 1, 7>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d, \
+                               ctx->Np, Wuse, cpw, nrows_dev);                                                   \
         else if (planes)                                                                                         \
-            hipLaunchKernelGGL((k_kcross_multi<DP, 1, true>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d, \
+            hipLaunchKernelGGL((k_kcross_multi<DP, 1, 6>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d, \
                                ctx->Np, Wuse, cpw, nrows_dev);                                                   \
         else                                                                                                     \
             hipLaunchKernelGGL((k_kcross_multi<DP, 1>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d,    \
@@ -874,7 +892,7 @@ int launch_vsq(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev) {
         int gsum = 0;
         for (int e = 0; e < E; ++e) {
             any_sliced = any_sliced || ctxs[e]->batch_sliced;
-            all_sliced = all_sliced && ctxs[e]->batch_sliced && ctxs[e]->Np == ctx->Np && ctxs[e]->Wld == Wuse && ctxs[e]->stream == ctx->stream;
+            all_sliced = all_sliced && ctxs[e]->batch_sliced && ctxs[e]->batch_sliced == ctx->batch_sliced && ctxs[e]->Np == ctx->Np && ctxs[e]->Wld == Wuse && ctxs[e]->stream == ctx->stream;
             gsum += (int)ctxs[e]->P;
         }
         if (all_sliced && gsum <= MAX_MULTI_GP) {       // one int8 launch over the GPs of all the emulators

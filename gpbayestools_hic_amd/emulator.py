@@ -20,13 +20,15 @@ import numpy as np
 import scipy.optimize
 
 from .engine import (GPEngine, MODE_EXPDIAG, MODE_NO_PCA, MODE_NO_PCA_EXPDIAG, MODE_PCA,
-                     NotPositiveDefinite)
+                     NotPositiveDefinite, PREDICT_SLICED_DEFAULT, predict_sliced_from_env)
 from .preprocess import (Standardizer, WhitenedPCA, observable_transform,
                          parse_model_parameter_file)
 
 log = logging.getLogger(__name__)
 
 _STATE_SERIAL = itertools.count(1)     # one number per fitted state of any emulator of this process (Chain.state_digest_cached)
+# Emulator.set_predict_arithmetic: name -> gpb_ctx_option 51 value (csrc/gpb_sliced.hip)
+_PREDICT_ARITHMETIC = {"fp64-int8": 3, "fp64": 0, "int8": 1}
 
 _KERNELS = {"RBF": ("RBF", (1e-1, 1e2)), "Matern": ("Matern15", (1e-3, 1e5)),
             "Matern25": ("Matern25", (1e-3, 1e5))}
@@ -474,26 +476,42 @@ class Emulator:
             self._engine.close()
         eng = GPEngine(self.device)
         eng.set_data(self._X_train, self._Z_train, _KERNELS[self.kernel_type_][0], self.alpha)
-        if getattr(self, "predict_arithmetic", "fp64") == "int8":
-            eng.tune("predict_sliced", 1)
+        which = getattr(self, "predict_arithmetic", None)
+        if which is not None:                        # (not set: the engine's own default, or what GPB_PREDICT_SLICED says)
+            eng.tune("predict_sliced", _PREDICT_ARITHMETIC[which])
         self._engine = eng
         self._like_key = None
         return eng
 
-    def set_predict_arithmetic(self, which="fp64"):
-        """"fp64" (default): V = L^-1 K*^T of every batch on the fp64 matrix cores; "int8": on the int8 matrix cores
-        (gpb_ctx_option 51, csrc/gpb_sliced.hip — six 8-bit digit planes per operand, exact int32 sums, fp64 combine), 1.8-2.1x faster,
-        the predictive variance within ~2e-11 relative of the fp64 kernel's, for an emulator whose GPs all have 1 + c / sigma_n^2 <= 128
-        (others keep the fp64 kernel).  The choice is kept through pickling; a walker's bits do not depend on batch size, compaction
-        or rank count in either arithmetic, but they differ between the two in the last digits: set it once per analysis."""
-        if which not in ("fp64", "int8"):
-            raise ValueError("predict arithmetic must be 'fp64' or 'int8'")
+    def set_predict_arithmetic(self, which="fp64-int8"):
+        """The arithmetic of V = L^-1 K*^T, the dominant product of every predict (gpb_ctx_option 51, csrc/gpb_sliced.hip).
+        "fp64-int8" (the default): on the int8 matrix cores as seven 8-bit digit planes per operand, exact int32 sums of the 28
+        upper digit products, fp64 combine — as accurate as the fp64 kernel (the log-posterior within 1e-10 of the oracle, like
+        it), ~1.7x faster at cfg 4.  "fp64": the fp64 matrix cores.  "int8": six digit planes, 21 products, ~2x faster, for an
+        emulator whose GPs all have 1 + c / sigma_n^2 <= 128 (others keep the fp64 kernel): the predictive variance within ~2e-11
+        relative of the fp64 kernel's, but a log-posterior only within ~1e-11 .. 2e-9 where its two terms cancel.  Designs of more
+        than 16384 points, the joint covariance and gradients always take the fp64 kernel.  The choice is kept through pickling
+        and is part of the state digest; a walker's bits do not depend on batch size, compaction or rank count in any of them,
+        but they differ between them in the last digits: set it once per analysis."""
+        if which not in _PREDICT_ARITHMETIC:
+            raise ValueError("predict arithmetic must be one of %s" % ", ".join(repr(k) for k in _PREDICT_ARITHMETIC))
         self.predict_arithmetic = which
         if self._engine is not None:
             self._engine._check_pid()
-            self._engine.tune("predict_sliced", 1 if which == "int8" else 0)
+            self._engine.tune("predict_sliced", _PREDICT_ARITHMETIC[which])
         self._state_serial = next(_STATE_SERIAL)      # (replicas of a sharded run must agree on it: it is part of the digest)
         return self
+
+    def _predict_option(self):
+        """the option-51 value this emulator's predicts run at: its engine's, else the one a new engine would take"""
+        eng = getattr(self, "_engine", None)
+        if eng is not None:
+            return int(getattr(eng, "predict_sliced", PREDICT_SLICED_DEFAULT))
+        which = getattr(self, "predict_arithmetic", None)
+        if which is not None:
+            return _PREDICT_ARITHMETIC[which]
+        env = predict_sliced_from_env()
+        return PREDICT_SLICED_DEFAULT if env is None else env
 
     def _engine_ready(self):
         """(Re)create the device state after unpickling, or in a worker forked BEFORE the parent touched the GPU.  A
@@ -517,8 +535,9 @@ class Emulator:
         h = hashlib.sha256()
         h.update(repr((self.kernel_type_, self._ngp, self.nobs, float(self.alpha), int(self._mode),
                        bool(self.parameterTrafoPCA_))).encode())
-        if getattr(self, "predict_arithmetic", "fp64") != "fp64":      # (absent / fp64: the digest of earlier rounds' objects)
-            h.update(b"predict_arithmetic=" + self.predict_arithmetic.encode())
+        opt = self._predict_option()                  # the arithmetic that runs, whoever chose it (0, the fp64 kernel: earlier digests)
+        if opt != 0:
+            h.update(b"predict_sliced=%d" % opt)
         arrs = [self._X_train, self._Z_train, self.thetas_, self.scaler.mean_]
         arrs += [self.scaler.scale_] if self.perform_no_PCA_ else [self._A, self._cov_trunc]
         if self.parameterTrafoPCA_:          # the parameter-space map in front of the GPs (src/emulator.py:492-551)

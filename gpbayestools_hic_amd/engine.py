@@ -25,6 +25,25 @@ def _is_torch(x):
 
 _SERIAL = itertools.count(1)
 
+# gpb_ctx_option 51, the arithmetic of V = L^-1 K*^T: 0 the fp64 kernel, 1 six int8 digit planes where their rule admits the
+# context, 2 six planes with the rule off (accuracy probes), 3 seven planes (fp64-accurate): the library's default
+PREDICT_SLICED_DEFAULT = 3
+_PREDICT_SLICED_ENV = {"0": 0, "fp64": 0, "1": 1, "int8": 1, "2": 2, "3": 3, "fp64-int8": 3}
+
+
+def predict_sliced_from_env():
+    """the option-51 value GPB_PREDICT_SLICED asks every engine of the process for ("0" / "fp64": the fp64 kernel, "1" / "int8":
+    six digit planes, "2": six planes with the rule off, "3" / "fp64-int8": seven planes), None when it is unset, empty or not one
+    of these (a warning says so: a typo must not fail every GPEngine() nor silently run another arithmetic than asked for)"""
+    v = os.environ.get("GPB_PREDICT_SLICED", "").strip().lower()
+    if not v:
+        return None
+    if v not in _PREDICT_SLICED_ENV:
+        import warnings
+        warnings.warn("GPB_PREDICT_SLICED=%r is not one of %s: ignored" % (v, sorted(_PREDICT_SLICED_ENV)), RuntimeWarning)
+        return None
+    return _PREDICT_SLICED_ENV[v]
+
 
 class GPEngine:
     def __init__(self, device=0, stream="torch", debug=None):
@@ -50,10 +69,13 @@ class GPEngine:
         elif stream is not None:
             self._ck(self.lib.gpb_ctx_set_stream(self.h, nat.VP(int(stream))))
         self.N = self.d = self.P = self.M = 0
-        # GPB_PREDICT_SLICED=1 (2: the rule off): every engine of the process evaluates V = L^-1 K*^T on the int8 matrix pipe where
-        # its accuracy rule admits the GPs (option key 51, csrc/gpb_sliced.hip) — the whole test suite runs under it this way
-        if os.environ.get("GPB_PREDICT_SLICED", "0") not in ("", "0"):
-            self.tune("predict_sliced", int(os.environ["GPB_PREDICT_SLICED"]))
+        # option key 51 (csrc/gpb_sliced.hip): the context starts at PREDICT_SLICED_DEFAULT (seven int8 digit planes); the
+        # GPB_PREDICT_SLICED environment hook gives every engine of the process another value (0: the fp64 kernel, 1: six planes)
+        # — the whole test suite runs under it this way
+        self.predict_sliced = PREDICT_SLICED_DEFAULT
+        env = predict_sliced_from_env()
+        if env is not None:
+            self.tune("predict_sliced", env)
 
     # ------------------------------------------------------------------ plumbing
     def _ck(self, rc):
@@ -509,6 +531,8 @@ class GPEngine:
              "mid_switch_c": 34, "narrow_switch_c": 35, "balance_shards": 36, "chain_batch": 40, "force_tile": 42, "generic_mvn": 43,
              "tile_switch": 44, "chol_pair": 47, "lr_split": 49, "kinv_tile": 50, "predict_sliced": 51}[key]
         self._ck(self.lib.gpb_ctx_option(self.h, k, int(value)))
+        if k == 51:
+            self.predict_sliced = int(value)         # (what Emulator.state_digest folds in)
 
     @property
     def has_variants(self):

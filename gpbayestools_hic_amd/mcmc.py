@@ -165,9 +165,9 @@ class Chain:
             self.emuList.append(emu)
         log.info("Number of Emulators: %d", len(self.emuList))
 
-    def set_predict_arithmetic(self, which="fp64"):
-        """the same choice for every drop-in emulator of the chain (Emulator.set_predict_arithmetic): "fp64" (default) or "int8" —
-        foreign emulators are left alone; an emulator outside the int8 rule keeps the fp64 kernel by itself"""
+    def set_predict_arithmetic(self, which="fp64-int8"):
+        """the same choice for every drop-in emulator of the chain (Emulator.set_predict_arithmetic): "fp64-int8" (default), "fp64"
+        or "int8" — foreign emulators are left alone; an emulator outside the six-plane rule keeps the fp64 kernel by itself"""
         from .emulator import Emulator
         for e in self.emuList:
             if isinstance(e, Emulator):

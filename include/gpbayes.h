@@ -328,12 +328,16 @@ GPB_API int gpb_dist_finalize(gpb_ctx* ctx);
  *   schedule (default: 1024 <= N <= 3072), 2 always, 0 never; results agree to rounding (another order of the same sums);
  *   49 the block log-likelihoods of a chain of emulators as one workgroup per (walker tile, emulator) and an ordered sum (1,
  *   default) or as one workgroup per walker tile that walks the emulators (0); same bits;
- *   51 V = L^-1 K*^T (sk:_gpr.py:454-460, src/emulator.py:573-575) on the INT8 matrix pipe (csrc/gpb_sliced.hip): 0 never
- *   (default), 1 for every batch of a context whose GPs all have 1 + c / sigma_n^2 <= 128 (the rule reads theta alone; other
- *   contexts keep the fp64 kernel), 2 the rule off (accuracy probes).  Operands as six signed 8-bit digit planes, the 21 digit
- *   products of the upper levels summed exactly in int32, combined in fp64: the variance within ~2e-11 relative of the fp64
- *   kernel's (1e-10 bar kept), a log-posterior within ~1e-11 .. 2e-9 depending on how far its two terms cancel; a walker's bits
- *   still do not depend on batch, tile, compaction or rank count.  1.8-2.1x the fp64 kernel at cfg 4.
+ *   51 V = L^-1 K*^T (sk:_gpr.py:454-460, src/emulator.py:573-575) on the INT8 matrix pipe (csrc/gpb_sliced.hip): operands as
+ *   D signed 8-bit digit planes, the digit products of the D upper levels summed exactly in int32, combined in fp64; a walker's
+ *   bits do not depend on batch, tile, compaction or rank count.  Contexts with a padded design size above 16384 (where the int32
+ *   sums could wrap), fit-only multi contexts and calls that need K*^T in fp64 (joint covariance, gradients) take the fp64 kernel
+ *   whatever the value.  3 (default): D = 7, the 28 products of levels 6..12 — as accurate as the fp64 kernel everywhere in the
+ *   search box, for every context; 0: the fp64 kernel; 1: D = 6, the 21 products of levels 5..10, for every batch of a context
+ *   whose GPs all have 1 + c / sigma_n^2 <= 128 (the rule reads theta alone; other contexts keep the fp64 kernel): the variance
+ *   within ~2e-11 relative of the fp64 kernel's, a log-posterior within ~1e-11 .. 2e-9 depending on how far its two terms
+ *   cancel; 2: D = 6 with the rule off (accuracy probes).  At cfg 4 D = 7 runs the predict launch in ~0.7 of the fp64 kernel's
+ *   time, D = 6 in ~0.5.
  *   Keys 26 / 32 (one rank's share of a sharded step on a single GPU: a measurement hook) take non-zero values in the debug build
  *   only (libgpbayes_debug.so: include/gpbayes_debug.h) and return GPB_E_ARG here.
  * gpb_debug_has_variants: 1 when the loaded library is that debug build (-DGPB_DEBUG_VARIANTS), 0 for the product library.

@@ -256,9 +256,11 @@ __global__ __launch_bounds__(256, 1) void k_sliced(const int8_t* __restrict__ A,
             __builtin_amdgcn_s_barrier();
             if (STAMP) stall += __builtin_amdgcn_s_memtime() - w0;
             __builtin_amdgcn_sched_barrier(0);
-            if (MODE & 1) dma_stage<D, WTM, WTN>(lds, s % 3, Ap, Bp, Np, Wld, mb, nb, 2 * (int64_t)(s + 3), wave, lane);
+            if ((MODE & 9) == 1) dma_stage<D, WTM, WTN>(lds, s % 3, Ap, Bp, Np, Wld, mb, nb, 2 * (int64_t)(s + 3), wave, lane);
             if (MODE & 2) read_frags<D, WTM, WTN>(nxt, lds, (s + 1) % 3, wm, wn, lane);
             if (MODE & 4) mma_step<D, LOW, WTM, WTN>(cur, acc);
+            // MODE bit 8: the DMA of stage s + 3 behind the step's MFMAs (the placement the 8-wave kernel keeps)
+            if ((MODE & 9) == 9) dma_stage<D, WTM, WTN>(lds, s % 3, Ap, Bp, Np, Wld, mb, nb, 2 * (int64_t)(s + 3), wave, lane);
             if (SCHED && (MODE & 4)) {
                 // NMMA MFMAs, NRD fragment reads, NPW DMAs: one memory instruction per MFMA while they last, DMAs first
                 if (MODE & 1) {
@@ -689,12 +691,12 @@ static double run(Problem& pr, int map, int RG, int CG, int reps, const char* na
 }
 
 // bit-exact check of the full loop against the host: exact integer level sums, the same fp64 epilogue
-template <int D, int LOW, int WTM, int WTN>
+template <int D, int LOW, int WTM, int WTN, int MODE = 7>
 static int check() {
     typedef Geo<D, WTM, WTN> G;
     constexpr int NLEV = 2 * D - 1 - LOW;
     Problem pr; make_problem(pr, 2, 256, 256, D, true);
-    run<D, LOW, WTM, WTN, 7>(pr, 0, 1, 1, 1, "check", false);
+    run<D, LOW, WTM, WTN, MODE, (MODE & 8) == 0>(pr, 0, 1, 1, 1, "check", false);
     std::vector<double> sp((size_t)(pr.Np / 64) * pr.P * pr.W);
     CK(hipMemcpy(sp.data(), pr.dsp, sp.size() * 8, hipMemcpyDeviceToHost));
     int bad = 0; double worst = 0;
@@ -815,6 +817,31 @@ static int check8() {
 
 int main(int argc, char** argv) {
     const int reps = argc > 1 ? atoi(argv[1]) : 10;
+    if (argc > 2 && !strcmp(argv[2], "d7")) {
+        // 28 products with the DMA of a step issued behind its MFMAs (round 6 measured D7 only with the DMA in front)
+        int bad = check<7, 6, 2, 1, 15>() + check8<7, 6, false, 1, 2>();
+        if (bad) { printf("layout or loop error: timings not taken\n"); return 1; }
+        {
+            Problem p6; make_problem(p6, 10, 2048, 2048, 6, false);
+            run8<6, 5, 7, false, 2, 7>(p6, 1, 8, 4, reps, "D6 8w 128x128 pos 7 (the library's)");
+            free_problem(p6);
+        }
+        Problem pr; make_problem(pr, 10, 2048, 2048, 7, false);
+        run<7, 6, 2, 1, 7, false>(pr, 1, 8, 4, reps, "D7 4w DMA first, superblk 8x4");
+        run<7, 6, 2, 1, 15, false>(pr, 1, 8, 4, reps, "D7 4w DMA behind MFMAs, superblk 8x4");
+        run<7, 6, 2, 1, 15, false>(pr, 1, 4, 8, reps, "D7 4w DMA behind MFMAs, superblk 4x8");
+        run8<7, 6, 7, false, 1, 2>(pr, 1, 8, 4, reps, "D7 8w DMA behind MFMAs, superblk 8x4");
+        run8<7, 6, 7, false, 1, 2>(pr, 1, 4, 8, reps, "D7 8w DMA behind MFMAs, superblk 4x8");
+        run8<7, 6, 7, false, 1, 1>(pr, 1, 8, 4, reps, "D7 8w DMA behind reads, superblk 8x4");
+        run<7, 6, 2, 1, 15, false>(pr, 1, 8, 4, reps, "D7 4w DMA behind MFMAs, 8x4 again");
+        run8<7, 6, 7, false, 1, 2>(pr, 1, 8, 4, reps, "D7 8w DMA behind MFMAs, 8x4 again");
+        run<7, 6, 2, 1, 4>(pr, 1, 8, 4, reps, "D7 4w MFMA only (random regs)");
+        free_problem(pr);
+        Problem p6; make_problem(p6, 10, 2048, 2048, 6, false);
+        run8<6, 5, 7, false, 2, 7>(p6, 1, 8, 4, reps, "D6 8w 128x128 pos 7 (the library's)");
+        free_problem(p6);
+        return 0;
+    }
     const bool all = argc > 2;
     int bad = 0;
     bad += check<7, 6, 2, 1>();
