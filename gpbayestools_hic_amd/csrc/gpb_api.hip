@@ -1058,8 +1058,6 @@ extern "C" int gpb_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, cons
 
 #endif  // GPB_DEBUG_VARIANTS
 
-// Launch-geometry knobs (never change a result); the key list is documented with the declaration in
-// include/gpbayes_debug.h and mirrored by GPEngine.tune() in engine.py.
 extern "C" int gpb_debug_has_variants(void) {
 #ifdef GPB_DEBUG_VARIANTS
     return 1;
@@ -1068,6 +1066,8 @@ extern "C" int gpb_debug_has_variants(void) {
 #endif
 }
 
+// Launch-geometry knobs and the arithmetic of the predict kernel; the key list is documented with the declaration in
+// include/gpbayes.h and mirrored by GPEngine.tune() in engine.py.
 extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
     if (!ctx) return GPB_E_ARG;
 #ifndef GPB_DEBUG_VARIANTS

@@ -268,6 +268,8 @@ int launch_kcross(gpb_ctx* ctx, const double* Xs_dev, int64_t W, const int* nrow
 int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, int64_t W, const int* nrows_dev);
 int launch_param_maps(gpb_ctx* const* ctxs, int n, const double* X_dev, int64_t W);      // gpb_pmap.hip
 int launch_vsq(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev);
+// rows of a compacted batch the last finished compaction suggests will be live (the tile rules), `rows` when nothing is known
+int64_t live_rows_estimate(const gpb_ctx* ctx, int64_t W, const int* nrows_dev, int64_t rows);
 int launch_finalize(gpb_ctx* ctx, int64_t W, bool need_var);
 // gpb_sliced.hip: the int8 form of launch_vsq's 128 x 128 launch for ONE context (rule: sliced_applies)
 int sliced_applies(const gpb_ctx* ctx);             // digit planes per operand (6, 7) the context's batches take, 0: the fp64 kernel

@@ -466,24 +466,49 @@ __device__ __forceinline__ bool decode_tile(int xcd_mode, unsigned t, unsigned q
     return true;
 }
 
+// The GP source of a predict launch (a template parameter of both kernels): GP g of the launch's G -> where its L^-1, K*^T and
+// partials live.  PredOne: one context's own launch, its raw pointers, GP g = the context's GP g.  PredTable: chains of several
+// emulators (Chain.emuList: nine emulators, 63 GPs in the reference's analyses) take ONE launch over the GPs of all emulators whose
+// designs pad to the same Np, instead of one launch per emulator with 6-8 GPs each and a partly filled chip behind every one of
+// them; the tile list is that of a single emulator with G = sum of P_e GPs, and entry g of the table (a kernel argument: at most
+// 96 GPs x 32 bytes) says where GP g lives.  A tile computes exactly what it computes in its emulator's own launch: same bits.
+struct PredGP {
+    const double* Linv;      // the emulator's [P_e][Np][Np]
+    const double* KsT;       // [P_e][Np][Wld]
+    double* spart;           // [Np / 64][P_e][Wld]
+    int P, p;                // GPs of the emulator, this GP's index in it
+};
+struct PredOne {
+    const double *Linv, *KsT;
+    double* spart;
+    __device__ PredGP at(int g, int G) const { return PredGP{Linv, KsT, spart, G, g}; }
+};
+constexpr int MAX_MULTI_GP = GPB_MAX_MULTI_GP;
+struct PredTable {
+    PredGP gp[MAX_MULTI_GP];
+    __device__ const PredGP& at(int g, int) const { return gp[g]; }
+};
+
+// compacted batch: only the walker tiles that hold rows exist.  The tile list (and with it the LPT order and the balance of the
+// eight queues) is rebuilt for them; the grid was sized for the whole batch, the surplus workgroups find their queues empty.
+template <int TN>
+__device__ __forceinline__ void live_tiles(const int* __restrict__ nrows, int xcd_mode, int G, int nI, int& nW, unsigned& nblocks) {
+    if (nrows) {
+        nW = (*nrows + TN - 1) / TN;
+        nblocks = (unsigned)((xcd_mode == 1 ? ((G * nI + 7) / 8) * 8 : G * nI) * nW);
+    }
+}
+
 // Persistent launch: `gridDim.x` workgroups (a few per CU) pull tile indices from device-scope ticket
 // queues in LPT order, so the triangular row blocks balance dynamically whatever the dispatcher does.
 // Exit condition: every workgroup walks all eight queues once and leaves each when its ticket is past
 // the queue's length; nothing spins.
-template <int T, int NW, int TN, int KB, bool PIPE = false>
-__global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (T == 64 && TN == 64 && NW == 4 ? 6 : 4))) void k_predict(const double* __restrict__ Linv, const double* __restrict__ KsT,
-                                                     double* __restrict__ spart, int64_t Np, int64_t Wld, int P,
-                                                     int nI, int nW, int xcd_mode, unsigned* __restrict__ queue,
-                                                     unsigned nblocks, unsigned* __restrict__ trace, int tri_skip,
-                                                     const int* __restrict__ nrows) {
+template <class Src, int T, int NW, int TN, int KB, bool PIPE>
+__global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (T == 64 && TN == 64 && NW == 4 ? 6 : 4))) void k_predict(
+    const Src src, int64_t Np, int64_t Wld, int G, int nI, int nW, int xcd_mode, unsigned* __restrict__ queue, unsigned nblocks,
+    unsigned* __restrict__ trace, int tri_skip, const int* __restrict__ nrows) {
     constexpr int prio_levels = 0;
-    if (nrows) {
-        // compacted batch: only the walker tiles that hold rows exist.  The tile list (and with it the LPT order and
-        // the balance of the eight queues) is rebuilt for them; the grid was sized for the whole batch, the surplus
-        // workgroups find their queues empty.
-        nW = (*nrows + TN - 1) / TN;
-        nblocks = (unsigned)((xcd_mode == 1 ? ((P * nI + 7) / 8) * 8 : P * nI) * nW);
-    }
+    live_tiles<TN>(nrows, xcd_mode, G, nI, nW, nblocks);
     __shared__ TileLds<T, TN, KB> lds;
     // The ticket lives in the padding of the last A row (never touched by the loaders, the MFMA fragment reads
     // or the epilogue's scratch): the operand tiles alone are an exact fraction of the CU's 160 KB LDS, and a
@@ -509,9 +534,10 @@ __global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (T == 64 && TN 
             const unsigned t = s_ticket;
             __syncthreads();                    // everyone has read the ticket before it is redrawn
             if (t >= nq) break;                 // uniform: this queue is exhausted
-            int p, ib, wt;
-            if (!decode_tile(xcd_mode, t, qx, nI, nW, P, p, ib, wt)) continue;   // padding (uniform)
-            predict_tile<T, NW, TN, KB, PIPE>(lds, p, ib, wt, Linv, KsT, spart, Np, Wld, P, prio_levels, trace, tri_skip);
+            int g, ib, wt;
+            if (!decode_tile(xcd_mode, t, qx, nI, nW, G, g, ib, wt)) continue;   // padding (uniform)
+            const PredGP& e = src.at(g, G);
+            predict_tile<T, NW, TN, KB, PIPE>(lds, e.p, ib, wt, e.Linv, e.KsT, e.spart, Np, Wld, e.P, prio_levels, trace, tri_skip);
         }
     }
     // the last workgroup to finish re-arms the queues for the next launch (all others are past their draws)
@@ -530,113 +556,34 @@ __global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (T == 64 && TN 
 // 2 = snake over the CUs (equal sums per CU), 3 = snake of neighbouring PAIRS (equal sums, and the two heaviest
 // tiles of a CU finish together).  Same tile -> queue maps as above; a separate kernel so that each has ONE
 // inlined copy of the tile body (with two copies the compiler parked the prefetch registers in scratch memory).
-template <int T, int NW, int TN, int KB, bool PIPE = false>
+__device__ __forceinline__ unsigned static_order(int order, unsigned t, unsigned nq, unsigned ncu_x) {
+    const unsigned k = t / ncu_x, c = t - k * ncu_x;
+    if (order == 2) {
+        if ((k & 1u) && (k + 1u) * ncu_x <= nq) t = k * ncu_x + (ncu_x - 1u - c);
+    } else if (order == 3) {
+        const unsigned n2 = (nq / (2u * ncu_x)) * (2u * ncu_x);
+        if (t < n2) {
+            const unsigned kp = k >> 1;
+            const unsigned pi = kp * ncu_x + ((kp & 1u) ? (ncu_x - 1u - c) : c);
+            t = 2u * pi + (k & 1u);
+        }
+    }
+    return t;
+}
+
+template <class Src, int T, int NW, int TN, int KB>
 __global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (KB == 32 ? 3 : 4))) void k_predict_static(
-    const double* __restrict__ Linv, const double* __restrict__ KsT, double* __restrict__ spart, int64_t Np, int64_t Wld,
-    int P, int nI, int nW, int xcd_mode, unsigned nblocks, int order, unsigned ncu_x, int prio_levels,
-    unsigned* __restrict__ trace, int tri_skip, const int* __restrict__ nrows) {
+    const Src src, int64_t Np, int64_t Wld, int G, int nI, int nW, int xcd_mode, unsigned nblocks, int order, unsigned ncu_x,
+    int prio_levels, unsigned* __restrict__ trace, int tri_skip, const int* __restrict__ nrows) {
     __shared__ TileLds<T, TN, KB> lds;
-    if (nrows) {                                       // compacted batch: the tile list of the live walker tiles only
-        nW = (*nrows + TN - 1) / TN;
-        nblocks = (unsigned)((xcd_mode == 1 ? ((P * nI + 7) / 8) * 8 : P * nI) * nW);
-    }
+    live_tiles<TN>(nrows, xcd_mode, G, nI, nW, nblocks);
     const unsigned qx = blockIdx.x & 7u;
     const unsigned nq = (nblocks > qx) ? (nblocks - qx + 7u) / 8u : 0u;
-    unsigned t = blockIdx.x >> 3;
+    const unsigned t = blockIdx.x >> 3;
     if (t >= nq) return;
-    const unsigned k = t / ncu_x, c = t - k * ncu_x;
-    if (order == 2) {
-        if ((k & 1u) && (k + 1u) * ncu_x <= nq) t = k * ncu_x + (ncu_x - 1u - c);
-    } else if (order == 3) {
-        const unsigned n2 = (nq / (2u * ncu_x)) * (2u * ncu_x);
-        if (t < n2) {
-            const unsigned kp = k >> 1;
-            const unsigned pi = kp * ncu_x + ((kp & 1u) ? (ncu_x - 1u - c) : c);
-            t = 2u * pi + (k & 1u);
-        }
-    }
-    int p, ib, wt;
-    if (decode_tile(xcd_mode, t, qx, nI, nW, P, p, ib, wt))
-        predict_tile<T, NW, TN, KB, PIPE>(lds, p, ib, wt, Linv, KsT, spart, Np, Wld, P, prio_levels, trace, tri_skip);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// Chains of several emulators (Chain.emuList: nine emulators, 63 GPs in the reference's analyses): ONE launch over the GPs
-// of all emulators whose designs pad to the same Np, instead of one launch per emulator with 6-8 GPs each and a partly
-// filled chip behind every one of them.  The tile list is that of a single emulator with G = sum of P_e GPs; entry g of
-// the table (a kernel argument: at most 96 GPs x 32 bytes) says where GP g's L^-1, K*^T and partials live.  A tile
-// computes exactly what it computes in its emulator's own launch: same bits.
-constexpr int MAX_MULTI_GP = GPB_MAX_MULTI_GP;
-struct PredGP {
-    const double* Linv;      // the emulator's [P_e][Np][Np]
-    const double* KsT;       // [P_e][Np][Wld]
-    double* spart;           // [Np / 64][P_e][Wld]
-    int P, p;                // GPs of the emulator, this GP's index in it
-};
-struct PredTable { PredGP gp[MAX_MULTI_GP]; };
-
-template <int T, int NW, int TN, int KB, bool PIPE = false>
-__global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (T == 64 && TN == 64 && NW == 4 ? 6 : 4))) void k_predict_multi(
-    const PredTable tab, int64_t Np, int64_t Wld, int G, int nI, int nW, int xcd_mode, unsigned* __restrict__ queue,
-    unsigned nblocks, unsigned* __restrict__ trace, int tri_skip, const int* __restrict__ nrows) {
-    if (nrows) {
-        nW = (*nrows + TN - 1) / TN;
-        nblocks = (unsigned)((xcd_mode == 1 ? ((G * nI + 7) / 8) * 8 : G * nI) * nW);
-    }
-    __shared__ TileLds<T, TN, KB> lds;
-    unsigned& s_ticket = *reinterpret_cast<unsigned*>(&lds.As[KB - 1][T + 12]);
-    const int x = blockIdx.x & 7;
-    for (int s = 0; s < 8; ++s) {                      // as k_predict: eight XCD-affine ticket queues, LPT order, stealing
-        const unsigned qx = (unsigned)((x + s) & 7);
-        const unsigned nq = (nblocks > qx) ? (nblocks - qx + 7u) / 8u : 0u;
-        for (;;) {
-            if (threadIdx.x == 0) s_ticket = atomicAdd(&queue[qx * 16], 1u);
-            __syncthreads();
-            const unsigned t = s_ticket;
-            __syncthreads();
-            if (t >= nq) break;
-            int g, ib, wt;
-            if (!decode_tile(xcd_mode, t, qx, nI, nW, G, g, ib, wt)) continue;
-            const PredGP& e = tab.gp[g];
-            predict_tile<T, NW, TN, KB, PIPE>(lds, e.p, ib, wt, e.Linv, e.KsT, e.spart, Np, Wld, e.P, 0, trace, tri_skip);
-        }
-    }
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&queue[128], 1u) == gridDim.x - 1) {
-            for (int i = 0; i < 8; ++i) queue[i * 16] = 0u;
-            queue[128] = 0u;
-        }
-    }
-}
-
-template <int T, int NW, int TN, int KB>
-__global__ __launch_bounds__(64 * NW, (T == 128 && NW == 4 ? 2 : (KB == 32 ? 3 : 4))) void k_predict_static_multi(
-    const PredTable tab, int64_t Np, int64_t Wld, int G, int nI, int nW, int xcd_mode, unsigned nblocks, int order,
-    unsigned ncu_x, int prio_levels, unsigned* __restrict__ trace, int tri_skip, const int* __restrict__ nrows) {
-    __shared__ TileLds<T, TN, KB> lds;
-    if (nrows) {
-        nW = (*nrows + TN - 1) / TN;
-        nblocks = (unsigned)((xcd_mode == 1 ? ((G * nI + 7) / 8) * 8 : G * nI) * nW);
-    }
-    const unsigned qx = blockIdx.x & 7u;
-    const unsigned nq = (nblocks > qx) ? (nblocks - qx + 7u) / 8u : 0u;
-    unsigned t = blockIdx.x >> 3;
-    if (t >= nq) return;
-    const unsigned k = t / ncu_x, c = t - k * ncu_x;
-    if (order == 2) {
-        if ((k & 1u) && (k + 1u) * ncu_x <= nq) t = k * ncu_x + (ncu_x - 1u - c);
-    } else if (order == 3) {
-        const unsigned n2 = (nq / (2u * ncu_x)) * (2u * ncu_x);
-        if (t < n2) {
-            const unsigned kp = k >> 1;
-            const unsigned pi = kp * ncu_x + ((kp & 1u) ? (ncu_x - 1u - c) : c);
-            t = 2u * pi + (k & 1u);
-        }
-    }
     int g, ib, wt;
-    if (decode_tile(xcd_mode, t, qx, nI, nW, G, g, ib, wt)) {
-        const PredGP& e = tab.gp[g];
+    if (decode_tile(xcd_mode, static_order(order, t, nq, ncu_x), qx, nI, nW, G, g, ib, wt)) {
+        const PredGP& e = src.at(g, G);
         predict_tile<T, NW, TN, KB, false>(lds, e.p, ib, wt, e.Linv, e.KsT, e.spart, Np, Wld, e.P, prio_levels, trace, tri_skip);
     }
 }
@@ -690,8 +637,12 @@ int ensure_wcap(gpb_ctx* ctx, int64_t W) {
     return 0;
 }
 
-template <int KIND>
-static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, int planes) {
+// launch geometry of the cross kernels over G GPs (one context's or a chain group's): walkers per lane, chunks per workgroup, grid
+struct KxGeo {
+    int wpl, cpw;
+    dim3 grid;
+};
+static int kcross_geometry(gpb_ctx* ctx, int64_t Wuse, int64_t G, const int* nrows_dev, KxGeo& geo) {
     const int nchunk = (int)((ctx->Np + KX_CHUNK - 1) / KX_CHUNK);
     // chunks per workgroup: as many as still leave >= 4 workgroups per CU (a geometry choice: the per-chunk
     // partials and their order do not depend on it; measured, cfg 4: 1 / 2 / 4 chunks at 512 / 1024 / 2048+ walkers)
@@ -703,14 +654,23 @@ static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int
         // compacted batches: about half of a stretch move's proposals from a spread-out ensemble are live (the count is
         // known on the device only); sizing the chunks per workgroup for the whole batch left 2.5 workgroups per CU
         const int64_t Wgeo = nrows_dev ? round_up(Wuse / 2, 64 * wpl) : Wuse;
-        const int64_t wgs1 = (Wgeo / (64 * wpl)) * nchunk * ctx->P;
+        const int64_t wgs1 = (Wgeo / (64 * wpl)) * nchunk * G;
         cpw = 1;
         while (cpw < 8 && wgs1 / (2 * cpw) >= 4 * (int64_t)ctx->num_cu) cpw *= 2;
     }
     // (grid.z, the walker tile, is limited to 65535: 4.19 M rows a call at one walker per lane; the host classes send long
     // inputs through in slabs of 131072 rows)
     if (Wuse / (64 * wpl) > 65535) GPB_FAIL(GPB_E_ARG, "gpb: more than 65535 walker tiles (4 million rows) in one batch: split it");
-    dim3 grid((unsigned)((nchunk + cpw - 1) / cpw), (unsigned)ctx->P, (unsigned)(Wuse / (64 * wpl)));
+    geo = KxGeo{wpl, cpw, dim3((unsigned)((nchunk + cpw - 1) / cpw), (unsigned)G, (unsigned)(Wuse / (64 * wpl)))};
+    return 0;
+}
+
+template <int KIND>
+static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, int planes) {
+    KxGeo geo;
+    if (const int rc = kcross_geometry(ctx, Wuse, ctx->P, nrows_dev, geo)) return rc;
+    const int wpl = geo.wpl, cpw = geo.cpw;
+    const dim3 grid = geo.grid;
     // two instantiations, one per distance form; each launch computes the GPs of its form (ctx->gpform, chosen from theta:
     // choose_forms) and is left out when no GP has it — the usual case is the Gram launch alone, with no form table to read
     const int* form = (ctx->n_diff > 0 && ctx->n_diff < ctx->P) ? ctx->gpform : nullptr;
@@ -833,17 +793,10 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
         G += (int)c->P;
     }
     tab.E = E;
-    const int nchunk = (int)((ctx->Np + KX_CHUNK - 1) / KX_CHUNK);
-    const int wpl = (ctx->kcross_wpl == 2 && ctx->dpad <= 32 && Wuse >= 256 && Wuse % 128 == 0) ? 2 : 1;
-    int cpw = ctx->kcross_chunks;
-    if (cpw <= 0) {                                    // as launch_kcross_kind, with the GPs of the whole group
-        const int64_t Wgeo = nrows_dev ? round_up(Wuse / 2, 64 * wpl) : Wuse;
-        const int64_t wgs1 = (Wgeo / (64 * wpl)) * nchunk * G;
-        cpw = 1;
-        while (cpw < 8 && wgs1 / (2 * cpw) >= 4 * (int64_t)ctx->num_cu) cpw *= 2;
-    }
-    if (Wuse / (64 * wpl) > 65535) GPB_FAIL(GPB_E_ARG, "gpb: more than 65535 walker tiles (4 million rows) in one batch: split it");
-    dim3 grid((unsigned)((nchunk + cpw - 1) / cpw), (unsigned)G, (unsigned)(Wuse / (64 * wpl)));
+    KxGeo geo;
+    if (const int rc = kcross_geometry(ctx, Wuse, G, nrows_dev, geo)) return rc;
+    const int wpl = geo.wpl, cpw = geo.cpw;
+    const dim3 grid = geo.grid;
 #define GPB_KXM(DP)                                                                                              \
     do {                                                                                                         \
         if (wpl == 2 && planes == 7)                                                                             \
@@ -879,201 +832,171 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
     return 0;
 }
 
+// Rows of a compacted batch the tile rules size their launches for.  A compacted batch is launched for its upper bound W, but the
+// tiles that exist are those of the rows inside the prior box.  Their number is only known on the device; the last compaction the
+// device has FINISHED left its (live rows, batch rows) in pinned host memory (k_compact_gather), and that fraction — a few launches
+// old, since the host enqueues ahead — scales W.  Any shape gives the same bits, so a stale fraction costs time at worst.  `rows`
+// when the batch is not compacted or nothing is known yet.
+int64_t live_rows_estimate(const gpb_ctx* ctx, int64_t W, const int* nrows_dev, int64_t rows) {
+    if (!nrows_dev || !ctx->tile_by_live || !ctx->hint_from || !ctx->hint_from->live_hint) return rows;
+    const unsigned long long h = __atomic_load_n(ctx->hint_from->live_hint, __ATOMIC_RELAXED);
+    const int64_t cnt = (int64_t)(h & 0xffffffffull), of = (int64_t)(h >> 32);
+    if (of <= 0 || cnt > of) return rows;
+    return (int64_t)((double)cnt / (double)of * (double)W * 1.03) + 8;
+}
+
+// T rows x TN walkers per tile of the fp64 launch over G GPs: the LARGEST shape of which enough tiles exist to fill the chip
+// (measured, cfg 3 and cfg 4 sweeps at 128..2048 walkers, profiles/r01_tile_shape_sweep.txt): 128x128 (2 per CU, 64 MFMAs per
+// wave between barriers) from 3.75 tiles per CU on, 64x128 (32 MFMAs) and 64x64 (16) from 5 per CU, else 64x32.  Fewer, larger
+// tiles leave CUs idle behind the heaviest triangular row block; more, smaller ones pay more barriers and operand traffic per MFMA.
+// Compacted batches count the live rows (cfg 4 sharded 2-way: 1024-row batches with ~495 live rows ran 128x128 tiles at 2.5 per
+// CU, 436 us; with the rule fed the live count 64x128).
+static std::pair<int, int> predict_tile_shape(const gpb_ctx* ctx, int64_t G, int64_t W, const int* nrows_dev) {
+    const int64_t Wuse = round_up(W, WPAD), nI64 = ctx->Np / 64;
+    const int64_t est = live_rows_estimate(ctx, W, nrows_dev, Wuse);
+    const int64_t Wsel = est < 64 ? 64 : (est > Wuse ? Wuse : est);
+    const int64_t tiles128 = G * ((ctx->Np + 127) / 128) * ((Wsel + 127) / 128);
+    const int64_t tiles64x128 = G * nI64 * ((Wsel + 127) / 128), tiles64 = G * nI64 * ((Wsel + 63) / 64);
+    // Compacted batches have their own switch points (tools/gpu_shard_sim.py --walkers=.. --tune=force_tile:..,
+    // profiles/r02_tile_shape_sweep_compacted.txt, cfg 4 at 190 .. 2060 live rows): the larger shape pays later —
+    // 64x32 up to 9.4 tiles of 64x64 per CU (5), 64x64 up to 4.5 of 64x128 (5), 64x128 up to 9.4 of 128x128 (3.75).
+    const bool cmpd = nrows_dev != nullptr && ctx->tile_by_live;
+    const int64_t sw128 = cmpd ? ctx->tile_switch_c : ctx->tile_switch, swmid = cmpd ? ctx->mid_switch_c : ctx->mid_switch,
+                  swnarrow = cmpd ? ctx->narrow_switch_c : ctx->narrow_switch;
+    int T = 64, TN = 32;
+    if (cmpd) {
+        // ... counted in fractions of a walker tile: the estimate wanders by a few rows from launch to launch, and
+        // a whole-tile count made a rank's ~495 live rows flip between 4 and 5 tiles of 128, i.e. between two shapes
+        const double f128 = (double)(G * ((ctx->Np + 127) / 128)) * (double)Wsel / 128.0 * 256.0 / ctx->num_cu;
+        const double f64 = (double)(G * nI64) * (double)Wsel / 64.0 * 256.0 / ctx->num_cu;
+        // ... and the 64x32 / 64x64 switch point moves with the design size below N = 2048: a tile's K loop is half as
+        // long at N = 1024 and its fixed cost (first loads, reduction, barriers) weighs twice as much, so the wider tile pays
+        // from half as many tiles on (tools/gpu_tile_rule_sweep.py, profiles/r03_tile_rule_sweep.txt: cfg 3 at 512 live
+        // rows 64x64 0.263 ms/step against 64x32 0.287; at 256 rows 64x32 0.179 against 0.199)
+        const double nscale = ctx->Np < 2048 ? (double)ctx->Np / 2048.0 : 1.0;
+        if (f128 >= (double)sw128) T = TN = 128;
+        else if (f64 * 0.5 >= (double)swmid / nscale) TN = 128;          // (N = 1024: 64x128 from twice as many tiles on)
+        else if (f64 >= (double)swnarrow * nscale) TN = 64;
+    } else if (tiles128 * 256 >= sw128 * ctx->num_cu) T = TN = 128;
+    else if (tiles64x128 * 256 >= swmid * ctx->num_cu) TN = 128;
+    else if (tiles64 * 256 >= swnarrow * ctx->num_cu) TN = 64;
+    if (ctx->force_tile == 64 || ctx->force_tile == 128) T = TN = ctx->force_tile;
+    if (ctx->force_tile == 32) { T = 64; TN = 32; }
+    if (ctx->force_tile == 65) { T = 64; TN = 128; }        // 64 rows x 128 walkers
+    return {T, TN};
+}
+
+// The fp64 launch over the G GPs of `src` (PredOne: a context's own, PredTable: a chain's shared launch).  The persistent 128 x 128
+// launch: two workgroups per CU (their registers), or one per tile when fewer tiles exist; the 64-row shapes launch static, one
+// workgroup per tile in weight order — beyond co-residency the hardware dispatcher hands the next workgroup to whichever CU frees a
+// slot, which balances as well as ticket queues do (7-12 % faster at 384-768 walkers).
+template <class Src>
+static void predict_launch(gpb_ctx* ctx, const Src& src, int G, int64_t W, int tri_arg, const int* nrows_dev) {
+    const auto [T, TN] = predict_tile_shape(ctx, G, W, nrows_dev);
+    const int64_t Wuse = round_up(W, WPAD);
+    const int nI = (T == 128) ? (int)((ctx->Np + 127) / 128) : (int)(ctx->Np / 64), nW = (int)(Wuse / TN);
+    // which operand is larger decides the XCD affinity: L^-1 (P Np^2/2) or K*^T (P Np W)
+    const int xcd = ctx->force_xcd >= 0 ? ctx->force_xcd : (2 * Wuse < ctx->Np ? 1 : 0);      // (force_xcd: 0 or 1)
+    const int64_t ngroups = (int64_t)G * nI;
+    const unsigned nblocks = (unsigned)(xcd == 1 ? ((ngroups + 7) / 8) * 8 * nW : ngroups * nW);
+    if (T == 128) {
+        const unsigned slots = 2u * (unsigned)ctx->num_cu;
+        hipLaunchKernelGGL((k_predict<Src, 128, 4, 128, 16, true>), dim3(nblocks < slots ? nblocks : slots), dim3(256), 0, ctx->stream,
+                           src, ctx->Np, ctx->Wld, G, nI, nW, xcd, ctx->tile_counter, nblocks, ctx->tile_trace, tri_arg, nrows_dev);
+        return;
+    }
+    const int order = ctx->resident_order ? ctx->resident_order : 2;
+#define GPB_PRED(NN)                                                                                                       \
+    hipLaunchKernelGGL((k_predict_static<Src, 64, 4, NN, 16>), dim3(nblocks), dim3(256), 0, ctx->stream, src, ctx->Np, ctx->Wld, \
+                       G, nI, nW, xcd, nblocks, order, (unsigned)(ctx->num_cu / 8), ctx->tile_priority ? nI : 0, ctx->tile_trace, \
+                       tri_arg, nrows_dev)
+    if (TN == 32) GPB_PRED(32);
+    else if (TN == 128) GPB_PRED(128);
+    else GPB_PRED(64);
+#undef GPB_PRED
+}
+
+// V = L^-1 K*^T and its partials for E contexts of one shape whose batches are all fp64 or all digit planes of one depth, in one
+// launch, untimed
+static int vsq_launch(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev) {
+    gpb_ctx* ctx = ctxs[0];
+    const int64_t Wuse = round_up(W, WPAD);
+    // leading all-zero rows of K*^T (the designs' padding, in front: gp_set_impl) common to every context of the launch, in whole
+    // 16-deep K-steps: the tiles start their K loops behind them
+    int64_t G = 0, kskip = ctx->Np;
+    for (int e = 0; e < E; ++e) {
+        if (ctxs[e]->Np != ctx->Np || ctxs[e]->Wld != Wuse || ctxs[e]->stream != ctx->stream)
+            GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq over contexts of different shape");
+        G += ctxs[e]->P;
+        kskip = imin64(kskip, pad_front(ctxs[e]->Np, ctxs[e]->N));
+    }
+    if (E > 1 && G > MAX_MULTI_GP) GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq: too many GPs for one table");
+    // the int8 kernel (option key 51, gpb_sliced.hip) on the digit planes k_kcross left: same partials' layout and meaning
+    if (ctx->batch_sliced)
+        return E > 1 ? launch_vsq_sliced_multi(ctxs, E, W, nrows_dev, (int)kskip) : launch_vsq_sliced(ctx, W, nrows_dev, (int)kskip);
+    const int tri_arg = (ctx->tri_skip ? 1 : 0) | ((int)kskip << 8);
+    if (E == 1) {
+        predict_launch(ctx, PredOne{ctx->Linv, ctx->KsT, ctx->spart}, (int)G, W, tri_arg, nrows_dev);
+        return 0;
+    }
+    PredTable tab;
+    int g = 0;
+    for (int e = 0; e < E; ++e)
+        for (int pp = 0; pp < (int)ctxs[e]->P; ++pp, ++g) tab.gp[g] = PredGP{ctxs[e]->Linv, ctxs[e]->KsT, ctxs[e]->spart, (int)ctxs[e]->P, pp};
+    predict_launch(ctx, tab, (int)G, W, tri_arg, nrows_dev);
+    return 0;
+}
+
+// live HIP-event timing of the dominant kernel (bench.py) into ctx: prof_begin before a launch over `gps` GPs, prof_end after it
+static int prof_begin(gpb_ctx* ctx, hipEvent_t& e0) {
+    e0 = nullptr;
+    if (ctx->profile) {
+        GPB_HIP(hipEventCreate(&e0));
+        GPB_HIP(hipEventRecord(e0, ctx->stream));
+    }
+    return 0;
+}
+static int prof_end(gpb_ctx* ctx, hipEvent_t e0, int64_t gps, int64_t W, const int* nrows_dev) {
+    if (!ctx->profile) return 0;
+    hipEvent_t e1 = nullptr;
+    GPB_HIP(hipEventCreate(&e1));
+    GPB_HIP(hipEventRecord(e1, ctx->stream));
+    ctx->prof_events.push_back({e0, e1});
+    ctx->prof_gps = (double)gps;                   // GPs per timed interval (a chain: all of them)
+    if (!nrows_dev) ctx->prof_units += (double)gps * (double)W;          // compacted: counted on the device
+    else ctx->prof_compacted = true;
+    return 0;
+}
+
 // V = L^-1 K*^T with the fused sum of squares for the GPs of E contexts in one launch (E = 1: an emulator's own launch;
-// E > 1: the emulators of a chain whose designs pad to the same Np — see k_predict_multi).  All contexts: same Np, same
+// E > 1: the emulators of a chain whose designs pad to the same Np — see PredTable).  All contexts: same Np, same
 // batch (launch_kcross done), same stream.  Timing events and the unit count go to ctxs[0].
 int launch_vsq(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_dev) {
     gpb_ctx* ctx = ctxs[0];
     const int64_t Wuse = round_up(W, WPAD);
-    if (E > 1) {
-        // option key 51: contexts whose batch exists as int8 digit planes take their own launches (see launch_kcross_group);
-        // the timing events of the whole group still go to ctxs[0]
-        bool any_sliced = false, all_sliced = true;
-        int gsum = 0;
-        for (int e = 0; e < E; ++e) {
-            any_sliced = any_sliced || ctxs[e]->batch_sliced;
-            all_sliced = all_sliced && ctxs[e]->batch_sliced && ctxs[e]->batch_sliced == ctx->batch_sliced && ctxs[e]->Np == ctx->Np && ctxs[e]->Wld == Wuse && ctxs[e]->stream == ctx->stream;
-            gsum += (int)ctxs[e]->P;
-        }
-        if (all_sliced && gsum <= MAX_MULTI_GP) {       // one int8 launch over the GPs of all the emulators
-            int64_t ks = ctx->Np;
-            for (int e = 0; e < E; ++e) ks = imin64(ks, pad_front(ctxs[e]->Np, ctxs[e]->N));
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (ctx->profile) {
-                GPB_HIP(hipEventCreate(&e0)); GPB_HIP(hipEventCreate(&e1));
-                GPB_HIP(hipEventRecord(e0, ctx->stream));
-            }
-            const int rc = launch_vsq_sliced_multi(ctxs, E, W, nrows_dev, (int)ks);
-            if (rc) return rc;
-            if (ctx->profile) {
-                GPB_HIP(hipEventRecord(e1, ctx->stream));
-                ctx->prof_events.push_back({e0, e1});
-                ctx->prof_gps = (double)gsum;
-                if (!nrows_dev) ctx->prof_units += (double)gsum * (double)W;
-                else ctx->prof_compacted = true;
-            }
-            GPB_HIP(hipGetLastError());
-            return 0;
-        }
-        if (any_sliced) {
-            for (int e = 0; e < E; ++e) {
-                gpb_ctx* one[1] = {ctxs[e]};
-                const bool prof = ctxs[e]->profile;
-                ctxs[e]->profile = ctx->profile;
-                const int rc = launch_vsq(one, 1, W, nrows_dev);
-                if (ctxs[e] != ctx) {
-                    for (auto& ev : ctxs[e]->prof_events) ctx->prof_events.push_back(ev);
-                    ctxs[e]->prof_events.clear();
-                    ctx->prof_units += ctxs[e]->prof_units; ctxs[e]->prof_units = 0.0;
-                    ctx->prof_compacted = ctx->prof_compacted || ctxs[e]->prof_compacted; ctxs[e]->prof_compacted = false;
-                    ctxs[e]->profile = prof;
-                }
-                if (rc) { ctx->err = ctxs[e]->err; return rc; }
-            }
-            return 0;
-        }
-    }
-    int64_t Gsum = 0;
+    bool any_sliced = false, all_sliced = true;
+    int64_t G = 0;
     for (int e = 0; e < E; ++e) {
-        if (ctxs[e]->Np != ctx->Np || ctxs[e]->Wld != Wuse || ctxs[e]->stream != ctx->stream)
-            GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq over contexts of different shape");
-        Gsum += ctxs[e]->P;
+        any_sliced = any_sliced || ctxs[e]->batch_sliced;
+        all_sliced = all_sliced && ctxs[e]->batch_sliced == ctx->batch_sliced && ctxs[e]->Np == ctx->Np && ctxs[e]->Wld == Wuse &&
+                     ctxs[e]->stream == ctx->stream;
+        G += ctxs[e]->P;
     }
-    const bool multi = E > 1;
-    // leading all-zero rows of K*^T (the designs' padding, in front: gp_set_impl) common to every context of the launch, in whole
-    // 16-deep K-steps: the tiles start their K loops behind them
-    int64_t kskip = ctx->Np;
-    for (int e = 0; e < E; ++e) kskip = imin64(kskip, pad_front(ctxs[e]->Np, ctxs[e]->N));
-    const int tri_arg = (ctx->tri_skip ? 1 : 0) | ((int)kskip << 8);
-    if (multi && Gsum > MAX_MULTI_GP) GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq: too many GPs for one table");
-    const int64_t GP = Gsum;                           // GPs of the launch: what the tile counts are made of
-    const int nI64 = (int)(ctx->Np / 64);
-    {
-        // T rows x TN walkers per tile: the LARGEST shape of which enough tiles exist to fill the chip (measured,
-        // cfg 3 and cfg 4 sweeps at 128..2048 walkers, profiles/r01_tile_shape_sweep.txt): 128x128 (2 per CU, 64
-        // MFMAs per wave between barriers) from 3.75 tiles per CU on, 64x128 (32 MFMAs) and 64x64 (16) from 5 per
-        // CU, else 64x32.  Fewer, larger tiles leave CUs idle behind the heaviest triangular row block; more,
-        // smaller ones pay more barriers and operand traffic per MFMA.
-        // A compacted batch is launched for its upper bound W, but the tiles that exist are those of the rows inside
-        // the prior box.  Their number is only known on the device; the last compaction the device has FINISHED left
-        // its (live rows, batch rows) in pinned host memory (k_compact_gather), and that fraction — a few launches
-        // old, since the host enqueues ahead — sizes the tile counts of the rule.  Any shape gives the same bits, so a
-        // stale fraction costs time at worst.  (cfg 4 sharded 2-way: 1024-row batches with ~495 live rows ran 128x128
-        // tiles at 2.5 per CU, 436 us; with the rule fed the live count 64x128.)
-        int64_t Wsel = Wuse;
-        if (nrows_dev && ctx->tile_by_live && ctx->hint_from && ctx->hint_from->live_hint) {
-            const unsigned long long h = __atomic_load_n(ctx->hint_from->live_hint, __ATOMIC_RELAXED);
-            const int64_t cnt = (int64_t)(h & 0xffffffffull), of = (int64_t)(h >> 32);
-            if (of > 0 && cnt <= of) {
-                const int64_t est = (int64_t)((double)cnt / (double)of * (double)W * 1.03) + 8;
-                Wsel = est < 64 ? 64 : (est > Wuse ? Wuse : est);
-            }
+    hipEvent_t e0;
+    int rc;
+    if (E > 1 && any_sliced && !(all_sliced && G <= MAX_MULTI_GP)) {
+        // option key 51: a group whose batches are not all int8 digit planes of one depth takes one launch per context, each in
+        // its own form (see launch_kcross_group)
+        for (int e = 0; e < E; ++e) {
+            if ((rc = prof_begin(ctx, e0))) return rc;
+            if ((rc = vsq_launch(ctxs + e, 1, W, nrows_dev))) { ctx->err = ctxs[e]->err; return rc; }
+            if ((rc = prof_end(ctx, e0, ctxs[e]->P, W, nrows_dev))) return rc;
         }
-        const int64_t tiles128 = GP * ((ctx->Np + 127) / 128) * ((Wsel + 127) / 128);
-        const int64_t tiles64x128 = GP * nI64 * ((Wsel + 127) / 128), tiles64 = GP * nI64 * ((Wsel + 63) / 64);
-        // Compacted batches have their own switch points (tools/gpu_shard_sim.py --walkers=.. --tune=force_tile:..,
-        // profiles/r02_tile_shape_sweep_compacted.txt, cfg 4 at 190 .. 2060 live rows): the larger shape pays later —
-        // 64x32 up to 9.4 tiles of 64x64 per CU (5), 64x64 up to 4.5 of 64x128 (5), 64x128 up to 9.4 of 128x128 (3.75).
-        const bool cmpd = nrows_dev != nullptr && ctx->tile_by_live;
-        const int64_t sw128 = cmpd ? ctx->tile_switch_c : ctx->tile_switch, swmid = cmpd ? ctx->mid_switch_c : ctx->mid_switch,
-                      swnarrow = cmpd ? ctx->narrow_switch_c : ctx->narrow_switch;
-        int T = 64, TN = 32;
-        if (cmpd) {
-            // ... counted in fractions of a walker tile: the estimate wanders by a few rows from launch to launch, and
-            // a whole-tile count made a rank's ~495 live rows flip between 4 and 5 tiles of 128, i.e. between two shapes
-            const double f128 = (double)(GP * ((ctx->Np + 127) / 128)) * (double)Wsel / 128.0 * 256.0 / ctx->num_cu;
-            const double f64 = (double)(GP * nI64) * (double)Wsel / 64.0 * 256.0 / ctx->num_cu;
-            // ... and the 64x32 / 64x64 switch point moves with the design size below N = 2048: a tile's K loop is half as
-            // long at N = 1024 and its fixed cost (first loads, reduction, barriers) weighs twice as much, so the wider tile pays
-            // from half as many tiles on (tools/gpu_tile_rule_sweep.py, profiles/r03_tile_rule_sweep.txt: cfg 3 at 512 live
-            // rows 64x64 0.263 ms/step against 64x32 0.287; at 256 rows 64x32 0.179 against 0.199)
-            const double nscale = ctx->Np < 2048 ? (double)ctx->Np / 2048.0 : 1.0;
-            if (f128 >= (double)sw128) T = TN = 128;
-            else if (f64 * 0.5 >= (double)swmid / nscale) TN = 128;          // (N = 1024: 64x128 from twice as many tiles on)
-            else if (f64 >= (double)swnarrow * nscale) TN = 64;
-        } else if (tiles128 * 256 >= sw128 * ctx->num_cu) T = TN = 128;
-        else if (tiles64x128 * 256 >= swmid * ctx->num_cu) TN = 128;
-        else if (tiles64 * 256 >= swnarrow * ctx->num_cu) TN = 64;
-        if (ctx->force_tile == 64 || ctx->force_tile == 128) T = TN = ctx->force_tile;
-        if (ctx->force_tile == 32) { T = 64; TN = 32; }
-        if (ctx->force_tile == 65) { T = 64; TN = 128; }        // 64 rows x 128 walkers
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (ctx->profile) {                    // live HIP-event timing of the dominant kernel (bench.py)
-            GPB_HIP(hipEventCreate(&e0));
-            GPB_HIP(hipEventRecord(e0, ctx->stream));
-            GPB_HIP(hipEventCreate(&e1));
-        }
-        const int nI = (T == 128) ? (int)((ctx->Np + 127) / 128) : nI64, nW = (int)(Wuse / TN);
-        // which operand is larger decides the XCD affinity: L^-1 (P Np^2/2) or K*^T (P Np W)
-        int xcd_rows = (2 * Wuse < ctx->Np) ? 1 : 0;
-        if (ctx->force_xcd >= 0) xcd_rows = ctx->force_xcd;      // 0 or 1
-        const int64_t ngroups = GP * nI;
-        const int64_t nblocks = (xcd_rows == 1) ? ((ngroups + 7) / 8) * 8 * nW : ngroups * nW;
-        // the persistent 128 x 128 launch: two workgroups per CU (their registers), or one per tile when fewer tiles exist; the
-        // 64-row shapes launch static, one workgroup per tile in weight order — beyond co-residency the hardware dispatcher hands the
-        // next workgroup to whichever CU frees a slot, which balances as well as ticket queues do (7-12 % faster at 384-768 walkers)
-        const int64_t slots = (int64_t)ctx->num_cu * 2;
-        const unsigned grid128 = (unsigned)(nblocks < slots ? nblocks : slots);
-        if (ctx->batch_sliced) {
-            // the int8 kernel (option key 51, gpb_sliced.hip) on the digit planes k_kcross left: same partials' layout and meaning
-            if (multi) GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq: a sliced batch in a shared launch");
-            const int rc = launch_vsq_sliced(ctx, W, nrows_dev, (int)kskip);
-            if (rc) return rc;
-        } else if (multi) {
-            // one launch over the GPs of all the emulators (see k_predict_multi): the product shapes only
-            PredTable tab;
-            int g = 0;
-            for (int e = 0; e < E; ++e)
-                for (int pp = 0; pp < (int)ctxs[e]->P; ++pp, ++g)
-                    tab.gp[g] = PredGP{ctxs[e]->Linv, ctxs[e]->KsT, ctxs[e]->spart, (int)ctxs[e]->P, pp};
-            const int order = ctx->resident_order ? ctx->resident_order : 2;
-            const int xr = xcd_rows;
-            const unsigned nb_s = (unsigned)nblocks;
-            if (T == 128)
-                hipLaunchKernelGGL((k_predict_multi<128, 4, 128, 16, true>), dim3(grid128),
-                                   dim3(256), 0, ctx->stream, tab, ctx->Np, ctx->Wld, (int)GP, nI, nW, xcd_rows,
-                                   ctx->tile_counter, (unsigned)nblocks, ctx->tile_trace, tri_arg, nrows_dev);
-            else if (TN == 32)
-                hipLaunchKernelGGL((k_predict_static_multi<64, 4, 32, 16>), dim3(nb_s), dim3(256), 0, ctx->stream, tab, ctx->Np,
-                                   ctx->Wld, (int)GP, nI, nW, xr, nb_s, order, (unsigned)(ctx->num_cu / 8),
-                                   ctx->tile_priority ? nI : 0, ctx->tile_trace, tri_arg, nrows_dev);
-            else if (TN == 128)
-                hipLaunchKernelGGL((k_predict_static_multi<64, 4, 128, 16>), dim3(nb_s), dim3(256), 0, ctx->stream, tab, ctx->Np,
-                                   ctx->Wld, (int)GP, nI, nW, xr, nb_s, order, (unsigned)(ctx->num_cu / 8),
-                                   ctx->tile_priority ? nI : 0, ctx->tile_trace, tri_arg, nrows_dev);
-            else
-                hipLaunchKernelGGL((k_predict_static_multi<64, 4, 64, 16>), dim3(nb_s), dim3(256), 0, ctx->stream, tab, ctx->Np,
-                                   ctx->Wld, (int)GP, nI, nW, xr, nb_s, order, (unsigned)(ctx->num_cu / 8),
-                                   ctx->tile_priority ? nI : 0, ctx->tile_trace, tri_arg, nrows_dev);
-        } else {
-        // the shapes the rule can select: the persistent 128x128 tile with the fragment read-ahead (ticket queues) and the static
-        // 64-row tiles (64x128, 64x64, 64x32; order 1-3, XCD map 0/1)
-        if (T == 128) {
-            hipLaunchKernelGGL((k_predict<128, 4, 128, 16, true>), dim3(grid128), dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT,
-                               ctx->spart, ctx->Np, ctx->Wld, (int)ctx->P, nI, nW, xcd_rows, ctx->tile_counter,
-                               (unsigned)nblocks, ctx->tile_trace, tri_arg, nrows_dev);
-        } else {
-            const int order = ctx->resident_order ? ctx->resident_order : 2;
-            const int xr = xcd_rows;
-#define GPB_PRED(NN)                                                                                                \
-    hipLaunchKernelGGL((k_predict_static<64, 4, NN, 16>), dim3((unsigned)(xr == 1 ? ((ngroups + 7) / 8) * 8 * nW : ngroups * nW)), \
-                       dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, ctx->spart, ctx->Np, ctx->Wld, (int)ctx->P, nI, nW, xr, \
-                       (unsigned)(xr == 1 ? ((ngroups + 7) / 8) * 8 * nW : ngroups * nW), order, (unsigned)(ctx->num_cu / 8), \
-                       ctx->tile_priority ? nI : 0, ctx->tile_trace, tri_arg, nrows_dev)
-            if (TN == 32) GPB_PRED(32);
-            else if (TN == 128) GPB_PRED(128);
-            else GPB_PRED(64);
-        }
-        }
-#undef GPB_PRED
-        if (ctx->profile) {
-            GPB_HIP(hipEventRecord(e1, ctx->stream));
-            ctx->prof_events.push_back({e0, e1});
-            // GPs per timed interval (a chain: all of them; a pair of launches: both groups')
-            ctx->prof_gps = (double)GP;
-            if (!nrows_dev) ctx->prof_units += (double)GP * (double)W;          // compacted: counted on the device
-            else ctx->prof_compacted = true;
-        }
+        if (ctx->profile) ctx->prof_gps = (double)G;
+    } else {
+        if ((rc = prof_begin(ctx, e0))) return rc;
+        if ((rc = vsq_launch(ctxs, E, W, nrows_dev))) return rc;
+        if ((rc = prof_end(ctx, e0, G, W, nrows_dev))) return rc;
     }
     GPB_HIP(hipGetLastError());
     return 0;

@@ -405,13 +405,7 @@ int sliced_read_kstar(gpb_ctx* ctx, int64_t p, int64_t pad, int64_t N, int64_t W
 // 653 / 344 / 220 / 217 against 757 / 375 / 206 / 136); either shape gives the same bits
 static int sliced_wtn(const gpb_ctx* ctx, int depth, int64_t gps, int nI, int64_t W, const int* nrows_dev) {
     if (depth == 7) return 1;
-    const int64_t Wld = ctx->Wld;
-    int64_t Wsel = Wld;
-    if (nrows_dev && ctx->tile_by_live && ctx->hint_from && ctx->hint_from->live_hint) {
-        const unsigned long long h = __atomic_load_n(ctx->hint_from->live_hint, __ATOMIC_RELAXED);
-        const int64_t cnt = (int64_t)(h & 0xffffffffull), of = (int64_t)(h >> 32);
-        if (of > 0 && cnt <= of) Wsel = imin64(Wld, (int64_t)((double)cnt / (double)of * (double)W * 1.03) + 8);
-    }
+    const int64_t Wsel = imin64(ctx->Wld, live_rows_estimate(ctx, W, nrows_dev, ctx->Wld));
     const int64_t tiles128 = gps * nI * ((Wsel + 127) / 128);
     int wtn = tiles128 >= 3 * (int64_t)ctx->num_cu ? 2 : 1;
     if (ctx->force_tile == 128) wtn = 2;

@@ -344,18 +344,24 @@ def test_predict_tile_sizes_are_bit_identical(request, library):
         eng.set_data(X, rng.standard_normal((P, N)), "RBF", 0.1)
         eng.set_theta(synth.fixed_theta(d, P)); eng.factor()
         Xs = rng.random((300, d))
-        eng.force_tile(128); m1, v1 = eng.predict(Xs)
-        # the shapes the rule selects: 128x128 on ticket queues; 64x128, 64x64, 64x32 as static launches in three orders, two XCD
-        # maps (the measured-and-rejected variants — 8-wave tiles, ticket queues for the 64-row tiles, folded row-block pairs,
-        # LDS-DMA staging of the fp64 tiles, two more XCD maps — were deleted in round 6: profiles/HISTORY.md)
-        for xcd in (0, 1):                                # tile -> XCD queue maps only reorder the work
-            eng.tune("xcd", xcd)
-            for tile in (64, 128, 32, 65):                # 32 = 64 rows x 32 walkers, 65 = 64 x 128
-                eng.force_tile(tile)
-                for order in (1, 2, 3):                   # static orders of the 64-row launches
-                    eng.tune("resident", order)
-                    m2, v2 = eng.predict(Xs)
-                    assert np.array_equal(m1, m2) and np.array_equal(v1, v2), (tile, xcd, order)
+        # the fp64 kernel (k_predict / k_predict_static): the int8 kernel the default selects ignores tile, order and XCD map
+        arith = eng.predict_sliced
+        eng.tune("predict_sliced", 0)
+        try:
+            eng.force_tile(128); m1, v1 = eng.predict(Xs)
+            # the shapes the rule selects: 128x128 on ticket queues; 64x128, 64x64, 64x32 as static launches in three orders, two
+            # XCD maps (the measured-and-rejected variants — 8-wave tiles, ticket queues for the 64-row tiles, folded row-block
+            # pairs, LDS-DMA staging of the fp64 tiles, two more XCD maps — were deleted in round 6: profiles/HISTORY.md)
+            for xcd in (0, 1):                            # tile -> XCD queue maps only reorder the work
+                eng.tune("xcd", xcd)
+                for tile in (64, 128, 32, 65):            # 32 = 64 rows x 32 walkers, 65 = 64 x 128
+                    eng.force_tile(tile)
+                    for order in (1, 2, 3):               # static orders of the 64-row launches
+                        eng.tune("resident", order)
+                        m2, v2 = eng.predict(Xs)
+                        assert np.array_equal(m1, m2) and np.array_equal(v1, v2), (tile, xcd, order)
+        finally:
+            eng.tune("predict_sliced", arith)
         eng.tune("xcd", -1); eng.tune("resident", 2)
         from gpbayestools_hic_amd._native import GPBError
         for key, val in (("xcd", 2), ("resident", 0)):
