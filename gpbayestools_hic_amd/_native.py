@@ -71,6 +71,9 @@ BOUNDARY = {
     "gpb_chain_logpost_grad": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, VP, C.c_double, C.c_double]),
     "gpb_chain_ptlmc_run": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_i64, c_u64, c_u64, c_i64, C.c_double, VP, VP, VP, VP,
                                       VP, VP, VP, VP, VP, VP, C.c_double, C.c_double, VP, c_i64, VP, VP]),
+    "gpb_chain_smc_reweight": (C.c_int, [VP, C.c_int, c_i64, c_u64, c_u64, C.c_double, VP, VP, VP, VP, VP, VP]),
+    "gpb_chain_smc_move": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_u64, c_u64, c_u64, VP, VP, VP, VP, VP, VP, C.c_double,
+                                     C.c_double]),
     "gpb_dist_available": (C.c_int, []),
     "gpb_dist_uid": (C.c_int, [VP]),
     "gpb_dist_init": (C.c_int, [VP, C.c_int, C.c_int, VP]),
@@ -87,6 +90,7 @@ DEBUG = {
     "gpb_test_philox": (C.c_int, [VP, c_i64, VP, VP]),
     "gpb_test_stretch_draws": (C.c_int, [VP, c_i64, C.c_int, c_u64, c_u64, C.c_int, VP, VP, VP, VP]),
     "gpb_test_ptlmc_draws": (C.c_int, [VP, c_i64, c_i64, c_u64, c_u64, VP, VP, VP, VP]),
+    "gpb_test_smc_draws": (C.c_int, [VP, c_i64, c_i64, c_u64, c_u64, c_u64, VP, VP, VP]),
     "gpb_test_gemm": (C.c_int, [VP, c_i64, c_i64, c_i64, VP, VP, VP, C.c_int]),
     "gpb_debug_loopback_group": (C.c_int, [VP, C.c_int]),
     "gpb_debug_loopback_release": (C.c_int, [VP]),

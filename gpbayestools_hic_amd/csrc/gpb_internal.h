@@ -170,6 +170,8 @@ struct gpb_ctx {
     int64_t mc_cap = 0;
     double* ptl_ws = nullptr;      // gpb_chain_ptlmc_run: draws, proposals, their lp / gradient, the other state buffers
     int64_t ptl_cap = 0;
+    double* smc_ws = nullptr;      // gpb_chain_smc_*: weights, their scan, the gathered / proposed particles, moments
+    int64_t smc_cap = 0;
     int sim_ranks = 0;             // measurement hook: gpb_emcee_run evaluates 1/sim_ranks of every batch (one rank's share)
     int num_cu = 256;               // multiprocessor count of the device
     int64_t narrow_switch = 1280;   // 64x64 tiles when at least this many of them exist per 256 CUs, else 64x32
@@ -297,6 +299,35 @@ int launch_compact(gpb_ctx* ctx, const double* X_dev, int64_t W, int64_t dx, con
 int ensure_cmp_rows(gpb_ctx* ctx, int64_t dx);
 int launch_mvn(gpb_ctx* ctx, const double* dY_dev, const double* cov_dev, int64_t W, int64_t M, double* ll_dev);
 bool compaction_applies(const gpb_ctx* ctx);
+// the chain's number of (original) parameters as context c sees it
+inline int64_t sampler_ndim(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }
+// The evaluation of the resident samplers (gpb_ptlmc.hip, gpb_smc.hip): lp of the rows X [W, nd], what Chain.log_prob_device
+// writes.  chain_call (gpb_chain_supported(ctxs, E) == 1): gpb_chain_logpost; else the per-emulator sequence for the
+// contexts it rejects (xg: room for the mapped parameters of every parameterTrafoPCA emulator, W * d doubles each).
+inline int chain_eval(gpb_ctx* const* ctxs, int E, bool chain_call, const double* X, int64_t W, int64_t nd, double* lp,
+                      const double* lo, const double* hi, double outside, double inside_const, double* xg) {
+    gpb_ctx* c0 = ctxs[0];
+    if (chain_call) return gpb_chain_logpost(ctxs, E, X, W, lp, lo, hi, outside, inside_const);
+    int rc;
+    for (int e = 0; e < E; ++e) {
+        gpb_ctx* c = ctxs[e];
+        const bool mapped = c->pmap_d_in > 0, last = e == E - 1;
+        const double* Xg = X;
+        if (mapped) {
+            if ((rc = gpb_param_map(c, X, W, xg))) { c0->err = c->err; return rc; }
+            Xg = xg;
+            xg += W * c->d;
+        }
+        if (!last || mapped) {
+            if ((rc = gpb_loglike(c, Xg, W, 1, lp, e > 0, nullptr))) { c0->err = c->err; return rc; }
+            if (last && (rc = gpb_box_finish(c, X, W, nd, lo, hi, outside, inside_const, lp))) { c0->err = c->err; return rc; }
+        } else if ((rc = gpb_logpost(c, X, W, lp, e > 0, lo, hi, outside, inside_const))) {
+            c0->err = c->err;
+            return rc;
+        }
+    }
+    return 0;
+}
 // test hooks
 int launch_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B,
                      double* C, int b_trans);

@@ -24,13 +24,7 @@ constexpr int PTL_CHUNK = 256;          // exchange picks drawn in parallel per 
 
 __device__ __forceinline__ void ptl_normal_pair(uint64_t seed, uint32_t c, uint32_t k, uint32_t j, double& n0,
                                                 double& n1) {
-#pragma clang fp contract(off)
-    const U4 r = philox(seed, c, k, j, PTL_TAG_NORMAL);
-    const double u1 = u01(r.x, r.y), u2 = u01(r.z, r.w);
-    const double rad = sqrt(-2.0 * log(1.0 - u1));
-    const double a = 6.283185307179586 * u2;                  // 2 pi
-    n0 = rad * cos(a);
-    n1 = rad * sin(a);
+    normal_pair(seed, c, k, j, PTL_TAG_NORMAL, n0, n1);
 }
 
 __device__ __forceinline__ void ptl_pick(uint64_t seed, uint32_t i, uint32_t k, int64_t T, int& rt, double& lu) {
@@ -249,34 +243,6 @@ __global__ void k_ptl_draws(int64_t T, int d, uint64_t seed, uint32_t k, double*
 }
 #endif
 
-int64_t ptl_ndim(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }
-
-// lp of the rows X [W, nd]: what Chain.log_prob_device writes (gpb_chain_logpost, or its per-emulator sequence for the
-// contexts gpb_chain_supported rejects; xg: room for the mapped parameters of every parameterTrafoPCA emulator)
-int ptl_eval(gpb_ctx* const* ctxs, int E, bool chain_call, const double* X, int64_t W, int64_t nd, double* lp,
-             const double* lo, const double* hi, double outside, double inside_const, double* xg) {
-    gpb_ctx* c0 = ctxs[0];
-    if (chain_call) return gpb_chain_logpost(ctxs, E, X, W, lp, lo, hi, outside, inside_const);
-    int rc;
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        const bool mapped = c->pmap_d_in > 0, last = e == E - 1;
-        const double* Xg = X;
-        if (mapped) {
-            if ((rc = gpb_param_map(c, X, W, xg))) { c0->err = c->err; return rc; }
-            Xg = xg;
-            xg += W * c->d;
-        }
-        if (!last || mapped) {
-            if ((rc = gpb_loglike(c, Xg, W, 1, lp, e > 0, nullptr))) { c0->err = c->err; return rc; }
-            if (last && (rc = gpb_box_finish(c, X, W, nd, lo, hi, outside, inside_const, lp))) { c0->err = c->err; return rc; }
-        } else if ((rc = gpb_logpost(c, X, W, lp, e > 0, lo, hi, outside, inside_const))) {
-            c0->err = c->err;
-            return rc;
-        }
-    }
-    return 0;
-}
 }  // namespace
 }  // namespace gpb
 
@@ -297,11 +263,11 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
     if (numtemps < 0 || numchain < 1 || T < 2 || T > PTL_MAX_T)
         GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: numtemps + numchain must be 2 .. 4096 with numchain >= 1");
     if (step0 + (uint64_t)nsteps > 0xFFFFFFFFull) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: steps are numbered below 2^32");
-    const int64_t nd = ptl_ndim(ctx);
+    const int64_t nd = sampler_ndim(ctx);
     int64_t nxg = 0;
     for (int e = 0; e < E; ++e) {
         if (!ctxs[e]) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: null context");
-        if (ptl_ndim(ctxs[e]) != nd) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: the emulators disagree on the number of parameters");
+        if (sampler_ndim(ctxs[e]) != nd) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: the emulators disagree on the number of parameters");
         if (ctxs[e]->device != ctx->device || ctxs[e]->stream != ctx->stream)
             GPB_FAIL(GPB_E_STATE, "gpb_chain_ptlmc_run: the emulators' contexts must share one device and stream");
         if (ctxs[e]->pmap_d_in > 0) nxg += T * ctxs[e]->d;
@@ -353,7 +319,7 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
         if (grad) {
             if ((rc = gpb_chain_logpost_grad(ctxs, E, thetap, T, lp, gbuf, lo_dev, hi_dev, outside_value, inside_const)))
                 return rc;
-        } else if ((rc = ptl_eval(ctxs, E, chain_call, thetap, T, nd, lp, lo_dev, hi_dev, outside_value, inside_const, xg))) {
+        } else if ((rc = chain_eval(ctxs, E, chain_call, thetap, T, nd, lp, lo_dev, hi_dev, outside_value, inside_const, xg))) {
             return rc;
         }
         hipLaunchKernelGGL(k_ptl_accept, gT, dim3(64), 0, ctx->stream, th, fv, df, thetap, lp, grad ? gbuf : nullptr,

@@ -589,3 +589,23 @@ class Chain:
         with open(self.mcmc_path, "wb") as f:
             pickle.dump({"chain": samples, "weights": weights, "logl": logl, "logp": logp, "logz": logz,
                          "logz_err": logz_err}, f)
+
+    def run_SMC(self, n_particles=4096, ess_fraction=0.5, nmcmc=20, max_stages=200, seed=None):
+        """A tempered sequential Monte Carlo sampler resident on the device, with an evidence estimate (smc.SMCSampler,
+        gpb_chain_smc_reweight / gpb_chain_smc_move, `DESIGN.md` §12).  It runs the outer algorithm pocoMC runs — adaptive
+        tempering from the uniform prior box to the posterior at an effective sample size of ess_fraction * n_particles,
+        systematic resampling, nmcmc Metropolis moves per stage, a running log-evidence — but it is not pocoMC: there is no
+        normalizing flow (the Cholesky factor of the particle covariance preconditions the random-walk moves) and no
+        reweighting of earlier stages' particles.  The defaults are choices, not tuned values.
+        Writes the six keys of the reference's pocoMC pickle (src/mcmc.py:816-819) to mcmc_path: chain [n_particles, ndim]
+        (equally weighted posterior samples), weights (uniform), logl (log_likelihood(chain, finite=True), bit for bit), logp
+        (-ln of the box volume), logz, and logz_err = NaN — a single run does not estimate its own error; run several seeds
+        for one.  Returns the same dict plus `beta` (the ladder, ending at exactly 1.0) and `acceptance` (per stage).
+        `seed` keys np.random.default_rng for the start particles and the device's Philox streams.  Raises
+        NotImplementedError for foreign emulators or a sharded chain, RuntimeError when the particle covariance is not
+        positive definite at a stage boundary or beta has not reached 1 after max_stages stages."""
+        from .smc import run_smc
+        out = run_smc(self, n_particles=n_particles, ess_fraction=ess_fraction, nmcmc=nmcmc, max_stages=max_stages, seed=seed)
+        with open(self.mcmc_path, "wb") as f:
+            pickle.dump({k: out[k] for k in ("chain", "weights", "logl", "logp", "logz", "logz_err")}, f)
+        return out

@@ -285,6 +285,39 @@ GPB_API int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps, i
                         const double* hc_dev, const double* covmat0_dev, const double* lo_dev, const double* hi_dev,
                         double outside_value, double inside_const, double* save_dev, int64_t nsave, int64_t* naccept_dev,
                         int64_t* nswap_dev);
+/* gpb_chain_smc_reweight / gpb_chain_smc_move <- Chain.run_SMC (smc.SMCSampler): a tempered sequential Monte Carlo sampler
+ *   over the chain of ctxs — pocoMC's outer algorithm (adaptive tempering from the prior box to the posterior, resampling,
+ *   MCMC moves, a running evidence) with the particle covariance as the preconditioner; there is no normalizing flow.
+ *   State, device memory in and out: x [N, d] particles in the chain's original parameters, logl [N] their
+ *   log-likelihoods (what gpb_chain_logpost writes with outside_value / inside_const), Lc [d, d] the lower Cholesky factor
+ *   of the particle covariance (written by reweight, read by move) and the state block of GPB_SMC_STATE_WORDS 8-byte
+ *   words: doubles [0] beta, [1] logz, [2] log_sigma, [3] the effective sample size at the new beta, [4] the last logz
+ *   increment; unsigned 64-bit counters [8], [9] scratch of the accept kernel (zero between calls), [10] accepted
+ *   proposals, [11] proposals with a NaN log-likelihood, [12] particles with a NaN log-likelihood at the last reweighting
+ *   (weight 0), [13] flags: bit 0 a non-positive pivot in the Cholesky factorisation, bit 1 no particle with a finite
+ *   weight.  The kernels only set the flags; the caller reads the block once per stage and decides.
+ *   Limits (GPB_E_ARG): 2 <= N <= 1048576; 1 <= d <= 128 (Lc and four rows live in LDS: 8 d^2 + 32 d bytes of the 160 KiB
+ *   of a workgroup); stage and step numbers below 2^32.
+ * gpb_chain_smc_reweight: one stage's reweighting.  beta in (beta_prev, 1] with ESS(beta) = (sum w)^2 / sum w^2 =
+ *   ess_fraction * N for w_i = exp((beta - beta_prev)(logl_i - max logl)): 1 when ESS(1) >= the target, else the upper end
+ *   after exactly 60 halvings of [beta_prev, 1]; logz += logsumexp((beta - beta_prev) logl) - ln N; systematic resampling
+ *   with one uniform u from the Philox counter (stage, 0, 0, 8): positions min((u + i) / N, 1 - 2^-53), the ancestor the
+ *   first index whose inclusive cumulative normalised weight exceeds the position, x and logl gathered; mean and covariance
+ *   (divided by N) of the resampled particles and Lc.  Optional device outputs: ancestors [N], mean [d].
+ * gpb_chain_smc_move: nsteps Metropolis steps numbered step0, step0 + 1, ... (global step k; stage_step0 is the index s of
+ *   the first of them within its stage), enqueued back to back, no host synchronisation; one call of n steps gives the bits
+ *   of n calls of one step.  Per step and particle i: z ~ N(0, I_d) from counters (i, k, pair, 9), x' = x + exp(log_sigma)
+ *   Lc z, all N proposals in one evaluation of the chain (gpb_chain_logpost, or for contexts gpb_chain_supported rejects the
+ *   per-emulator sequence), accepted where ln u < beta (logl' - logl) with u from (i, k, 0, 10) and logl' neither NaN nor
+ *   outside_value; then log_sigma += (accepted / N - 0.234) / (s + 1).
+ *   Both are asynchronous on the contexts' stream; all pointers device memory. */
+#define GPB_SMC_STATE_WORDS 16
+GPB_API int gpb_chain_smc_reweight(gpb_ctx* const* ctxs, int E, int64_t N, uint64_t stage, uint64_t seed, double ess_fraction,
+                           double* x_dev /*[N,d]*/, double* logl_dev /*[N]*/, double* state_dev, double* Lc_dev /*[d,d]*/,
+                           int64_t* ancestors_dev /*[N] or NULL*/, double* mean_dev /*[d] or NULL*/);
+GPB_API int gpb_chain_smc_move(gpb_ctx* const* ctxs, int E, int64_t N, int64_t nsteps, uint64_t step0, uint64_t stage_step0,
+                       uint64_t seed, double* x_dev, double* logl_dev, double* state_dev, const double* Lc_dev,
+                       const double* lo_dev, const double* hi_dev, double outside_value, double inside_const);
 /* gpb_chain_emcee_prepare: everything of gpb_chain_emcee_run that can fail on one rank alone — argument and state checks,
  * workspace allocation — and nothing that is enqueued.  A sharded caller runs it on every rank and lets the ranks agree on
  * the outcome (an all-reduce of the return codes) BEFORE any rank calls gpb_chain_emcee_run: a rank that failed there

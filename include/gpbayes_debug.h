@@ -34,6 +34,11 @@ GPB_API int gpb_test_stretch_draws(gpb_ctx* ctx, int64_t nwalkers, int half, uin
  * the serial lane takes them) and logu_swap [5T].  Device outputs. */
 GPB_API int gpb_test_ptlmc_draws(gpb_ctx* ctx, int64_t T, int64_t d, uint64_t seed, uint64_t step, double* normals_dev,
                          double* logu_accept_dev /*[T]*/, int64_t* picks_dev /*[5T]*/, double* logu_swap_dev /*[5T]*/);
+/* test hook: every random number of gpb_chain_smc_reweight's stage `stage` and gpb_chain_smc_move's step `step` for N
+ * particles of d parameters: normals [N, d] (the proposal's z), logu_accept [N] (the accept test's log u) and
+ * u_resample [1] (the uniform of the systematic resampling).  Device outputs. */
+GPB_API int gpb_test_smc_draws(gpb_ctx* ctx, int64_t N, int64_t d, uint64_t seed, uint64_t stage, uint64_t step,
+                       double* normals_dev /*[N,d]*/, double* logu_accept_dev /*[N]*/, double* u_resample_dev /*[1]*/);
 
 /* ---- micro-benchmarks / self-tests (device) --------------------------------------- */
 /* C[M,N] = A*B through the f64 MFMA tile engine (K%16==0).  b_trans bits 0-1: 0 = A[M,K] B[K,N],
