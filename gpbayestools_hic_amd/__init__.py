@@ -8,13 +8,16 @@ src/mcmc.py log-posterior loop): hand-written HIP kernels for gfx950 behind a C 
 __version__ = "0.1.0"
 
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
-           "WalkerSharding"]
+           "WalkerSharding", "rms_relative_error", "honesty"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
     if name == "Emulator":
         from .emulator import Emulator
         return Emulator
+    if name in ("rms_relative_error", "honesty"):
+        from . import emulator
+        return getattr(emulator, name)
     if name in ("Chain", "mvn_loglike"):
         from . import mcmc
         return getattr(mcmc, name)

@@ -146,7 +146,7 @@ extern "C" int gpb_ctx_destroy(gpb_ctx* ctx) {
     dev_free(&ctx->alpha); dev_free(&ctx->apart); dev_free(&ctx->info); dev_free(&ctx->lmlbuf);
     dev_free(&ctx->gpart); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->KsT); dev_free(&ctx->mpart);
     dev_free(&ctx->spart); dev_free(&ctx->mean_pc); dev_free(&ctx->var_pc); dev_free(&ctx->out_stage);
-    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
+    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
     dev_free(&ctx->tile_trace);
     dev_free(&ctx->A); dev_free(&ctx->mu); dev_free(&ctx->scale); dev_free(&ctx->C0); dev_free(&ctx->yexp);
     dev_free(&ctx->Cexp); dev_free(&ctx->mvn_ws); dev_free(&ctx->notpd); dev_free(&ctx->tile_counter);
@@ -744,6 +744,51 @@ extern "C" int gpb_emu_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on
     double* dm = ctx->out_stage;
     double* dc = cov ? ctx->out_stage + W * M : nullptr;
     if ((rc = launch_obs(ctx, W, estd_dev, dm, dc))) return rc;
+    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * M, hipMemcpyDeviceToHost, ctx->stream));
+    if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * W * M * M, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- closed-form cross-validation (gpb_cv.hip)
+extern "C" int gpb_gp_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, const int32_t* fold_ptr_host, int64_t nf,
+                         int on_device, double* mean, double* var, double* cov) {
+    if (!ctx || !mean) return GPB_E_ARG;
+    int64_t kmax;
+    int rc = cv_plan(ctx, "gpb_gp_cv", idx_host, n_idx, fold_ptr_host, nf, &kmax);
+    if (rc) return rc;
+    const int64_t P = ctx->P, ncov = P * nf * kmax * kmax;
+    if (on_device) return launch_cv(ctx, mean, var, 1, P, cov);
+    if ((rc = ensure_out(ctx, 2 * n_idx * P + (cov ? ncov : 0)))) return rc;
+    double* dm = ctx->out_stage;
+    double* dv = var ? dm + n_idx * P : nullptr;
+    double* dc = cov ? dm + 2 * n_idx * P : nullptr;
+    if ((rc = launch_cv(ctx, dm, dv, 1, P, dc))) return rc;
+    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * n_idx * P, hipMemcpyDeviceToHost, ctx->stream));
+    if (var) GPB_HIP(hipMemcpyAsync(var, dv, sizeof(double) * n_idx * P, hipMemcpyDeviceToHost, ctx->stream));
+    if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * ncov, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, const int32_t* fold_ptr_host, int64_t nf,
+                          int on_device, double* mean, double* cov) {
+    if (!ctx || !mean) return GPB_E_ARG;
+    if (!ctx->have_transform) GPB_FAIL(GPB_E_STATE, "gpb_emu_cv before gpb_emu_set_transform");
+    int64_t kmax;
+    int rc = cv_plan(ctx, "gpb_emu_cv", idx_host, n_idx, fold_ptr_host, nf, &kmax);
+    if (rc) return rc;
+    // the hold-out means and variances take the place of a predict batch's in front of the observable transform
+    if ((rc = ensure_wcap(ctx, n_idx))) return rc;
+    ctx->Wld = round_up(n_idx, WPAD);
+    ctx->last_W = 0;                                   // the K*^T of the last predict batch is no longer described by Wld
+    if ((rc = launch_cv(ctx, ctx->mean_pc, ctx->var_pc, ctx->Wld, 1, nullptr))) return rc;
+    const int64_t W = n_idx, M = ctx->M;
+    if (on_device) return launch_obs(ctx, W, nullptr, mean, cov);
+    if ((rc = ensure_out(ctx, W * M + (cov ? W * M * M : 0)))) return rc;
+    double* dm = ctx->out_stage;
+    double* dc = cov ? ctx->out_stage + W * M : nullptr;
+    if ((rc = launch_obs(ctx, W, nullptr, dm, dc))) return rc;
     GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * M, hipMemcpyDeviceToHost, ctx->stream));
     if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * W * M * M, hipMemcpyDeviceToHost, ctx->stream));
     GPB_HIP(hipStreamSynchronize(ctx->stream));

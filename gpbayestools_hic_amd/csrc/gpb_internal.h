@@ -139,6 +139,13 @@ struct gpb_ctx {
     int64_t covbuf_cap = 0;
     double* out_stage = nullptr;   // staging for host outputs
     int64_t out_cap = 0;
+    // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
+    // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
+    int* cv_ws = nullptr;
+    int64_t cv_cap = 0;            // bytes
+    std::vector<int> h_cv;
+    int64_t cv_n = 0, cv_nf = 0, cv_kmax = 0, cv_ints = 0;
+    bool cv_loo = false, cv_has_idx = false;
 
     // ---- emulator transform / likelihood ----------------------------------------
     int mode = 0;
@@ -284,6 +291,11 @@ int sliced_read_kstar(gpb_ctx* ctx, int64_t p, int64_t pad, int64_t N, int64_t W
 constexpr int GPB_MAX_MULTI_GP = 96;      // GPs one batched launch can address (its table is a kernel argument)
 int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* cov_dev);
 int launch_vmat(gpb_ctx* ctx);     // gpb_cov.hip: vbuf = L^-1 K*^T of the current (fp64) batch
+// closed-form cross-validation (gpb_cv.hip): cv_plan checks the folds (GPB_E_ARG / GPB_E_STATE) and uploads them, launch_cv
+// writes element (GP p, position q of idx) of the hold-out mean / variance at [p * sp + q * si] and, when cov_dev is given,
+// the fold covariance blocks [P][nf][kmax][kmax]
+int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, const int32_t* fold_ptr, int64_t nf, int64_t* kmax);
+int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64_t si, double* cov_dev);
 // likelihood (gpb_like.hip)
 int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev, double* cov_dev);
 // true when launch_loglike will take the block log-likelihood kernels that sum the partials themselves

@@ -380,6 +380,7 @@ class Emulator:
         X = (self.PCA_new_design_points if self.parameterTrafoPCA_ else self.design_points)[mask]
         self._X_train = np.ascontiguousarray(X, dtype=np.float64)
         self._Z_train = np.ascontiguousarray(Z.T, dtype=np.float64)       # [P, N]
+        self._train_events = np.flatnonzero(mask)                         # rows of model_data behind the design points
         self.kernel_type_ = kernel_type
         self._ngp = self._Z_train.shape[0]
 
@@ -732,6 +733,72 @@ class Emulator:
         r = lambda a: np.array(a).reshape(-1, self.nobs)
         return r(pred), r(perr), r(truth), r(terr)
 
+    def _trained_events(self):
+        """rows of model_data (events) behind the GPs' design points, in their order"""
+        N = self._X_train.shape[0]
+        ev = getattr(self, "_train_events", None)
+        if ev is not None and len(ev) == N:
+            return np.asarray(ev)
+        if N == self.nev:
+            return np.arange(N)
+        # an adopted or older state without the training mask: find the design points among the events' parameters
+        D = np.ascontiguousarray(self.PCA_new_design_points if self.parameterTrafoPCA_ else self.design_points, dtype=np.float64)
+        where = {row.tobytes(): i for i, row in reversed(list(enumerate(D)))}
+        try:
+            return np.array([where[row.tobytes()] for row in self._X_train])
+        except KeyError:
+            raise RuntimeError("cross_validate: the GPs' training inputs are not rows of the design points") from None
+
+    def cross_validate(self, folds=None, shuffle=False, random_state=None):
+        """Leave-one-out / k-fold validation of the TRAINED emulator in closed form on the device (GPEngine.emu_cross_validate,
+        gpb_emu_cv): every trained event is predicted by the GPs refitted without its fold, with no refit — one pass over the
+        resident factorisation instead of one training per fold.
+
+        folds: None = leave-one-out of every trained event; an int = that many folds over the trained events in order, of
+        sklearn KFold's sizes (the first n % folds one larger), the events shuffled first by `random_state` when `shuffle` is
+        set (as KFold(shuffle=True) does); or a list of index arrays into the trained events.  A fold holds at most 64 events
+        (ValueError otherwise: use more folds).
+
+        Returns (pred, pred_err, truth, truth_err), each [n_idx, nobs] in the order of the concatenated folds, with the log /
+        exp handling of testEmulatorErrors — its return values, so the validation notebook's code takes them as they are.
+
+        What differs from testEmulatorErrors (src/emulator.py:636-679): that one RETRAINS on the first nev - k events —
+        hyper-parameter search, scaler and output PCA included — and predicts the last k, always the same ones.  Here the
+        hyper-parameters theta, the scaler and the output PCA are those of the full fit and are NOT refit per fold; only the
+        fold's events leave the GPs' conditioning set.  This is the textbook GP leave-one-out cross-validation (Rasmussen &
+        Williams 5.4.2), not a retraining."""
+        eng = self._engine_ready()
+        ev = self._trained_events()
+        n = ev.shape[0]
+        if folds is None:
+            flat = np.arange(n)
+        elif isinstance(folds, (int, np.integer)):
+            k = int(folds)
+            if k < 1 or k > n:
+                raise ValueError("cross_validate: folds=%d for %d trained events (need 1 <= folds <= events)" % (k, n))
+            order = np.arange(n)
+            if shuffle:
+                _check_random_state(random_state).shuffle(order)
+            sizes = np.full(k, n // k)
+            sizes[:n % k] += 1
+            folds = np.split(order, np.cumsum(sizes)[:-1])
+            flat = order
+        else:
+            folds = [np.atleast_1d(np.asarray(f)).reshape(-1) for f in folds]
+            flat = np.concatenate(folds) if folds else np.zeros(0, dtype=np.int64)
+        pred, cov = eng.emu_cross_validate(folds, return_cov=True)
+        perr = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+        if self.logTrafo_ and not self.exp_and_cov_diagonal_:
+            pred, perr = np.exp(pred), perr * np.exp(pred)
+        rows = ev[flat]
+        if self.logTrafo_:
+            truth = np.exp(self.model_data[rows])
+            terr = self.model_data_err[rows] * truth
+        else:
+            truth, terr = self.model_data[rows], self.model_data_err[rows]
+        r = lambda a: np.array(a).reshape(-1, self.nobs)
+        return r(pred), r(perr), r(truth), r(terr)
+
     def testEmulatorErrors(self, nTestPoints=1, thetas=None):
         """Train on the first nev-nTestPoints points, predict the rest (src/emulator.py:636-679): returns
         (predictions, their errors, true values, their errors), each [nTestPoints, nobs].  `thetas` (extension)
@@ -741,6 +808,20 @@ class Emulator:
     def testEmulatorErrorsWithTrainingPoints(self, nTestPoints=1, thetas=None):
         """Same split, but predict the training points themselves (src/emulator.py:682-726)."""
         return self._holdout(nTestPoints, on_training=True, thetas=thetas)
+
+
+def rms_relative_error(pred, truth):
+    """per observable: sqrt(mean over the validation points of ((pred - truth) / truth)^2) — the emulator's relative error as
+    examples/EmulatorValidation.ipynb tabulates it; pred, truth [n, nobs] -> [nobs]"""
+    pred, truth = np.asarray(pred, dtype=np.float64), np.asarray(truth, dtype=np.float64)
+    return np.sqrt(np.mean(((pred - truth) / truth) ** 2, axis=0))
+
+
+def honesty(pred, pred_err, truth):
+    """per observable: sqrt(mean over the validation points of ((pred - truth) / pred_err)^2) — 1 for an emulator whose quoted
+    uncertainty is honest, above 1 for an overconfident one; pred, pred_err, truth [n, nobs] -> [nobs]"""
+    pred, pred_err, truth = (np.asarray(a, dtype=np.float64) for a in (pred, pred_err, truth))
+    return np.sqrt(np.mean(((pred - truth) / pred_err) ** 2, axis=0))
 
 
 _BATCH_BYTES_MAX = 96 << 30          # three N x N matrices per virtual GP of a search batch: beyond this the emulators train one by one

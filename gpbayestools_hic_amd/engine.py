@@ -302,6 +302,61 @@ class GPEngine:
         self._ck(self.lib.gpb_gp_predict_grad(self.h, nat.ptr(Xs), W, 0, nat.ptr(dm), nat.ptr(dv)))
         return (dm, dv) if return_var else dm
 
+    # ------------------------------------------------------------------ closed-form cross-validation
+    CV_MAX_FOLD = 64
+
+    def _cv_folds(self, folds):
+        """folds (None = leave-one-out of all points, or a list of index arrays) -> (idx int32 [n] | None, fold_ptr int32
+        [nf+1] | None, n, nf, kmax); ValueError for what gpb_gp_cv answers with GPB_E_ARG"""
+        self._need_data()
+        if folds is None:
+            return None, None, self.N, self.N, 1
+        folds = [np.atleast_1d(np.asarray(f)).reshape(-1) for f in folds]
+        if not folds:
+            raise ValueError("cross_validate: no folds")
+        sizes = np.array([f.shape[0] for f in folds], dtype=np.int64)
+        if sizes.min() < 1:
+            raise ValueError("cross_validate: fold %d is empty" % int(np.argmin(sizes)))
+        if sizes.max() > self.CV_MAX_FOLD:
+            raise ValueError("cross_validate: fold %d has %d points; the closed form takes folds of 1 to %d points "
+                             "(use more folds, or refit for larger hold-out sets)" % (int(np.argmax(sizes)), int(sizes.max()), self.CV_MAX_FOLD))
+        flat = np.concatenate(folds)
+        if not np.issubdtype(flat.dtype, np.integer):
+            raise ValueError("cross_validate: folds must hold integer design-point indices")
+        if flat.min() < 0 or flat.max() >= self.N:
+            raise ValueError("cross_validate: design-point index outside [0, %d)" % self.N)
+        if np.unique(flat).shape[0] != flat.shape[0]:
+            raise ValueError("cross_validate: a design point appears in the folds twice")
+        idx = np.ascontiguousarray(flat, dtype=np.int32)
+        fptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int32)
+        return idx, fptr, idx.shape[0], len(folds), int(sizes.max())
+
+    def cross_validate(self, folds=None, return_cov=False):
+        """Hold-out predictions of the fitted GPs in closed form (gpb_gp_cv): for every fold F the mean and variance, at X_F, of
+        the GP refitted WITHOUT the fold's points at the same theta — mean = z_F - G^-1 alpha_F, cov = G^-1 - alpha I with
+        G = (Ky^-1)_FF from the resident L^-1; no refit, no N-sized factorisation.  folds: None = leave-one-out of all N points,
+        or a list of arrays of distinct design-point indices, 1 to 64 points each.  Returns (mean [n_idx, P], var [n_idx, P]) in
+        the order of the concatenated folds, plus with return_cov the folds' covariance blocks [P, nf, kmax, kmax] (zero-padded
+        to the largest fold size kmax).  Variances are not clipped.  ValueError for empty or oversized folds, indices out of
+        range or repeated."""
+        idx, fptr, n, nf, kmax = self._cv_folds(folds)
+        self._track_stream()
+        mean, var = np.empty((n, self.P)), np.empty((n, self.P))
+        cov = nat.host_empty((self.P, nf, kmax, kmax)) if return_cov else None
+        self._ck(self.lib.gpb_gp_cv(self.h, nat.ptr(idx), n, nat.ptr(fptr), nf, 0, nat.ptr(mean), nat.ptr(var), nat.ptr(cov)))
+        return (mean, var, cov) if return_cov else (mean, var)
+
+    def emu_cross_validate(self, folds=None, return_cov=True):
+        """cross_validate through the installed observable transform (gpb_emu_cv, extra_std = 0): mean [n_idx, M] and, with
+        return_cov, cov [n_idx, M, M] — what emu_predict would give at the held-out design points after a refit without their
+        fold.  Overwrites the workspace of the last predict batch (get("Kstar") is undefined afterwards)."""
+        idx, fptr, n, nf, _ = self._cv_folds(folds)
+        self._track_stream()
+        mean = nat.host_empty((n, self.M))
+        cov = nat.host_empty((n, self.M, self.M)) if return_cov else None
+        self._ck(self.lib.gpb_emu_cv(self.h, nat.ptr(idx), n, nat.ptr(fptr), nf, 0, nat.ptr(mean), nat.ptr(cov)))
+        return (mean, cov) if return_cov else mean
+
     # ------------------------------------------------------------------ emulator transform
     def set_transform(self, mode, mu, A=None, cov_trunc=None, scale=None):
         mu = nat.f64(mu)

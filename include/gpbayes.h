@@ -154,6 +154,38 @@ GPB_API int gpb_emu_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on_de
  * The response matrix the reference's SensitivityAnalysis notebook builds from 2 d finite-difference predictions. */
 GPB_API int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device, double* jac /*[W,M,d_in]*/);
 
+/* ---- closed-form cross-validation: hold-out predictions of the fitted GPs without refitting ------------------------ *
+ * gpb_gp_cv  <- for every fold F: GPR(kernel_ at the SAME theta, alpha).fit(X without F, z without F)  sk:_gpr.py:346-364
+ *               followed by .predict(X_F, return_cov=True)                                          sk:_gpr.py:441-469
+ * gpb_emu_cv <- those per-GP hold-out means / variances through Emulator.predict's observable transform with
+ *               extra_std = 0                                                               src/emulator.py:555-605
+ * (the reference's only accuracy check, Emulator.testEmulatorErrors, src/emulator.py:636-679, retrains on the first nev - k events
+ * for k validation points; here theta, scaler and PCA are those of the full fit: the textbook GP leave-one-out / leave-k-out.)
+ * With Ky = K + (sigma_n^2 + alpha) I = L L^T (gpb_gp_factor) and a fold F of k points (Rasmussen & Williams 5.4.2, for blocks):
+ *   G_F  = (Ky^-1)_FF = (L^-1[:, F])^T (L^-1[:, F])      a k x k Gram matrix over the rows of the resident L^-1
+ *   mean = z_F - G_F^-1 alpha_F                           the refit's predictive mean at X_F (alpha_ = Ky^-1 z, GPB_GET_ALPHA)
+ *   cov  = G_F^-1 - alpha I                               the refit's predictive covariance at X_F (sklearn's prior carries the
+ *                                                         White noise but not GPR's alpha); var = its diagonal, not clipped
+ * idx_host [n_idx]: distinct design-point indices in [0, N), grouped into folds; fold_ptr_host [nf + 1]: offsets into idx, from 0
+ * to n_idx, every fold 1 .. 64 points (fold_ptr_host == NULL: one point per fold, nf = n_idx).  idx_host == NULL: leave-one-out
+ * of all N points in order (n_idx = nf = N, fold_ptr_host = NULL).  Both are host arrays; on_device says where the OUTPUTS live
+ * (0: host, the call synchronises; 1: device memory, asynchronous).  mean / var [n_idx, P] in the order of idx (var may be
+ * NULL); cov [P, nf, kmax, kmax] or NULL: the folds' covariance blocks, zero-padded to the largest fold size kmax.  A call whose
+ * folds all hold one point takes one streaming pass over L^-1 (a column's sum of squares); other calls one workgroup per
+ * (fold, GP).  A fold's bits do not depend on the folds or GPs that share the call.  A fold whose G_F has a non-positive pivot
+ * gets NaN for that GP and counts in the context's not-positive-definite counter; the call does not fail.
+ * Errors: GPB_E_STATE without a factorisation, on a gpb_gp_set_multi context and (gpb_emu_cv) without a transform; GPB_E_ARG for
+ * an empty fold, a fold of more than 64 points, an index outside [0, N), a repeated index, a fold_ptr that does not increase
+ * from 0 to n_idx.  The factorisation, alpha and the results of later predict / likelihood calls are untouched.  gpb_emu_cv
+ * (mean [n_idx, M], cov [n_idx, M, M] or NULL, all four GPB_MODE_*) overwrites the workspace of the last predict batch:
+ * gpb_gp_get(GPB_GET_KSTAR) is undefined after it (GPB_E_STATE) until the next predict / likelihood call. */
+GPB_API int gpb_gp_cv(gpb_ctx* ctx, const int32_t* idx_host /*[n_idx] or NULL*/, int64_t n_idx,
+              const int32_t* fold_ptr_host /*[nf+1] or NULL*/, int64_t nf, int on_device,
+              double* mean /*[n_idx,P]*/, double* var /*[n_idx,P] or NULL*/, double* cov /*[P,nf,kmax,kmax] or NULL*/);
+GPB_API int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host /*[n_idx] or NULL*/, int64_t n_idx,
+               const int32_t* fold_ptr_host /*[nf+1] or NULL*/, int64_t nf, int on_device,
+               double* mean /*[n_idx,M]*/, double* cov /*[n_idx,M,M] or NULL*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
