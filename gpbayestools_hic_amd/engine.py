@@ -273,11 +273,17 @@ class GPEngine:
         self._ck(self.lib.gpb_gp_predict(self.h, nat.ptr(Xs), W, 0, nat.ptr(mean), nat.ptr(var)))
         return (mean, var) if return_var else mean
 
+    # gpb_gp_predict_cov's own limit (csrc/gpb_api.hip, "W > 8192": the library refuses a larger batch itself; tests/
+    # test_gpu_predict_cov.py::test_limits asks both for PREDICT_COV_MAX_W + 1 rows, so the two cannot drift apart unnoticed)
+    PREDICT_COV_MAX_W = 8192
+
     def predict_cov(self, Xs):
         """per-GP mean[W,P] and full covariance cov[P,W,W] between the query points (numpy in/out)."""
         self._need_data()
         Xs = nat.f64(Xs).reshape(-1, self.d)
         W = Xs.shape[0]
+        if W > self.PREDICT_COV_MAX_W:       # before P x W x W doubles of pinned memory are asked for
+            raise nat.GPBError("predict_cov: W = %d > %d (the W x W covariance is for small batches)" % (W, self.PREDICT_COV_MAX_W))
         mean = np.empty((W, self.P))
         cov = nat.host_empty((self.P, W, W))
         self._ck(self.lib.gpb_gp_predict_cov(self.h, nat.ptr(Xs), W, 0, nat.ptr(mean), nat.ptr(cov)))
