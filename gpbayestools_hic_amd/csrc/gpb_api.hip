@@ -36,12 +36,7 @@ int pick_dpad(int64_t d) {
 }
 
 int ensure_out(gpb_ctx* ctx, int64_t count) {
-    if (count <= ctx->out_cap) return 0;
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    dev_free(&ctx->out_stage);
-    GPB_HIP(pool_malloc_t(&ctx->out_stage, sizeof(double) * (size_t)count));
-    ctx->out_cap = count;
-    return 0;
+    return pool_grow(ctx, &ctx->out_stage, &ctx->out_cap, count);
 }
 
 // [P][Wld] -> [W][P]

@@ -87,13 +87,7 @@ __global__ void k_cov_pack(const double* __restrict__ src, double* __restrict__ 
 int launch_vmat(gpb_ctx* ctx) {
     const int64_t P = ctx->P, Np = ctx->Np, Wld = ctx->Wld;
     const int64_t need_v = P * Np * Wld;
-    if (need_v > ctx->vbuf_cap) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->vbuf) pool_free(ctx->vbuf);
-        ctx->vbuf_cap = 0;
-        GPB_HIP(pool_malloc_t(&ctx->vbuf, need_v * sizeof(double)));
-        ctx->vbuf_cap = need_v;
-    }
+    if (int rc = pool_grow(ctx, &ctx->vbuf, &ctx->vbuf_cap, need_v)) return rc;
     dim3 gv((unsigned)(Wld / 128), (unsigned)((Np + 127) / 128), (unsigned)P);
     hipLaunchKernelGGL(k_vmat, gv, dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, ctx->vbuf, Np, Wld);
     GPB_HIP(hipGetLastError());
@@ -104,12 +98,7 @@ int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* co
     // Wc: padded extent of this batch (cov's own ld); launch_predict lays the batch out with ld = Wc
     const int64_t P = ctx->P, Np = ctx->Np, Wc = round_up(W, WPAD);
     const int64_t need_c = P * Wc * Wc;
-    if (need_c > ctx->covbuf_cap) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->covbuf) pool_free(ctx->covbuf);
-        GPB_HIP(pool_malloc_t(&ctx->covbuf, need_c * sizeof(double)));
-        ctx->covbuf_cap = need_c;
-    }
+    if (int rc = pool_grow(ctx, &ctx->covbuf, &ctx->covbuf_cap, need_c)) return rc;
     ctx->want_kst = true;                                    // (the joint covariance reads the fp64 K*^T itself: no digit planes here)
     int rc = launch_predict(ctx, Xs_dev, W, false);          // K*^T and the mean
     ctx->want_kst = false;

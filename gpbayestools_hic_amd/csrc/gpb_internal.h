@@ -257,6 +257,20 @@ void pool_free(void* p);
 void pool_trim();
 template <typename T>
 inline hipError_t pool_malloc_t(T** p, size_t bytes) { return pool_malloc(reinterpret_cast<void**>(p), bytes); }
+// A workspace of the context grown on demand to `need` elements (never shrunk; the contents are not kept).  The stream is
+// synchronised before the old buffer goes back to the cache, and pointer and capacity are cleared before the allocation
+// that may fail, so that a failure leaves an empty workspace, not a dangling one.
+template <typename T>
+inline int pool_grow(gpb_ctx* ctx, T** p, int64_t* cap, int64_t need) {
+    if (*cap >= need) return 0;
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    if (*p) pool_free(*p);
+    *p = nullptr;
+    *cap = 0;
+    GPB_HIP(pool_malloc_t(p, sizeof(T) * (size_t)need));
+    *cap = need;
+    return 0;
+}
 // fit side (gpb_fit.hip)
 int launch_scale_design(gpb_ctx* ctx);
 int choose_forms(gpb_ctx* ctx, bool upload = true);    // gpb_api.hip: per-GP distance form from h_theta and the design's extents
@@ -310,6 +324,12 @@ int launch_compact(gpb_ctx* ctx, const double* X_dev, int64_t W, int64_t dx, con
                    double outside, double* ll_dev, int premarked = 0);
 int ensure_cmp_rows(gpb_ctx* ctx, int64_t dx);
 int launch_mvn(gpb_ctx* ctx, const double* dY_dev, const double* cov_dev, int64_t W, int64_t M, double* ll_dev);
+// A chain's compacted batch whose every emulator takes the low-rank kernel (chain_batch, 1 < E <= MAX_LR_CTX of gpb_like.hip,
+// fused finalize, one Wld): all E blocks added up in emuList order by one launch or two.  *taken = false: not such a chain,
+// nothing launched.
+int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double* ll_dev, const int* cmpv, double inside_const,
+                                 bool* taken);
+int ensure_lr_blocks(gpb_ctx* ctx, int E);          // its per-emulator blocks [E][Wcap] in the chain's first context
 bool compaction_applies(const gpb_ctx* ctx);
 // the chain's number of (original) parameters as context c sees it
 inline int64_t sampler_ndim(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }

@@ -1,54 +1,37 @@
-// gpb_like.hip — PC -> observable transform, batched multivariate-normal log-likelihood,
-// prior box, and the emcee-equivalent stretch move.
+// gpb_like.hip — PC -> observable transform, batched multivariate-normal log-likelihood, prior box and the
+// compaction of a batch to the rows inside it.  (The stretch move that drives them: gpb_stretch.hip.)
 //   k_obs       Emulator.predict after the per-GP calls            src/emulator.py:555-605
 //   k_loglike   Chain._predict block + mvn_loglike, fused          src/mcmc.py:23-65,153-166,288-293
 //   k_box       strict prior box + constant                        src/mcmc.py:194-198,275-276,296-297
-//   k_propose / k_accept   emcee StretchMove (a=2) as driven by     src/mcmc.py:68-92,372-412
 #include "gpb_internal.h"
-#include "philox.h"
 #include <math.h>
 
 namespace gpb {
 
-// ------------------------------------------------------------------ observable transform (materialised)
-// one workgroup per walker; writes mean[w][M] and (optionally) cov[w][M][M]
-__global__ __launch_bounds__(256) void k_obs(const double* __restrict__ mean_pc, const double* __restrict__ var_pc,
-                                             const double* __restrict__ estd, int64_t Wld, int P, int M, int mode,
-                                             const double* __restrict__ A, const double* __restrict__ mu,
-                                             const double* __restrict__ scale, const double* __restrict__ C0,
-                                             double* __restrict__ mean_out, double* __restrict__ cov_out) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double* zm = sm;            // [P]
-    double* zv = sm + P;        // [P]
-    double* mo = sm + 2 * P;    // [M]
-    const int64_t w = blockIdx.x;
-    const int tid = threadIdx.x;
-    const bool no_pca = (mode == GPB_MODE_NO_PCA || mode == GPB_MODE_NO_PCA_EXPDIAG);
-    const bool expdiag = (mode == GPB_MODE_EXPDIAG || mode == GPB_MODE_NO_PCA_EXPDIAG);
-    const double e = estd ? estd[w] : 0.0;
-    for (int p = tid; p < P; p += 256) {
-        zm[p] = mean_pc[(int64_t)p * Wld + w];
-        zv[p] = var_pc ? (var_pc[(int64_t)p * Wld + w] + e * e) : 0.0;     // src/emulator.py:578-579
-    }
-    __syncthreads();
-    for (int m = tid; m < M; m += 256) {
+// ------------------------------------------------------------------ observable transform
+// The emulator's observables from the principal components of one walker, in the four modes: the mean of column m from the
+// PC means zm[P], the model covariance entry (i, j) from the PC variances zv[P] and the observable means mo[M].
+struct ObsModel {
+    int P, M;
+    bool no_pca, expdiag;
+    const double *A, *mu, *scale, *C0;
+    __device__ __forceinline__ ObsModel(int P_, int M_, int mode, const double* A_, const double* mu_, const double* scale_,
+                                        const double* C0_)
+        : P(P_), M(M_), no_pca(mode == GPB_MODE_NO_PCA || mode == GPB_MODE_NO_PCA_EXPDIAG),
+          expdiag(mode == GPB_MODE_EXPDIAG || mode == GPB_MODE_NO_PCA_EXPDIAG), A(A_), mu(mu_), scale(scale_), C0(C0_) {}
+    __device__ __forceinline__ double mean(const double* zm, int m) const {
         double v;
         if (!no_pca) {
             v = 0.0;
-            for (int p = 0; p < P; ++p) v = fma(zm[p], A[p * M + m], v);   // :559-561, 373-374
+            for (int p = 0; p < P; ++p) v = fma(zm[p], A[p * M + m], v);   // src/emulator.py:559-561, 373-374
             v += mu[m];
         } else {
             v = zm[m] * scale[m] + mu[m];                                    // :563-565
         }
         if (expdiag) v = exp(v);                                             // :567-568
-        mo[m] = v;
-        mean_out[w * M + m] = v;
+        return v;
     }
-    if (!cov_out) return;
-    __syncthreads();
-    double* co = cov_out + w * (int64_t)M * M;
-    for (int e2 = tid; e2 < M * M; e2 += 256) {
-        const int i = e2 / M, j = e2 % M;
+    __device__ __forceinline__ double cov(const double* zv, const double* mo, int i, int j) const {
         double v;
         if (!no_pca) {
             if (expdiag && i != j) v = 0.0;
@@ -64,8 +47,38 @@ __global__ __launch_bounds__(256) void k_obs(const double* __restrict__ mean_pc,
             const double f = sqrt(v) * mo[i];                                                  // :599-600
             v = f * f;
         }
-        co[e2] = v;
+        return v;
     }
+};
+
+// materialised: one workgroup per walker; writes mean[w][M] and (optionally) cov[w][M][M]
+__global__ __launch_bounds__(256) void k_obs(const double* __restrict__ mean_pc, const double* __restrict__ var_pc,
+                                             const double* __restrict__ estd, int64_t Wld, int P, int M, int mode,
+                                             const double* __restrict__ A, const double* __restrict__ mu,
+                                             const double* __restrict__ scale, const double* __restrict__ C0,
+                                             double* __restrict__ mean_out, double* __restrict__ cov_out) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    double* zm = sm;            // [P]
+    double* zv = sm + P;        // [P]
+    double* mo = sm + 2 * P;    // [M]
+    const int64_t w = blockIdx.x;
+    const int tid = threadIdx.x;
+    const ObsModel obs(P, M, mode, A, mu, scale, C0);
+    const double e = estd ? estd[w] : 0.0;
+    for (int p = tid; p < P; p += 256) {
+        zm[p] = mean_pc[(int64_t)p * Wld + w];
+        zv[p] = var_pc ? (var_pc[(int64_t)p * Wld + w] + e * e) : 0.0;     // src/emulator.py:578-579
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += 256) {
+        const double v = obs.mean(zm, m);
+        mo[m] = v;
+        mean_out[w * M + m] = v;
+    }
+    if (!cov_out) return;
+    __syncthreads();
+    double* co = cov_out + w * (int64_t)M * M;
+    for (int e2 = tid; e2 < M * M; e2 += 256) co[e2] = obs.cov(zv, mo, e2 / M, e2 % M);
 }
 
 int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev, double* cov_dev) {
@@ -162,23 +175,14 @@ __global__ __launch_bounds__(256) void k_loglike(const double* __restrict__ mean
     double* c;                       // [(M+1)][ld]
     if (GWS) c = gws + w * (int64_t)(M + 1) * ld;
     else     c = sm + 2 * P + 2 * M;
-    const bool no_pca = (mode == GPB_MODE_NO_PCA || mode == GPB_MODE_NO_PCA_EXPDIAG);
-    const bool expdiag = (mode == GPB_MODE_EXPDIAG || mode == GPB_MODE_NO_PCA_EXPDIAG);
+    const ObsModel obs(P, M, mode, A, mu, scale, C0);
     for (int p = tid; p < P; p += 256) {
         zm[p] = mean_pc[(int64_t)p * Wld + w];
         zv[p] = var_pc[(int64_t)p * Wld + w];       // extra_std == 0 on this path (src/mcmc.py:205,281)
     }
     __syncthreads();
     for (int m = tid; m < M; m += 256) {
-        double v;
-        if (!no_pca) {
-            v = 0.0;
-            for (int p = 0; p < P; ++p) v = fma(zm[p], A[p * M + m], v);
-            v += mu[m];
-        } else {
-            v = zm[m] * scale[m] + mu[m];
-        }
-        if (expdiag) v = exp(v);
+        const double v = obs.mean(zm, m);
         mo[m] = v;
         c[M * ld + m] = v - yexp[m];                // dY (src/mcmc.py:288)
     }
@@ -186,22 +190,7 @@ __global__ __launch_bounds__(256) void k_loglike(const double* __restrict__ mean
     for (int e2 = tid; e2 < M * M; e2 += 256) {
         const int i = e2 / M, j = e2 % M;
         if (j > i) continue;
-        double v;
-        if (!no_pca) {
-            if (expdiag && i != j) v = 0.0;
-            else {
-                v = 0.0;
-                for (int p = 0; p < P; ++p) v = fma(zv[p] * A[p * M + i], A[p * M + j], v);
-                v += C0[i * M + j];
-            }
-        } else {
-            v = (i == j) ? zv[i] : 0.0;
-        }
-        if (expdiag && i == j) {
-            const double f = sqrt(v) * mo[i];
-            v = f * f;
-        }
-        c[i * ld + j] = v + Cexp[i * M + j];        // src/mcmc.py:290
+        c[i * ld + j] = obs.cov(zv, mo, i, j) + Cexp[i * M + j];        // src/mcmc.py:290
     }
     __syncthreads();
     chol_aug_finish(c, ld, M, dg, ll, w, accumulate, notpd);
@@ -242,6 +231,24 @@ struct PartArgs {
     const double* noise;  // [P]
     int nchunk, nI64;
 };
+
+// The end of a dense block log-likelihood kernel, by the one lane that writes row w's result -1/2 q - logdet (formed here,
+// behind the load of the scatter index: handed over finished, k_loglike_reg<64> spills 12 more scalar registers): NaN and a
+// counted status when the block is not positive definite inside the box, the emulators' blocks added up, the box's constant
+// or `outside`, and the scatter through cmp for a compacted batch.
+__device__ __forceinline__ void loglike_finish(const BoxArgs& box, int64_t w, double q, double logdet, bool bad, bool inside,
+                                               int accumulate, double* ll, int* notpd) {
+    const int64_t wo = box.cmp ? box.cmp[4 + w] : w;
+    double r = -0.5 * q - logdet;
+    if (bad && inside) {
+        r = nan("");
+        atomicAdd(notpd, 1);
+    }
+    r = accumulate ? (ll[wo] + r) : r;
+    if (box.X) r = inside ? (r + box.inside_const) : box.outside;
+    else if (box.cmp) r += box.inside_const;
+    ll[wo] = r;
+}
 
 template <int MP>
 __global__ __launch_bounds__(256) void k_loglike_reg(const double* __restrict__ mean_pc,
@@ -337,18 +344,7 @@ __global__ __launch_bounds__(256) void k_loglike_reg(const double* __restrict__ 
         }
         inside = __all(ok);
     }
-    if (lane == 0 && (!box.cmp || w < box.cmp[0])) {
-        const int64_t wo = box.cmp ? box.cmp[4 + w] : w;
-        double r = -0.5 * q - logdet;
-        if (bad && inside) {
-            r = nan("");
-            atomicAdd(notpd, 1);
-        }
-        r = accumulate ? (ll[wo] + r) : r;
-        if (box.X) r = inside ? (r + box.inside_const) : box.outside;
-        else if (box.cmp) r += box.inside_const;
-        ll[wo] = r;
-    }
+    if (lane == 0 && (!box.cmp || w < box.cmp[0])) loglike_finish(box, w, q, logdet, bad, inside, accumulate, ll, notpd);
 }
 
 template <int MP>
@@ -486,19 +482,7 @@ __global__ __launch_bounds__(256) void k_loglike_wg(const double* __restrict__ m
     if (tid == 0) {
         double logdet = 0.0;
         for (int g = 0; g < 16; ++g) logdet = fma(0.5, col[g], logdet);      // fixed order (as k_loglike_reg)
-        const bool inside = !s_outside;
-        if (!box.cmp || w < box.cmp[0]) {
-            const int64_t wo = box.cmp ? box.cmp[4 + w] : w;
-            double r = -0.5 * q - logdet;
-            if (bad && inside) {
-                r = nan("");
-                atomicAdd(notpd, 1);
-            }
-            r = accumulate ? (ll[wo] + r) : r;
-            if (box.X) r = inside ? (r + box.inside_const) : box.outside;
-            else if (box.cmp) r += box.inside_const;
-            ll[wo] = r;
-        }
+        if (!box.cmp || w < box.cmp[0]) loglike_finish(box, w, q, logdet, bad, !s_outside, accumulate, ll, notpd);
     }
 }
 
@@ -639,6 +623,8 @@ __global__ __launch_bounds__(lr_threads<PP>()) void k_loglike_lowrank(const doub
     }
     double r = -0.5 * (cperp + q) - 0.5 * (logdet0 + logsum);
     bad = bad || !(logsum < INFINITY);       // an overflowing pivot product is a failure, not a silent -inf
+    // loglike_finish, written out: through the helper the forms of 11 GPs and more take up to 82 more registers and the one
+    // of 13 GPs loses a wave per SIMD (the scatter index wo has to be loaded up here, ahead of the algebra)
     if (bad && inside) {
         r = nan("");
         atomicAdd(notpd, 1);
@@ -714,6 +700,8 @@ __global__ __launch_bounds__(lr_threads<PP>()) void k_loglike_lowrank_multi(cons
             partial_sums<PP>(smg, c.mpart, c.spart, c.amp, c.noise, P, c.nchunk, c.nI64, Wld, w, lane, grp);
         __syncthreads();
         if (grp != 0 || !live) continue;               // (uniform per wave; every wave still reaches the barriers above)
+        // From here to `bad` a copy of k_loglike_lowrank's algebra on purpose: a shared force-inlined body made every form
+        // spill (up to 1.7 KB of scratch at 16 GPs).
         double m[PP], g[PP];
 #pragma unroll
         for (int p = 0; p < PP; ++p) {
@@ -776,11 +764,61 @@ __global__ __launch_bounds__(256) void k_lowrank_sum(const double* __restrict__ 
     ll[cmp[4 + w]] = total + inside_const;
 }
 
-__global__ void k_box(const double* __restrict__ X, int64_t W, int d, const double* __restrict__ lo,
-                      const double* __restrict__ hi, double outside, double inside_const, double* __restrict__ ll);
+// the per-emulator blocks of a chain's log-likelihood, [E][Wcap] in the chain's first context (k_loglike_lowrank_multi / k_lowrank_sum)
+int ensure_lr_blocks(gpb_ctx* ctx, int E) {
+    if (E < 2 || !ctx->lr_split) return 0;
+    return pool_grow(ctx, &ctx->lr_blocks, &ctx->lr_blocks_cap, (int64_t)E * ctx->Wcap);
+}
 
-// box_* optional (X_box == nullptr: no prior box).  The register-resident kernel applies the box itself;
-// the generic kernels are followed by k_box.
+// The block log-likelihoods of a chain's compacted batch, added up in emuList order, when every block takes the low-rank
+// kernel: one launch that walks the emulators (or one workgroup per (walker tile, emulator) and the ordered sum).  *taken =
+// false: not this chain, nothing was launched, and the caller runs one launch_loglike per emulator.
+int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double* ll_dev, const int* cmpv, double inside_const,
+                                 bool* taken) {
+    gpb_ctx* ctx = ctxs[0];
+    *taken = ctx->chain_batch && E > 1 && E <= MAX_LR_CTX;
+    int64_t pmax = 0;
+    for (int e = 0; e < E && *taken; ++e) {
+        *taken = lowrank_applies(ctxs[e]) && ctxs[e]->fuse_finalize && ctxs[e]->Wld == ctx->Wld;
+        pmax = ctxs[e]->P > pmax ? ctxs[e]->P : pmax;
+    }
+    if (!*taken) return 0;
+    LrTable tab;
+    for (int e = 0; e < E; ++e) {
+        const gpb_ctx* c = ctxs[e];
+        tab.c[e] = LrCtx{c->mpart, c->spart, c->amp, c->noise, c->lr_R, c->lr_v0, c->notpd, c->lr_cperp, c->lr_logdet0,
+                         (int)c->P, (int)((c->Np + KX_CHUNK - 1) / KX_CHUNK), (int)(c->Np / 64)};
+    }
+    tab.E = E;
+    // one workgroup per (walker tile, emulator) + the ordered sum, when the blocks' buffer is there (ensure_lr_blocks;
+    // option key 49 = 0: the one-launch walk — the A/B, and the bit-identity test)
+    double* blocks = (ctx->lr_split && ctx->lr_blocks && ctx->lr_blocks_cap >= (int64_t)E * ctx->Wld) ? ctx->lr_blocks : nullptr;
+    const dim3 grid((unsigned)((W + 63) / 64), blocks ? (unsigned)E : 1u);
+#define GPB_LRM(PPV)                                                                                             \
+    hipLaunchKernelGGL(k_loglike_lowrank_multi<PPV>, grid, dim3(lr_threads<PPV>()), 0, ctx->stream, tab, ctx->Wld, W, ll_dev, cmpv, inside_const, blocks)
+    if (pmax <= 4) GPB_LRM(4); else if (pmax <= 8) GPB_LRM(8); else if (pmax <= 12) GPB_LRM(12); else GPB_LRM(16);
+#undef GPB_LRM
+    if (blocks)
+        hipLaunchKernelGGL(k_lowrank_sum, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, ctx->stream, blocks, E, ctx->Wld, W,
+                           ll_dev, cmpv, inside_const);
+    if (hipGetLastError() != hipSuccess) GPB_FAIL(GPB_E_HIP, "gpb: k_loglike_lowrank_multi launch failed");
+    return 0;
+}
+
+// ------------------------------------------------------------------ prior box
+__global__ void k_box(const double* __restrict__ X, int64_t W, int d, const double* __restrict__ lo,
+                      const double* __restrict__ hi, double outside, double inside_const,
+                      double* __restrict__ ll) {
+    const int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (w >= W) return;
+    bool in = true;
+    for (int k = 0; k < d; ++k) {
+        const double x = X[w * d + k];
+        in = in && (x > lo[k]) && (x < hi[k]);      // strict (src/mcmc.py:275)
+    }
+    ll[w] = in ? (ll[w] + inside_const) : outside;
+}
+
 static bool block_kernels_apply(const gpb_ctx* ctx) {
     return ctx->mode == GPB_MODE_PCA && ctx->M <= 64 && ctx->P <= 96 && !ctx->force_generic_mvn;
 }
@@ -793,6 +831,21 @@ bool loglike_fuses_finalize(const gpb_ctx* ctx, int64_t W) {
     return block_kernels_apply(ctx) && ctx->P <= 32 && ctx->fuse_finalize && W <= ctx->mvn_wg_switch;
 }
 
+// Where the generic kernels keep a walker's augmented (M + 1) x (M + 1) matrix: in LDS behind the `small` bytes of their
+// vectors, or (M > ~135) in a slab of ctx->mvn_ws, grown here.  Out: gws (null: LDS) and the dynamic LDS bytes sh.
+static int mvn_storage(gpb_ctx* ctx, int64_t W, int64_t M, size_t small, double** gws, size_t* sh) {
+    *gws = nullptr;
+    *sh = small + (size_t)(M + 1) * (M + 1) * sizeof(double);
+    if (*sh <= 150 * 1024) return 0;
+    int rc = pool_grow(ctx, &ctx->mvn_ws, &ctx->mvn_ws_cap, W * (M + 1) * (M + 1));
+    if (rc) return rc;
+    *gws = ctx->mvn_ws;
+    *sh = small;
+    return 0;
+}
+
+// box_* optional (X_box == nullptr: no prior box).  The register-resident kernel applies the box itself;
+// the generic kernels are followed by k_box.
 int launch_loglike(gpb_ctx* ctx, int64_t W, double* ll_dev, bool accumulate, bool from_partials, const double* X_box,
                    const double* lo_dev, const double* hi_dev, double outside, double inside_const, const int* cmp_dev) {
     const int64_t M = ctx->M, P = ctx->P;
@@ -812,21 +865,10 @@ int launch_loglike(gpb_ctx* ctx, int64_t W, double* ll_dev, bool accumulate, boo
         if (W <= ctx->mvn_wg_switch) return launch_loglike_wg(ctx, W, ll_dev, accumulate, box, part);   // same bits, lower latency
         return launch_loglike_reg<64>(ctx, W, ll_dev, accumulate, box, part);
     }
-    const size_t small = (2 * P + 2 * M) * sizeof(double);
-    const size_t mat = (size_t)(M + 1) * (M + 1) * sizeof(double);
-    double* gws = nullptr;
-    size_t sh = small + mat;
-    if (sh > 150 * 1024) {                       // M > ~135: slab in HBM/L2 instead of LDS
-        const int64_t need = W * (M + 1) * (M + 1);
-        if (need > ctx->mvn_ws_cap) {
-            GPB_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->mvn_ws) pool_free(ctx->mvn_ws);
-            GPB_HIP(pool_malloc_t(&ctx->mvn_ws, need * sizeof(double)));
-            ctx->mvn_ws_cap = need;
-        }
-        gws = ctx->mvn_ws;
-        sh = small;
-    }
+    double* gws;
+    size_t sh;
+    int rc = mvn_storage(ctx, W, M, (2 * P + 2 * M) * sizeof(double), &gws, &sh);
+    if (rc) return rc;
     if (sh > 64 * 1024) {
         GPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_loglike<false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
@@ -847,20 +889,10 @@ int launch_loglike(gpb_ctx* ctx, int64_t W, double* ll_dev, bool accumulate, boo
 }
 
 int launch_mvn(gpb_ctx* ctx, const double* dY_dev, const double* cov_dev, int64_t W, int64_t M, double* ll_dev) {
-    const size_t mat = (size_t)(M + 1) * (M + 1) * sizeof(double);
-    size_t sh = M * sizeof(double) + mat;
-    double* gws = nullptr;
-    if (sh > 150 * 1024) {
-        const int64_t need = W * (M + 1) * (M + 1);
-        if (need > ctx->mvn_ws_cap) {
-            GPB_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->mvn_ws) pool_free(ctx->mvn_ws);
-            GPB_HIP(pool_malloc_t(&ctx->mvn_ws, need * sizeof(double)));
-            ctx->mvn_ws_cap = need;
-        }
-        gws = ctx->mvn_ws;
-        sh = M * sizeof(double);
-    }
+    double* gws;
+    size_t sh;
+    int rc = mvn_storage(ctx, W, M, M * sizeof(double), &gws, &sh);
+    if (rc) return rc;
     if (sh > 64 * 1024) {
         GPB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mvn<false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
@@ -1003,433 +1035,16 @@ int launch_compact(gpb_ctx* ctx, const double* X_dev, int64_t W, int64_t dx, con
 
 // the buffer of gathered rows [Wcap][dx], grown on demand
 int ensure_cmp_rows(gpb_ctx* ctx, int64_t dx) {
-    if (ctx->cmp_X_cap < ctx->Wcap * dx) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->cmp_X) pool_free(ctx->cmp_X);
-        ctx->cmp_X = nullptr;
-        GPB_HIP(pool_malloc_t(&ctx->cmp_X, sizeof(double) * (size_t)(ctx->Wcap * dx)));
-        GPB_HIP(hipMemsetAsync(ctx->cmp_X, 0, sizeof(double) * (size_t)(ctx->Wcap * dx), ctx->stream));   // rows past the count are read (not used) by the upper-bound launches
-        ctx->cmp_X_cap = ctx->Wcap * dx;
-    }
+    if (ctx->cmp_X_cap >= ctx->Wcap * dx) return 0;    // (tested here as well: the memset below is for a NEW buffer only)
+    int rc = pool_grow(ctx, &ctx->cmp_X, &ctx->cmp_X_cap, ctx->Wcap * dx);
+    if (rc) return rc;
+    GPB_HIP(hipMemsetAsync(ctx->cmp_X, 0, sizeof(double) * (size_t)(ctx->Wcap * dx), ctx->stream));   // rows past the count are read (not used) by the upper-bound launches
     return 0;
 }
 
 // true when gpb_logpost / gpb_emcee_run may evaluate the rows inside the box only (a block likelihood kernel follows)
 bool compaction_applies(const gpb_ctx* ctx) {
     return ctx->compact && (lowrank_applies(ctx) || block_kernels_apply(ctx));
-}
-
-// ------------------------------------------------------------------ prior box
-__global__ void k_box(const double* __restrict__ X, int64_t W, int d, const double* __restrict__ lo,
-                      const double* __restrict__ hi, double outside, double inside_const,
-                      double* __restrict__ ll) {
-    const int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (w >= W) return;
-    bool in = true;
-    for (int k = 0; k < d; ++k) {
-        const double x = X[w * d + k];
-        in = in && (x > lo[k]) && (x < hi[k]);      // strict (src/mcmc.py:275)
-    }
-    ll[w] = in ? (ll[w] + inside_const) : outside;
-}
-
-// ---- red/blue split ----------------------------------------------------------------------------------
-// emcee's RedBlueMove shuffles which walkers form the two halves at every step (randomize_split=True,
-// its default).  Here the shuffle is a keyed pseudo-random permutation pi_step of [0, n) that every
-// thread (and every rank) can evaluate for a single index without communication or sorting: a 4-round
-// Feistel network on 2*hb >= log2(n) bits with cycle walking.  Walker k of half h is pi(2k + h); with
-// randomize = 0, pi is the identity (emcee's inds = arange(n) % 2).
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-struct SplitPerm {
-    uint32_t n, hb, k0, k1, on;
-    __device__ __forceinline__ int64_t operator()(int64_t i) const {
-        if (!on) return i;
-        const uint32_t mask = (1u << hb) - 1u;
-        uint32_t x = (uint32_t)i;
-        do {
-            uint32_t L = x >> hb, R = x & mask;
-#pragma unroll
-            for (uint32_t r = 0; r < 4; ++r) {
-                const uint32_t F = mix32(R ^ (k0 + r * 0x9E3779B9u)) ^ mix32(k1 + r);
-                const uint32_t t = L ^ (F & mask);
-                L = R;
-                R = t;
-            }
-            x = (L << hb) | R;
-        } while (x >= n);                      // cycle walking keeps it a bijection on [0, n)
-        return (int64_t)x;
-    }
-    // the inverse map: rounds backwards (a round takes (L, R) to (R, L ^ F(R))), cycle walking likewise
-    __device__ __forceinline__ int64_t inv(int64_t i) const {
-        if (!on) return i;
-        const uint32_t mask = (1u << hb) - 1u;
-        uint32_t x = (uint32_t)i;
-        do {
-            uint32_t L = x >> hb, R = x & mask;
-#pragma unroll
-            for (int r = 3; r >= 0; --r) {
-                const uint32_t F = mix32(L ^ (k0 + (uint32_t)r * 0x9E3779B9u)) ^ mix32(k1 + (uint32_t)r);
-                const uint32_t t = R ^ (F & mask);
-                R = L;
-                L = t;
-            }
-            x = (L << hb) | R;
-        } while (x >= n);
-        return (int64_t)x;
-    }
-};
-__device__ __forceinline__ SplitPerm make_perm(uint64_t seed, uint32_t step, int64_t n, int hb, int randomize) {
-    const U4 k = philox(seed, 0xFFFFFFFFu, step, 0u, 7u);
-    return SplitPerm{(uint32_t)n, (uint32_t)hb, k.x, k.y, (uint32_t)randomize};
-}
-
-// A slot of the compacted batch for every walker of the workgroup that asks for one (`want`, set in the walker's lane t0 = 0):
-// ONE atomic per workgroup — 2048 walkers taking their slots from one counter one by one serialised on the atomic's return
-// (k_accept_propose 18 us at 2048 rows a batch against 8 at 256).  The order of the slots does not matter (a row's result
-// does not depend on its place in the batch).  Barriers: only in workgroups whose every thread has a walker (`full`, uniform
-// per workgroup); the ensemble's last, partly filled workgroup takes the slots walker by walker.  Returns the slot in the
-// lane t0 = 0 that asked (-1 elsewhere).
-__device__ __forceinline__ int take_slot(bool want, bool full, int* __restrict__ cmp) {
-    __shared__ int s_want[32], s_base;                 // up to 1024 threads = 32 walkers per workgroup
-    if (!full) return want ? atomicAdd(cmp, 1) : -1;
-    const int wl = (int)(threadIdx.x >> 5), nw = (int)(blockDim.x >> 5);
-    if ((threadIdx.x & 31) == 0) s_want[wl] = want ? 1 : 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int i = 0; i < nw; ++i) tot += s_want[i];
-        s_base = tot ? atomicAdd(cmp, tot) : 0;
-    }
-    __syncthreads();
-    if (!want) return -1;
-    int off = 0;
-    for (int i = 0; i < wl; ++i) off += s_want[i];
-    return s_base + off;
-}
-
-// lo != nullptr (the C-driven loop over a compacted chain): the prior-box test of the rows [r0, r0 + chunk) — this
-// rank's rows of the batch — is taken here, on the proposal still in registers: flags[k - r0] = 1 inside / 0 outside
-// (strict inequalities, src/mcmc.py:275) and ll[k] = outside for the rows outside; k_compact_gather then ranks the
-// flags itself and k_compact_mark's launch is saved (7.6 of a sharded half-step's 166 us).
-__global__ void k_propose(const double* __restrict__ pos, int64_t nhalf, int d, int half, uint64_t seed,
-                          uint32_t step, double a, double* __restrict__ q, double* __restrict__ factor, int hb,
-                          int randomize, const double* __restrict__ lo = nullptr, const double* __restrict__ hi = nullptr,
-                          double outside = 0.0, double* __restrict__ ll = nullptr, int* __restrict__ flags = nullptr,
-                          int64_t r0 = 0, int64_t chunk = 0, double* __restrict__ Xc = nullptr, int* __restrict__ cmp = nullptr) {
-    // 32 lanes per walker (one parameter each): these kernels sit between the log-probability batches of a
-    // step, so they are organised for latency, not for thread economy — every lane redoes the walker's draws
-#pragma clang fp contract(off)       // emcee's arithmetic rounds every product: no fused multiply-adds in here
-    const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t k = gid >> 5;
-    const int t0 = (int)(gid & 31);
-    const bool full = ((int64_t)(blockIdx.x + 1) * blockDim.x) >> 5 <= nhalf;      // every thread of this workgroup has a walker
-    if (k >= nhalf) return;
-    const SplitPerm pi = make_perm(seed, step, 2 * nhalf, hb, randomize);
-    const U4 r = philox(seed, (uint32_t)k, step, (uint32_t)half, 0u);
-    const double u = u01(r.x, r.y);
-    // emcee StretchMove.get_proposal, operation for operation:
-    //   zz = ((a - 1) * u + 1) ** 2 / a ;  q = c - (c - s) * zz ;  factor = (ndim - 1) * log(zz)
-    const double zs = (a - 1.0) * u + 1.0;
-    const double zz = (zs * zs) / a;
-    const int64_t j = (int64_t)(((uint64_t)r.z * (uint64_t)nhalf) >> 32);
-    const double* s = pos + pi(2 * k + half) * d;
-    const double* c = pos + pi(2 * j + (1 - half)) * d;
-    int ok = 1;
-    double v2[2] = {0.0, 0.0};                         // the first two parameters of this lane (all of them for d <= 64)
-    int nv = 0;
-    for (int t = t0; t < d; t += 32) {
-        const double v = c[t] - (c[t] - s[t]) * zz;
-        q[k * d + t] = v;
-        if (lo) ok &= (int)(v > lo[t]) & (int)(v < hi[t]);
-        if (nv < 2) v2[nv] = v;
-        ++nv;
-    }
-    if (t0 == 0) factor[k] = (d - 1.0) * log(zz);
-    if (lo) {                                          // wave-uniform; a walker's 32 lanes are one half of a wave
-        const unsigned long long out = __ballot(!ok);
-        const bool in = (((threadIdx.x & 32) ? (out >> 32) : out) & 0xffffffffull) == 0ull;
-        const bool mine = k >= r0 && k < r0 + chunk;
-        if (t0 == 0 && mine) {
-            if (flags) flags[k - r0] = in ? 1 : 0;
-            if (!in && ll) ll[k] = outside;
-        }
-        if (Xc) {
-            // ... and gathers the rows inside the box itself: a slot from a counter (cmp[0], zeroed by k_accept), in
-            // whatever order the walkers arrive — a row's result does not depend on its place in the batch
-            int slot = take_slot(t0 == 0 && mine && in, full, cmp);
-            if (slot >= 0) cmp[4 + slot] = (int)(k - r0);
-            slot = __shfl(slot, (int)(threadIdx.x & 32), 64);
-            if (slot >= 0) {
-                if (t0 < d) Xc[(int64_t)slot * d + t0] = v2[0];
-                if (t0 + 32 < d) Xc[(int64_t)slot * d + t0 + 32] = v2[1];
-                // chains with more than 64 parameters (parameterTrafoPCA: the chain's ndim is the map's d_in, which only
-                // the GPs' reduced d bounds): the same arithmetic again, operation for operation
-                for (int t = t0 + 64; t < d; t += 32) Xc[(int64_t)slot * d + t] = c[t] - (c[t] - s[t]) * zz;
-            }
-        }
-    }
-}
-// Where the accept step finds a proposal's log-probability.  Plain: lpq[slot].  Balanced sharding (see
-// k_balance_gather): lpq is the all-gathered array of the ranks' padded slices, a proposal inside the box is found through
-// its position g in the ordered list of all live rows — slice g / per, entry g % per — and one outside the box has
-// `outside` without a memory access.
-struct LpSource {
-    const double* lpq;
-    const int* rank_of;                // null: plain
-    const int* meta;                   // [0] = live rows in the whole batch, [1] = rows per slice
-    int64_t chunk;                     // slice stride in lpq
-    double outside;
-    __device__ __forceinline__ double at(int64_t slot) const {
-        if (!rank_of) return lpq[slot];
-        const int g = rank_of[slot];
-        if (g < 0) return outside;
-        const int per = meta[1];
-        return lpq[(int64_t)(g / per) * chunk + (g % per)];
-    }
-};
-
-__global__ void k_accept(double* __restrict__ pos, double* __restrict__ lp, int64_t nhalf, int d, int half,
-                         uint64_t seed, uint32_t step, const double* __restrict__ q,
-                         const double* __restrict__ factor, const double* __restrict__ lpq,
-                         long long* __restrict__ naccept, int hb, int randomize,
-                         long long* __restrict__ n_nan, int* __restrict__ cmp = nullptr,
-                         unsigned long long* __restrict__ hint = nullptr, int64_t W_batch = 0,
-                         unsigned long long* __restrict__ rows_live = nullptr, const int* __restrict__ rank_of = nullptr,
-                         const int* __restrict__ meta = nullptr, int64_t chunk = 0, double outside = 0.0) {
-    // 32 lanes per walker, all inside one wave: every lane takes the same decision from the OLD lp[idx]
-    // (the load precedes lane 0's store in program order), then moves its own parameters
-#pragma clang fp contract(off)
-    const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t k = gid >> 5;
-    const int t0 = (int)(gid & 31);
-    if (cmp && gid == 0) {
-        // the batch's kernels are done with the count of rows inside the box (stream order): report it (tile-shape
-        // rule of the next launches, profile counter) and re-arm the counter for the next proposal kernel
-        const int cnt = cmp[0];
-        if (hint) __hip_atomic_store(hint, ((unsigned long long)W_batch << 32) | (unsigned long long)cnt, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_SYSTEM);
-        if (rows_live) atomicAdd(rows_live, (unsigned long long)cnt);
-        cmp[0] = 0;
-    }
-    if (k >= nhalf) return;
-    const SplitPerm pi = make_perm(seed, step, 2 * nhalf, hb, randomize);
-    const U4 r = philox(seed, (uint32_t)k, step, (uint32_t)half, 1u);
-    const double u = u01(r.x, r.y);
-    const int64_t idx = pi(2 * k + half);
-    const double lpq_k = LpSource{lpq, rank_of, meta, chunk, outside}.at(k);
-    // emcee raises "Probability function returned NaN" at the step it happens (emcee/ensemble.py compute_log_prob);
-    // here the proposal is rejected (NaN compares false) and counted, and the host raises at its next check
-    if (n_nan && t0 == 0 && lpq_k != lpq_k) atomicAdd(reinterpret_cast<unsigned long long*>(n_nan), 1ull);
-    const double diff = (factor[k] + lpq_k) - lp[idx];
-    const bool take = diff > log(u);                                 // emcee RedBlueMove.propose: f + nlp - lp[j] > log(rand)
-    __builtin_amdgcn_wave_barrier();                                 // keep the loads above the stores below
-    if (take) {
-        for (int t = t0; t < d; t += 32) pos[idx * d + t] = q[k * d + t];
-        if (t0 == 0) {
-            lp[idx] = lpq_k;
-            if (naccept) naccept[idx] += 1;
-        }
-    }
-}
-
-// The accept of one half-step and the proposal of the next in ONE launch (gpb_chain_emcee_run): a proposal needs the
-// positions AFTER the pending accept, of its own walker and of its partner; instead of waiting for another kernel to
-// have moved them, a walker group looks both walkers up — the inverse split permutation tells whether a walker is in the
-// pending half and in which slot — and takes that slot's accept decision itself (same draws, same arithmetic as the
-// group that owns the slot).  Accepted walkers are read from the pending proposals q_a, all others from pos, which this
-// kernel writes for accepted walkers only: no read of a location another group writes.  lp is ping-ponged (lp_in is
-// read by every decision, lp_out written once per walker), q / factor / lpq alternate between two sets.
-struct PendingAccept {
-    const double *q, *factor, *lp_in;
-    LpSource lpq;
-    uint64_t seed;
-    uint32_t step;
-    int half;
-};
-__device__ __forceinline__ bool accept_decision(const PendingAccept& A, int64_t slot, int64_t idx, double& lpq_k) {
-#pragma clang fp contract(off)
-    const U4 r = philox(A.seed, (uint32_t)slot, A.step, (uint32_t)A.half, 1u);
-    const double u = u01(r.x, r.y);
-    lpq_k = A.lpq.at(slot);
-    const double diff = (A.factor[slot] + lpq_k) - A.lp_in[idx];
-    return diff > log(u);                                            // as k_accept
-}
-__global__ void k_accept_propose(double* __restrict__ pos, const double* __restrict__ lp_in, double* __restrict__ lp_out,
-                                 int64_t nhalf, int d, uint64_t seed, int hb, int randomize,
-                                 int half_a, uint32_t step_a, const double* __restrict__ q_a,
-                                 const double* __restrict__ factor_a, const double* __restrict__ lpq_a,
-                                 long long* __restrict__ naccept, long long* __restrict__ n_nan, int* __restrict__ cmp_prev,
-                                 unsigned long long* __restrict__ hint, int64_t W_batch,
-                                 unsigned long long* __restrict__ rows_live,
-                                 int half_p, uint32_t step_p, double a, double* __restrict__ q_p,
-                                 double* __restrict__ factor_p, const double* __restrict__ lo,
-                                 const double* __restrict__ hi, double outside, double* __restrict__ ll, int64_t r0,
-                                 int64_t chunk, double* __restrict__ Xc, int* __restrict__ cmp,
-                                 const int* __restrict__ rank_of_a, const int* __restrict__ meta_a, int64_t chunk_a,
-                                 int* __restrict__ flags_p) {
-#pragma clang fp contract(off)
-    const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const int64_t k = gid >> 5;
-    const int t0 = (int)(gid & 31);
-    if (gid == 0) {                                    // as k_accept: report and re-arm the finished batch's counter
-        const int cnt = cmp_prev[0];
-        if (hint) __hip_atomic_store(hint, ((unsigned long long)W_batch << 32) | (unsigned long long)cnt, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_SYSTEM);
-        if (rows_live) atomicAdd(rows_live, (unsigned long long)cnt);
-        cmp_prev[0] = 0;
-    }
-    const bool full = ((int64_t)(blockIdx.x + 1) * blockDim.x) >> 5 <= nhalf;      // every thread of this workgroup has a walker
-    if (k >= nhalf) return;
-    const SplitPerm pa = make_perm(seed, step_a, 2 * nhalf, hb, randomize);
-    const PendingAccept A{q_a, factor_a, lp_in, LpSource{lpq_a, rank_of_a, meta_a, chunk_a, outside}, seed, step_a, half_a};
-    {   // ---- the accept of slot k (k_accept, with lp written to the other buffer)
-        const int64_t idx = pa(2 * k + half_a);
-        double lpq_k;
-        const bool take = accept_decision(A, k, idx, lpq_k);
-        if (n_nan && t0 == 0 && lpq_k != lpq_k) atomicAdd(reinterpret_cast<unsigned long long*>(n_nan), 1ull);
-        if (take)
-            for (int t = t0; t < d; t += 32) pos[idx * d + t] = q_a[k * d + t];
-        if (t0 == 0) {
-            lp_out[idx] = take ? lpq_k : lp_in[idx];
-            if (take && naccept) naccept[idx] += 1;
-            const int64_t other = pa(2 * k + (1 - half_a));           // the walker of the resting half with this slot
-            lp_out[other] = lp_in[other];
-        }
-    }
-    // ---- the proposal of slot k for (step_p, half_p): k_propose on the positions after the pending accept
-    const SplitPerm pp = make_perm(seed, step_p, 2 * nhalf, hb, randomize);
-    const U4 r = philox(seed, (uint32_t)k, step_p, (uint32_t)half_p, 0u);
-    const double u = u01(r.x, r.y);
-    const double zs = (a - 1.0) * u + 1.0;
-    const double zz = (zs * zs) / a;
-    const int64_t j = (int64_t)(((uint64_t)r.z * (uint64_t)nhalf) >> 32);
-    auto current = [&](int64_t w) -> const double* {
-        const int64_t y = pa.inv(w);
-        if ((int)(y & 1) == half_a) {
-            double unused;
-            if (accept_decision(A, y >> 1, w, unused)) return q_a + (y >> 1) * d;
-        }
-        return pos + w * d;
-    };
-    const double* s = current(pp(2 * k + half_p));
-    const double* c = current(pp(2 * j + (1 - half_p)));
-    int ok = 1;
-    double v2[2] = {0.0, 0.0};
-    int nv = 0;
-    for (int t = t0; t < d; t += 32) {
-        const double v = c[t] - (c[t] - s[t]) * zz;
-        q_p[k * d + t] = v;
-        ok &= (int)(v > lo[t]) & (int)(v < hi[t]);
-        if (nv < 2) v2[nv] = v;
-        ++nv;
-    }
-    if (t0 == 0) factor_p[k] = (d - 1.0) * log(zz);
-    const unsigned long long out = __ballot(!ok);
-    const bool in = (((threadIdx.x & 32) ? (out >> 32) : out) & 0xffffffffull) == 0ull;
-    if (flags_p) {                                     // balanced sharding: the flag of EVERY row, k_balance_gather does the rest
-        if (t0 == 0) flags_p[k] = in ? 1 : 0;
-        return;
-    }
-    const bool mine = k >= r0 && k < r0 + chunk;
-    if (t0 == 0 && mine && !in) ll[k] = outside;
-    int slot = take_slot(t0 == 0 && mine && in, full, cmp);
-    if (slot >= 0) cmp[4 + slot] = (int)(k - r0);
-    slot = __shfl(slot, (int)(threadIdx.x & 32), 64);
-    if (slot >= 0) {
-        if (t0 < d) Xc[(int64_t)slot * d + t0] = v2[0];
-        if (t0 + 32 < d) Xc[(int64_t)slot * d + t0 + 32] = v2[1];
-        for (int t = t0 + 64; t < d; t += 32) Xc[(int64_t)slot * d + t] = c[t] - (c[t] - s[t]) * zz;   // ndim > 64: as k_propose
-    }
-}
-
-// Balanced sharding of a batch over the ranks (gpb_chain_emcee_run with a communicator).  A rank's contiguous share of
-// the proposals holds a varying number of rows inside the prior box (256 proposals: 120 +- 8), and the step waits for the
-// rank with the most — which, more often than not, needs one walker tile more than the others.  Every rank knows all
-// proposals, so every rank ranks ALL live rows in order here (flags from the proposal kernel; counts of integers: any
-// order) and takes the `r`-th of R equal slices of that list: rows with rank g in [r per, (r + 1) per), per =
-// ceil(live / R), gathered into Xc.  The slices are padded to the collective's fixed size (per <= nhalf / R), so the
-// all-gather is the one of the contiguous scheme; the accept kernels find a live row's value through rank_of (LpSource).
-//   flags[nhalf] in; rank_of[nhalf] out (-1 outside the box); meta = {live, per}; cmp[0] = rows of this rank's slice,
-//   cmp[4 + i] = i (the likelihood kernel's scatter list: results land densely in the send buffer)
-__global__ __launch_bounds__(256) void k_balance_gather(const double* __restrict__ q, int64_t nhalf, int d,
-                                                        const int* __restrict__ flags, int* __restrict__ rank_of,
-                                                        int R, int r, double* __restrict__ Xc, int* __restrict__ cmp,
-                                                        int* __restrict__ meta) {
-    __shared__ int wsum[4], wbase[4], wtot[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t w0 = (int64_t)blockIdx.x * 256;
-    int before = 0, total = 0;
-    for (int64_t w = tid; w < nhalf; w += 256) {
-        const int f = flags[w];
-        total += f;
-        if (w < w0) before += f;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        before += __shfl_xor(before, o);
-        total += __shfl_xor(total, o);
-    }
-    const bool in = w0 + tid < nhalf && flags[w0 + tid] != 0;
-    const unsigned long long m = __ballot(in);
-    if (lane == 0) { wsum[wave] = __popcll(m); wbase[wave] = before; wtot[wave] = total; }
-    __syncthreads();
-    int off = (wbase[0] + wbase[1]) + (wbase[2] + wbase[3]);
-    const int live = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-    for (int i = 0; i < wave; ++i) off += wsum[i];
-    const int g = in ? off + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-    const int per = live > 0 ? (live + R - 1) / R : 1;
-    const int lo = r * per, hi = min(lo + per, live);
-    if (w0 + tid < nhalf) rank_of[w0 + tid] = g;
-    if (g >= lo && g < hi) {
-        const int64_t src = (w0 + tid) * d, dst = (int64_t)(g - lo) * d;
-        for (int k = 0; k < d; ++k) Xc[dst + k] = q[src + k];
-        cmp[4 + (g - lo)] = g - lo;
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        cmp[0] = hi > lo ? hi - lo : 0;
-        meta[0] = live;
-        meta[1] = per;
-    }
-}
-
-#ifdef GPB_DEBUG_VARIANTS
-// test hooks: the generator and the draws of a (seed, step, half), for the parity tests against the oracle
-__global__ void k_philox_test(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t n) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* v = in + 6 * i;
-    const U4 r = philox((uint64_t)v[0] | ((uint64_t)v[1] << 32), v[2], v[3], v[4], v[5]);
-    out[4 * i + 0] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
-}
-__global__ void k_stretch_draws(int64_t nhalf, int half, uint64_t seed, uint32_t step, int hb, int randomize,
-                                double* __restrict__ u_z, long long* __restrict__ jj, double* __restrict__ u_acc,
-                                long long* __restrict__ perm) {
-    const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (k >= 2 * nhalf) return;
-    perm[k] = make_perm(seed, step, 2 * nhalf, hb, randomize)(k);
-    if (k >= nhalf) return;
-    const U4 r = philox(seed, (uint32_t)k, step, (uint32_t)half, 0u);           // as k_propose
-    u_z[k] = u01(r.x, r.y);
-    jj[k] = (long long)(((uint64_t)r.z * (uint64_t)nhalf) >> 32);
-    const U4 ra = philox(seed, (uint32_t)k, step, (uint32_t)half, 1u);          // as k_accept
-    u_acc[k] = u01(ra.x, ra.y);
-}
-
-// test hook: out[i] = pi_step(i)
-__global__ void k_perm(long long* __restrict__ out, int64_t n, uint64_t seed, uint32_t step, int hb) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = make_perm(seed, step, n, hb, 1)(i);
-}
-#endif  // GPB_DEBUG_VARIANTS
-
-static int half_bits(int64_t n) {
-    int b = 1;
-    while ((1ll << b) < n) ++b;
-    return (b + 1) / 2;
 }
 
 }  // namespace gpb
@@ -1447,466 +1062,3 @@ extern "C" int gpb_box_finish(gpb_ctx* ctx, const double* X_dev, int64_t W, int6
     GPB_HIP(hipGetLastError());
     return 0;
 }
-
-extern "C" int gpb_stretch_propose(gpb_ctx* ctx, const double* pos_dev, int64_t nwalkers, int64_t d, int half,
-                                   uint64_t seed, uint64_t step, double a, double* q_dev, double* factor_dev,
-                                   int randomize_split) {
-    if (!ctx || nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30) || d < 1 || (half != 0 && half != 1))
-        return GPB_E_ARG;
-    const int64_t nh = nwalkers / 2;
-    hipLaunchKernelGGL(k_propose, dim3((unsigned)((nh * 32 + 255) / 256)), dim3(256), 0, ctx->stream, pos_dev, nh, (int)d,
-                       half, seed, (uint32_t)step, a, q_dev, factor_dev, half_bits(nwalkers), randomize_split ? 1 : 0,
-                       (const double*)nullptr, (const double*)nullptr, 0.0, (double*)nullptr, (int*)nullptr, (int64_t)0, (int64_t)0,
-                       (double*)nullptr, (int*)nullptr);
-    GPB_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int gpb_stretch_accept(gpb_ctx* ctx, double* pos_dev, double* lp_dev, int64_t nwalkers, int64_t d,
-                                  int half, uint64_t seed, uint64_t step, const double* q_dev,
-                                  const double* factor_dev, const double* lpq_dev, int64_t* naccept_dev,
-                                  int randomize_split) {
-    if (!ctx || nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30) || d < 1 || (half != 0 && half != 1))
-        return GPB_E_ARG;
-    const int64_t nh = nwalkers / 2;
-    hipLaunchKernelGGL(k_accept, dim3((unsigned)((nh * 32 + 255) / 256)), dim3(256), 0, ctx->stream, pos_dev, lp_dev, nh,
-                       (int)d, half, seed, (uint32_t)step, q_dev, factor_dev, lpq_dev,
-                       reinterpret_cast<long long*>(naccept_dev), half_bits(nwalkers), randomize_split ? 1 : 0,
-                       reinterpret_cast<long long*>(ctx->n_nan), (int*)nullptr, (unsigned long long*)nullptr, (int64_t)0,
-                       (unsigned long long*)nullptr);
-    GPB_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int gpb_stretch_nan_count(gpb_ctx* ctx, int64_t* count_host, int reset) {
-    if (!ctx || !count_host) return GPB_E_ARG;
-    GPB_HIP(hipSetDevice(ctx->device));
-    long long v = 0;
-    GPB_HIP(hipMemcpyAsync(&v, ctx->n_nan, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (reset) GPB_HIP(hipMemsetAsync(ctx->n_nan, 0, sizeof(long long), ctx->stream));
-    *count_host = (int64_t)v;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- device-resident sampling loop
-__global__ void k_store_step(const double* __restrict__ pos, const double* __restrict__ lp, double* __restrict__ chain,
-                             double* __restrict__ lpchain, int64_t nw, int d) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (chain && i < nw * d) chain[i] = pos[i];
-    if (lpchain && i < nw) lpchain[i] = lp[i];
-}
-
-__global__ void k_fill(double* __restrict__ x, int64_t n, double v) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i < n) x[i] = v;
-}
-
-// ---- chains of several emulators ---------------------------------------------------------------------
-// Chain._predict concatenates the emulators' observables and the covariance is block-diagonal over them
-// (src/mcmc.py:153-166), so the log-likelihood is the sum of the emulators' blocks; all emulators see the same rows of
-// the same parameter space (those with a parameter map, src/emulator.py:492-551, through gpb_param_map).
-namespace {
-int64_t chain_ndim(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }
-// parameters of the CHAIN (a parameter map's d_in; the GPs' own d is bounded by 64 in gpb_gp_set).  The proposal kernels
-// take any number; k_compact_mark stages 256 rows of it in LDS in tiles, so the bound is only a sanity limit.
-constexpr int64_t MAX_CHAIN_NDIM = 512;
-
-// the per-emulator blocks of a chain's log-likelihood, [E][Wcap] in the chain's first context (k_loglike_lowrank_multi / k_lowrank_sum)
-int ensure_lr_blocks(gpb_ctx* ctx, int E) {
-    if (E < 2 || !ctx->lr_split) return 0;
-    const int64_t need = (int64_t)E * ctx->Wcap;
-    if (ctx->lr_blocks_cap >= need) return 0;
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->lr_blocks) { pool_free(ctx->lr_blocks); ctx->lr_blocks = nullptr; }
-    ctx->lr_blocks_cap = 0;
-    GPB_HIP(pool_malloc_t(&ctx->lr_blocks, sizeof(double) * (size_t)need));
-    ctx->lr_blocks_cap = need;
-    return 0;
-}
-
-// every context usable by the compacted chain path?  (same device, stream and parameter space; likelihood installed;
-// a block likelihood kernel applies)
-int chain_check(gpb_ctx* const* ctxs, int E, const char* who) {
-    gpb_ctx* ctx = ctxs[0];
-    for (int e = 0; e < E; ++e) {
-        const gpb_ctx* c = ctxs[e];
-        if (!c) GPB_FAIL(GPB_E_ARG, std::string(who) + ": null context");
-        if (!c->have_like) GPB_FAIL(GPB_E_STATE, std::string(who) + " before gpb_like_set");
-        if (c->device != ctx->device || c->stream != ctx->stream)
-            GPB_FAIL(GPB_E_STATE, std::string(who) + ": the emulators' contexts must share one device and stream");
-        if (chain_ndim(c) != chain_ndim(ctx)) GPB_FAIL(GPB_E_ARG, std::string(who) + ": the emulators disagree on the number of parameters");
-        if (!compaction_applies(c))
-            GPB_FAIL(GPB_E_STATE, std::string(who) + ": needs the block likelihood kernels (PCA mode, M <= 64 or npc <= 16) for every emulator");
-        if (c->pmap_d_in > 0 && c->pmap_d_out != c->d)
-            GPB_FAIL(GPB_E_STATE, std::string(who) + ": a parameter map's output must be the GPs' input");
-    }
-    if (chain_ndim(ctx) > MAX_CHAIN_NDIM)
-        GPB_FAIL(GPB_E_ARG, std::string(who) + ": more than 512 chain parameters");
-    return 0;
-}
-
-// log-posterior of rows X[W][ndim] over all emulators, rows inside the box only (ctxs[0] owns the compaction)
-int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
-               const double* hi_dev, double outside, double inside_const, int premarked = 0, const int* cmpv = nullptr) {
-    gpb_ctx* c0 = ctxs[0];
-    int rc;
-    for (int e = 0; e < E; ++e)
-        if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
-    if ((rc = ensure_lr_blocks(c0, E))) return rc;
-    if ((rc = launch_compact(c0, X_dev, W, chain_ndim(c0), lo_dev, hi_dev, outside, ll_dev, premarked))) return rc;
-    if (!cmpv) cmpv = c0->cmp_idx;                     // (count, -, -, -, indices ...) of the rows inside the box
-    // Three passes over the emulators (each kernel sees what it would see in its own emulator's sequence: same bits):
-    // (1) parameter maps, then K*^T and the mean partials — ONE launch per run of emulators of equal padded size
-    //     (k_kcross_multi);
-    // (2) V = L^-1 K*^T with the fused sum of squares: ONE launch for each run of emulators whose designs pad to the same
-    //     Np (the reference's analyses: nine emulators on one design) instead of one partly filled launch per emulator;
-    // (3) the block log-likelihoods, added up in emuList order: one launch that walks the emulators (k_loglike_lowrank_multi)
-    //     when every block takes the low-rank kernel, else one launch per emulator.
-    const double* Xg[64];
-    gpb_ctx* mapped[64];
-    int nmapped = 0;
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        Xg[e] = c0->cmp_X;
-        c->hint_from = c0;
-        if (c->pmap_d_in > 0) {                        // this emulator's GPs see the PCA-reduced parameters
-            mapped[nmapped++] = c;
-            Xg[e] = c->Xs;
-        }
-    }
-    if (nmapped > 1 && c0->chain_batch) {              // the maps of all mapped emulators over the gathered rows: one launch
-        if ((rc = launch_param_maps(mapped, nmapped, c0->cmp_X, W))) { c0->err = mapped[0]->err; return rc; }
-    } else {
-        for (int i = 0; i < nmapped; ++i)
-            if ((rc = gpb_param_map(mapped[i], c0->cmp_X, W, mapped[i]->Xs))) { c0->err = mapped[i]->err; return rc; }
-    }
-    for (int e = 0; e < E;) {              // K*^T: one launch per run of emulators of equal padded size and PADDED input
-        int n = 1;                                     // count (parameterTrafoPCA emulators keep 17-19 of 20 inputs each: one launch)
-        while (c0->chain_batch && e + n < E && ctxs[e + n]->Np == ctxs[e]->Np && ctxs[e + n]->dpad == ctxs[e]->dpad && n < 32) ++n;
-        if ((rc = launch_kcross_group(ctxs + e, Xg + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
-        e += n;
-    }
-    for (int e = 0; e < E;) {
-        int n = 1, gps = (int)ctxs[e]->P;
-        while (c0->chain_batch && e + n < E && ctxs[e + n]->Np == ctxs[e]->Np && gps + (int)ctxs[e + n]->P <= GPB_MAX_MULTI_GP) {
-            gps += (int)ctxs[e + n]->P;
-            ++n;
-        }
-        if ((rc = launch_vsq(ctxs + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
-        e += n;
-    }
-    if (c0->chain_batch && E > 1 && E <= MAX_LR_CTX) {  // all blocks by the low-rank kernel: one launch walks the emulators
-        bool all = true;
-        int64_t pmax = 0;
-        for (int e = 0; e < E; ++e) {
-            all = all && lowrank_applies(ctxs[e]) && ctxs[e]->fuse_finalize && ctxs[e]->Wld == c0->Wld;
-            pmax = ctxs[e]->P > pmax ? ctxs[e]->P : pmax;
-        }
-        if (all) {
-            LrTable tab;
-            for (int e = 0; e < E; ++e) {
-                const gpb_ctx* c = ctxs[e];
-                tab.c[e] = LrCtx{c->mpart, c->spart, c->amp, c->noise, c->lr_R, c->lr_v0, c->notpd, c->lr_cperp, c->lr_logdet0,
-                                 (int)c->P, (int)((c->Np + KX_CHUNK - 1) / KX_CHUNK), (int)(c->Np / 64)};
-            }
-            tab.E = E;
-            // one workgroup per (walker tile, emulator) + the ordered sum, when the blocks' buffer is there (ensure_lr_blocks;
-            // option key 49 = 0: the one-launch walk — the A/B, and the bit-identity test)
-            double* blocks = (c0->lr_split && c0->lr_blocks && c0->lr_blocks_cap >= (int64_t)E * c0->Wld) ? c0->lr_blocks : nullptr;
-            const dim3 grid((unsigned)((W + 63) / 64), blocks ? (unsigned)E : 1u);
-#define GPB_LRM(PPV)                                                                                             \
-    hipLaunchKernelGGL(k_loglike_lowrank_multi<PPV>, grid, dim3(lr_threads<PPV>()), 0, c0->stream, tab, c0->Wld, W, ll_dev, cmpv, inside_const, blocks)
-            if (pmax <= 4) GPB_LRM(4); else if (pmax <= 8) GPB_LRM(8); else if (pmax <= 12) GPB_LRM(12); else GPB_LRM(16);
-#undef GPB_LRM
-            if (blocks)
-                hipLaunchKernelGGL(k_lowrank_sum, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, c0->stream, blocks, E, c0->Wld, W,
-                                   ll_dev, cmpv, inside_const);
-            if (hipGetLastError() != hipSuccess) { c0->err = "gpb: k_loglike_lowrank_multi launch failed"; return GPB_E_HIP; }
-            return 0;
-        }
-    }
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        const bool fused = loglike_fuses_finalize(c, W);
-        if ((!fused && (rc = launch_finalize(c, W, true))) ||
-            (rc = launch_loglike(c, W, ll_dev, e > 0, fused, nullptr, nullptr, nullptr, outside,
-                                 e == E - 1 ? inside_const : 0.0, cmpv))) {
-            c0->err = c->err;
-            return rc;
-        }
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" int gpb_chain_supported(gpb_ctx* const* ctxs, int E) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    for (int e = 0; e < E; ++e) {
-        const gpb_ctx* c = ctxs[e];
-        if (!c) return GPB_E_ARG;
-        if (!c->have_like || c->device != ctxs[0]->device || c->stream != ctxs[0]->stream ||
-            chain_ndim(c) != chain_ndim(ctxs[0]) || !compaction_applies(c) || chain_ndim(c) > MAX_CHAIN_NDIM ||
-            (c->pmap_d_in > 0 && c->pmap_d_out != c->d))
-            return 0;
-    }
-    return 1;
-}
-
-extern "C" int gpb_chain_logpost(gpb_ctx* const* ctxs, int E, const double* Xs_dev, int64_t W, double* ll_dev,
-                                 const double* lo_dev, const double* hi_dev, double outside_value, double inside_const) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    gpb_ctx* ctx = ctxs[0];
-    if (!Xs_dev || !ll_dev || !lo_dev || !hi_dev || W < 0) GPB_FAIL(GPB_E_ARG, "gpb_chain_logpost: null pointer or negative size");
-    int rc = chain_check(ctxs, E, "gpb_chain_logpost");
-    if (rc) return rc;
-    if (W == 0) return 0;
-    GPB_HIP(hipSetDevice(ctx->device));
-    return chain_rows(ctxs, E, Xs_dev, W, ll_dev, lo_dev, hi_dev, outside_value, inside_const);
-}
-
-namespace {
-// What gpb_chain_emcee_run decides before it enqueues anything: argument checks, the share of every batch this rank
-// evaluates, which of the step's kernels are fused, and every workspace it needs — all of which can fail on ONE rank only
-// (bad state, hipMalloc).  gpb_chain_emcee_prepare runs exactly this and nothing else, so that the ranks of a sharded run
-// can agree that all of them are ready BEFORE any of them enqueues a collective the others would wait in.
-struct EmceePlan {
-    int64_t nh = 0, d = 0, chunk = 0, r0 = 0;
-    int R = 1;
-    bool sim = false, plain = false, fused = false, premark = false, fuse_ap = false, balanced = false;
-    int pre = 0;
-};
-
-int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
-    gpb_ctx* ctx = ctxs[0];
-    if (nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30)) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: nwalkers must be even, 2 .. 2^30");
-    // one emulator without a parameter map may also run uncompacted (tune key 27 = 0, non-PCA modes): gpb_logpost's sequence
-    pl.plain = E == 1 && ctx->pmap_d_in == 0 && !compaction_applies(ctx);
-    int rc;
-    if (pl.plain) {
-        if (!ctx->have_like) GPB_FAIL(GPB_E_STATE, "gpb_emcee_run before gpb_like_set");
-    } else if ((rc = chain_check(ctxs, E, "gpb_chain_emcee_run"))) {
-        return rc;
-    }
-    GPB_HIP(hipSetDevice(ctx->device));
-    const int64_t nh = nwalkers / 2, d = chain_ndim(ctx);
-    int R = ctx->comm ? ctx->nranks : 1;
-    const int rank = ctx->comm ? ctx->rank : 0;
-    // measurement / test hook (tune keys 26, 32): behave like rank `sim_rank` of `sim_ranks` on a single GPU — evaluate
-    // that rank's nh / sim_ranks rows of every batch only (the other rows keep -inf: rejected) and still issue the collective
-    pl.sim = ctx->sim_ranks > 1 && R == 1;
-    if (pl.sim) R = ctx->sim_ranks;
-    if (nh % R) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: half the ensemble must divide evenly over the ranks");
-    if (pl.sim && ctx->sim_rank >= R) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: tune key 32 (simulated rank) must be below key 26 (ranks)");
-    pl.nh = nh; pl.d = d; pl.R = R;
-    pl.chunk = nh / R;
-    pl.r0 = (pl.sim ? ctx->sim_rank : rank) * pl.chunk;
-    const int64_t chunk = pl.chunk;
-    for (int e = 0; e < E; ++e)                        // all workspaces now: the loop holds pointers into them
-        if ((rc = ensure_wcap(ctxs[e], chunk))) { if (e) ctx->err = ctxs[e]->err; return rc; }
-    if (!pl.plain && (rc = ensure_lr_blocks(ctx, E))) return rc;
-    // proposal workspace: two sets of q[nh][d], factor[nh], lpq[nh] (the fused accept + proposal kernel reads one set and
-    // writes the other) and a second log-probability vector [nwalkers]
-    if (ctx->mc_cap < 2 * nh * (d + 3)) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->mc_ws) pool_free(ctx->mc_ws);
-        ctx->mc_ws = nullptr;
-        ctx->mc_cap = 0;
-        GPB_HIP(pool_malloc_t(&ctx->mc_ws, sizeof(double) * (size_t)(2 * nh * (d + 3))));
-        ctx->mc_cap = 2 * nh * (d + 3);
-    }
-    pl.fused = pl.plain && loglike_fuses_finalize(ctx, chunk);
-    // the gather kernel counts the flags in front of each of its workgroups itself: fine for a rank's rows of an
-    // ensemble, quadratic for very large batches, which keep the marking kernel with its per-workgroup counts
-    pl.premark = !pl.plain && ctx->premark && chunk <= 16384;
-    // ... premark 2 (default): the proposal kernel gathers the rows as well (slots from a counter that the accept kernel
-    // re-arms), no compaction kernel at all; 1: flags only, k_compact_gather follows
-    pl.pre = pl.premark ? (ctx->premark >= 2 ? 2 : 1) : 0;
-    // ... and with that, tune key 30 (default on): the accept of a half-step and the proposal of the next are one launch
-    pl.fuse_ap = pl.pre == 2 && ctx->fuse_accept_propose;
-    // sharded (or playing one rank of several): equal slices of the ordered list of ALL live rows instead of the live rows
-    // of a contiguous share (k_balance_gather; tune key 36)
-    // Worth its extra launch (k_balance_gather + the rank look-ups of the accept step: +11 us per half-step, measured) only
-    // where the ranks' live counts straddle a walker-tile boundary often: 256 proposals per rank hold 120 +- 8 live rows, so
-    // at 8 ranks three half-steps in four have a rank with a fifth 64x32 tile (+23 us, measured per tile); at 2 and 4 ranks
-    // the contiguous shares rarely differ by a tile.  0 = never (default), 1 = from 8 ranks on, 2 = always.
-    pl.balanced = pl.pre == 2 && R > 1 && nh <= 16384 &&
-                  (ctx->balance_shards == 2 || (ctx->balance_shards == 1 && R >= 8));
-    if (pl.balanced) {
-        const int64_t need = 4 * nh + 2 * (4 + chunk) + 16;
-        if (ctx->bal_cap < need) {
-            GPB_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->bal_ws) pool_free(ctx->bal_ws);
-            ctx->bal_ws = nullptr;
-            ctx->bal_cap = 0;
-            GPB_HIP(pool_malloc_t(&ctx->bal_ws, sizeof(int) * (size_t)need));
-            ctx->bal_cap = need;
-        }
-    }
-    if (pl.pre && (rc = ensure_cmp_rows(ctx, d))) return rc;
-    return 0;
-}
-}  // namespace
-
-extern "C" int gpb_chain_emcee_prepare(gpb_ctx* const* ctxs, int E, int64_t nwalkers) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    EmceePlan pl;
-    return emcee_plan(ctxs, E, nwalkers, pl);
-}
-
-extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev, double* lp_dev, int64_t nwalkers,
-                                   int64_t nsteps, uint64_t seed, uint64_t step0, double a, int randomize_split,
-                                   const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
-                                   double* chain_dev, double* lpchain_dev, int64_t* naccept_dev) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    gpb_ctx* ctx = ctxs[0];
-    if (!pos_dev || !lp_dev || !lo_dev || !hi_dev || nsteps < 0) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: null pointer or negative size");
-    EmceePlan pl;
-    int rc = emcee_plan(ctxs, E, nwalkers, pl);
-    if (rc) return rc;
-    const int64_t nh = pl.nh, d = pl.d, chunk = pl.chunk, r0 = pl.r0;
-    const int R = pl.R, pre = pl.pre;
-    const bool sim = pl.sim, plain = pl.plain, fused = pl.fused, premark = pl.premark, fuse_ap = pl.fuse_ap,
-               balanced = pl.balanced;
-    double* qs[2] = {ctx->mc_ws, ctx->mc_ws + nh * (d + 2)};
-    double* factors[2] = {qs[0] + nh * d, qs[1] + nh * d};
-    double* lpqs[2] = {factors[0] + nh, factors[1] + nh};
-    double* lp2 = ctx->mc_ws + 2 * nh * (d + 2);
-    const int hb = half_bits(nwalkers), rnd = randomize_split ? 1 : 0;
-    const dim3 g32((unsigned)((nh * 32 + 255) / 256));
-    int *bal_flags[2] = {nullptr, nullptr}, *bal_rank[2] = {nullptr, nullptr}, *bal_cmp[2] = {nullptr, nullptr},
-        *bal_meta[2] = {nullptr, nullptr};
-    if (balanced) {
-        const int64_t need = 4 * nh + 2 * (4 + chunk) + 16;
-        GPB_HIP(hipMemsetAsync(ctx->bal_ws, 0, sizeof(int) * (size_t)need, ctx->stream));
-        for (int b = 0; b < 2; ++b) {
-            bal_flags[b] = ctx->bal_ws + b * nh;
-            bal_rank[b] = ctx->bal_ws + 2 * nh + b * nh;
-            bal_cmp[b] = ctx->bal_ws + 4 * nh + b * (4 + chunk);
-            bal_meta[b] = ctx->bal_ws + 4 * nh + 2 * (4 + chunk) + 4 * b;
-        }
-    }
-    if (pre) GPB_HIP(hipMemsetAsync(ctx->cmp_idx, 0, 2 * sizeof(int), ctx->stream));
-    if (sim) hipLaunchKernelGGL(k_fill, dim3((unsigned)((2 * nh * (d + 2) + 255) / 256)), dim3(256), 0, ctx->stream, ctx->mc_ws,
-                                2 * nh * (d + 2), -INFINITY);
-    unsigned long long* const live = pre == 2 && ctx->profile ? ctx->rows_live : (unsigned long long*)nullptr;
-    double* lp_cur = lp_dev;                           // fuse_ap: lp alternates between the caller's vector and lp2
-    double* lp_alt = lp2;
-    const int64_t nhalfsteps = 2 * nsteps;
-    for (int64_t g = 0; g < nhalfsteps; ++g) {
-        const int64_t n = g >> 1;
-        const int half = (int)(g & 1), b = fuse_ap ? (int)(g & 1) : 0;
-        const uint32_t step = (uint32_t)(step0 + (uint64_t)n);
-        double *q = qs[b], *factor = factors[b], *lpq = lpqs[b];
-        // the counter + index list of this batch's rows inside the box: two views one int apart, so that the fused kernel
-        // can re-arm the finished batch's counter while it fills the next one's
-        int* cmpv = balanced ? bal_cmp[b] : (ctx->cmp_idx ? ctx->cmp_idx + b : nullptr);
-        if (!fuse_ap || g == 0) {
-            if (balanced)      // flags of every row; k_balance_gather ranks them and takes this rank's slice
-                hipLaunchKernelGGL(k_propose, g32, dim3(256), 0, ctx->stream, pos_dev, nh, (int)d, half, seed, step, a, q,
-                                   factor, hb, rnd, lo_dev, hi_dev, outside_value, (double*)nullptr, bal_flags[b], (int64_t)0,
-                                   nh, (double*)nullptr, (int*)nullptr);
-            else if (premark)  // the proposal kernel also takes the prior-box test of this rank's rows
-                hipLaunchKernelGGL(k_propose, g32, dim3(256), 0, ctx->stream, pos_dev, nh, (int)d, half, seed, step, a, q,
-                                   factor, hb, rnd, lo_dev, hi_dev, outside_value, lpq,
-                                   pre == 1 ? ctx->cmp_idx + 4 + ctx->Wcap : (int*)nullptr, r0, chunk,
-                                   pre == 2 ? ctx->cmp_X : (double*)nullptr, pre == 2 ? cmpv : (int*)nullptr);
-            else
-                hipLaunchKernelGGL(k_propose, g32, dim3(256), 0, ctx->stream, pos_dev, nh, (int)d, half, seed, step, a, q,
-                                   factor, hb, rnd, (const double*)nullptr, (const double*)nullptr, 0.0, (double*)nullptr,
-                                   (int*)nullptr, (int64_t)0, (int64_t)0, (double*)nullptr, (int*)nullptr);
-        }
-        if (balanced)
-            hipLaunchKernelGGL(k_balance_gather, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, ctx->stream, q, nh, (int)d,
-                               bal_flags[b], bal_rank[b], R, (int)(r0 / chunk), ctx->cmp_X, cmpv, bal_meta[b]);
-        // this rank's rows of the batch: [compaction to the rows inside the box,] per emulator K*^T + mean partials,
-        // V = L^-1 K*^T with the fused sum of squares, block log-likelihood (+ prior box + constant)
-        if (plain) {
-            if ((rc = launch_predict(ctx, q + r0 * d, chunk, true, !fused))) return rc;
-            if ((rc = launch_loglike(ctx, chunk, lpq + r0, false, fused, q + r0 * d, lo_dev, hi_dev, outside_value,
-                                     inside_const)))
-                return rc;
-        } else if ((rc = chain_rows(ctxs, E, q + r0 * d, chunk, lpq + r0, lo_dev, hi_dev, outside_value, inside_const, pre,
-                                    cmpv))) {
-            return rc;
-        }
-        if (sim ? ctx->comm != nullptr : R > 1)                      // in place, on this stream
-            if ((rc = gpb_dist_allgather(ctx, lpq + r0, lpq, chunk))) return rc;
-        if (fuse_ap && g + 1 < nhalfsteps) {
-            const int64_t g1 = g + 1;
-            hipLaunchKernelGGL(k_accept_propose, g32, dim3(256), 0, ctx->stream, pos_dev, lp_cur, lp_alt, nh, (int)d, seed, hb,
-                               rnd, half, step, q, factor, lpq, reinterpret_cast<long long*>(naccept_dev),
-                               reinterpret_cast<long long*>(ctx->n_nan), cmpv, ctx->live_hint, chunk, live,
-                               (int)(g1 & 1), (uint32_t)(step0 + (uint64_t)(g1 >> 1)), a, qs[1 - b], factors[1 - b], lo_dev,
-                               hi_dev, outside_value, lpqs[1 - b], r0, chunk, ctx->cmp_X,
-                               balanced ? bal_cmp[1 - b] : ctx->cmp_idx + (1 - b), (const int*)bal_rank[b],
-                               (const int*)bal_meta[b], chunk, bal_flags[1 - b]);
-            double* sw = lp_cur; lp_cur = lp_alt; lp_alt = sw;
-        } else {
-            hipLaunchKernelGGL(k_accept, g32, dim3(256), 0, ctx->stream, pos_dev, lp_cur, nh, (int)d, half, seed, step, q,
-                               factor, lpq, reinterpret_cast<long long*>(naccept_dev), hb, rnd,
-                               reinterpret_cast<long long*>(ctx->n_nan), pre == 2 ? cmpv : (int*)nullptr,
-                               pre == 2 ? ctx->live_hint : (unsigned long long*)nullptr, chunk, live,
-                               (const int*)bal_rank[b], (const int*)bal_meta[b], chunk, outside_value);
-        }
-        if (half == 1 && (chain_dev || lpchain_dev))
-            hipLaunchKernelGGL(k_store_step, dim3((unsigned)((nwalkers * d + 255) / 256)), dim3(256), 0, ctx->stream, pos_dev,
-                               lp_cur, chain_dev ? chain_dev + n * nwalkers * d : nullptr,
-                               lpchain_dev ? lpchain_dev + n * nwalkers : nullptr, nwalkers, (int)d);
-    }
-    if (lp_cur != lp_dev)
-        GPB_HIP(hipMemcpyAsync(lp_dev, lp_cur, sizeof(double) * (size_t)nwalkers, hipMemcpyDeviceToDevice, ctx->stream));
-    GPB_HIP(hipGetLastError());
-    return 0;
-}
-
-
-extern "C" int gpb_emcee_run(gpb_ctx* ctx, double* pos_dev, double* lp_dev, int64_t nwalkers, int64_t nsteps,
-                             uint64_t seed, uint64_t step0, double a, int randomize_split, const double* lo_dev,
-                             const double* hi_dev, double outside_value, double inside_const, double* chain_dev,
-                             double* lpchain_dev, int64_t* naccept_dev) {
-    if (!ctx) return GPB_E_ARG;
-    if (ctx->pmap_d_in > 0 && !compaction_applies(ctx))
-        GPB_FAIL(GPB_E_STATE, "gpb_emcee_run: an emulator with a parameter map needs the block likelihood kernels");
-    gpb_ctx* one[1] = {ctx};
-    return gpb_chain_emcee_run(one, 1, pos_dev, lp_dev, nwalkers, nsteps, seed, step0, a, randomize_split, lo_dev, hi_dev,
-                               outside_value, inside_const, chain_dev, lpchain_dev, naccept_dev);
-}
-
-#ifdef GPB_DEBUG_VARIANTS      // test hooks (include/gpbayes_debug.h)
-extern "C" int gpb_test_split_perm(gpb_ctx* ctx, int64_t n, uint64_t seed, uint64_t step, int64_t* out_dev) {
-    if (!ctx || n < 2 || n > (1ll << 30) || !out_dev) return GPB_E_ARG;
-    hipLaunchKernelGGL(k_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<long long*>(out_dev), n, seed, (uint32_t)step, half_bits(n));
-    GPB_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int gpb_test_philox(gpb_ctx* ctx, int64_t n, const uint32_t* in_host, uint32_t* out_host) {
-    if (!ctx || n < 1 || n > (1 << 20) || !in_host || !out_host) return GPB_E_ARG;
-    GPB_HIP(hipSetDevice(ctx->device));
-    uint32_t *din = nullptr, *dout = nullptr;
-    GPB_HIP(hipMalloc(&din, sizeof(uint32_t) * 6 * n));
-    GPB_HIP(hipMalloc(&dout, sizeof(uint32_t) * 4 * n));
-    GPB_HIP(hipMemcpy(din, in_host, sizeof(uint32_t) * 6 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_philox_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, din, dout, n);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(out_host, dout, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost);
-    (void)hipFree(din); (void)hipFree(dout);
-    GPB_HIP(e);
-    return 0;
-}
-
-extern "C" int gpb_test_stretch_draws(gpb_ctx* ctx, int64_t nwalkers, int half, uint64_t seed, uint64_t step,
-                                      int randomize_split, double* u_z_dev, int64_t* j_dev, double* u_acc_dev,
-                                      int64_t* perm_dev) {
-    if (!ctx || nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30) || (half != 0 && half != 1) || !u_z_dev ||
-        !j_dev || !u_acc_dev || !perm_dev)
-        return GPB_E_ARG;
-    hipLaunchKernelGGL(k_stretch_draws, dim3((unsigned)((nwalkers + 255) / 256)), dim3(256), 0, ctx->stream,
-                       nwalkers / 2, half, seed, (uint32_t)step, half_bits(nwalkers), randomize_split ? 1 : 0, u_z_dev,
-                       reinterpret_cast<long long*>(j_dev), u_acc_dev, reinterpret_cast<long long*>(perm_dev));
-    GPB_HIP(hipGetLastError());
-    return 0;
-}
-#endif  // GPB_DEBUG_VARIANTS

@@ -389,15 +389,7 @@ int smc_check(gpb_ctx* const* ctxs, int E, int64_t N, const char* who, int64_t& 
 // reweighting, the proposals of a move step); cov [nd, nd]; mean [nd]; the mapped parameters of the per-emulator sequence
 int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd, int64_t nxg) {
     const int64_t need = 3 * N + N * nd + nd * nd + nd + nxg;
-    if (ctx->smc_cap < need) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->smc_ws) pool_free(ctx->smc_ws);
-        ctx->smc_ws = nullptr;
-        ctx->smc_cap = 0;
-        GPB_HIP(pool_malloc_t(&ctx->smc_ws, sizeof(double) * (size_t)need));
-        ctx->smc_cap = need;
-    }
-    return 0;
+    return pool_grow(ctx, &ctx->smc_ws, &ctx->smc_cap, need);
 }
 }  // namespace
 }  // namespace gpb
