@@ -141,7 +141,7 @@ extern "C" int gpb_ctx_destroy(gpb_ctx* ctx) {
     dev_free(&ctx->alpha); dev_free(&ctx->apart); dev_free(&ctx->info); dev_free(&ctx->lmlbuf);
     dev_free(&ctx->gpart); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->KsT); dev_free(&ctx->mpart);
     dev_free(&ctx->spart); dev_free(&ctx->mean_pc); dev_free(&ctx->var_pc); dev_free(&ctx->out_stage);
-    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
+    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->sobol_ws); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
     dev_free(&ctx->tile_trace);
     dev_free(&ctx->A); dev_free(&ctx->mu); dev_free(&ctx->scale); dev_free(&ctx->C0); dev_free(&ctx->yexp);
     dev_free(&ctx->Cexp); dev_free(&ctx->mvn_ws); dev_free(&ctx->notpd); dev_free(&ctx->tile_counter);
@@ -786,6 +786,68 @@ extern "C" int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, 
     if ((rc = launch_obs(ctx, W, nullptr, dm, dc))) return rc;
     GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * M, hipMemcpyDeviceToHost, ctx->stream));
     if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * W * M * M, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- closed-form Sobol indices (gpb_sobol.hip)
+// results are formed in the Sobol workspace behind the tables and tile partials; host callers get them copied from there
+extern "C" int gpb_gp_sobol(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int on_device, double* e, double* H) {
+    if (!ctx || !e || !H) return GPB_E_ARG;
+    int rc = sobol_plan(ctx, "gpb_gp_sobol", lo_host, hi_host, false, -1);     // (checks first: the sizes below are the context's)
+    if (rc) return rc;
+    const int64_t P = ctx->P, nH = P * P * (2 * ctx->d + 1), np = sobol_part_doubles(ctx);
+    if ((rc = sobol_plan(ctx, "gpb_gp_sobol", lo_host, hi_host, false, np + P + nH))) return rc;
+    if (on_device) return launch_sobol(ctx, e, H);
+    double* de = ctx->sobol_ws + sobol_tab_doubles(ctx) + np;
+    double* dH = de + P;
+    if ((rc = launch_sobol(ctx, de, dH))) return rc;
+    GPB_HIP(hipMemcpyAsync(e, de, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipMemcpyAsync(H, dH, sizeof(double) * nH, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int gpb_emu_sobol(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int on_device, double* mean, double* var,
+                             double* first, double* total) {
+    if (!ctx || !mean || !var || !first || !total) return GPB_E_ARG;
+    int rc = sobol_plan(ctx, "gpb_emu_sobol", lo_host, hi_host, true, -1);
+    if (rc) return rc;
+    const int64_t P = ctx->P, M = ctx->M, d = ctx->d, nH = P * P * (2 * d + 1), np = sobol_part_doubles(ctx);
+    if ((rc = sobol_plan(ctx, "gpb_emu_sobol", lo_host, hi_host, true, np + P + nH + 2 * M + 2 * M * d))) return rc;
+    double* de = ctx->sobol_ws + sobol_tab_doubles(ctx) + np;
+    double* dH = de + P;
+    if ((rc = launch_sobol(ctx, de, dH))) return rc;
+    if (on_device) return launch_sobol_obs(ctx, de, dH, mean, var, first, total);
+    double* dm = dH + nH;
+    double* dv = dm + M;
+    double* df = dv + M;
+    double* dt = df + M * d;
+    if ((rc = launch_sobol_obs(ctx, de, dH, dm, dv, df, dt))) return rc;
+    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipMemcpyAsync(var, dv, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipMemcpyAsync(first, df, sizeof(double) * M * d, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipMemcpyAsync(total, dt, sizeof(double) * M * d, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int64_t j, const double* t, int64_t G,
+                                   int on_device, double* curve) {
+    if (!ctx || !t || !curve) return GPB_E_ARG;
+    int rc = sobol_plan(ctx, "gpb_emu_main_effect", lo_host, hi_host, true, -1);
+    if (rc) return rc;
+    if (j < 0 || j >= ctx->d) GPB_FAIL(GPB_E_ARG, "gpb_emu_main_effect: parameter index outside [0, d)");
+    if (G < 1 || G > (int64_t)1 << 24) GPB_FAIL(GPB_E_ARG, "gpb_emu_main_effect: need 1 <= G <= 2^24 grid points");
+    const int64_t P = ctx->P, M = ctx->M;
+    if ((rc = sobol_plan(ctx, "gpb_emu_main_effect", lo_host, hi_host, true, G * P + G + G * M))) return rc;
+    double* zbuf = ctx->sobol_ws + sobol_tab_doubles(ctx);
+    if (on_device) return launch_sobol_main_effect(ctx, j, t, G, zbuf, curve);
+    double* dt = zbuf + G * P;
+    double* dc = dt + G;
+    GPB_HIP(hipMemcpyAsync(dt, t, sizeof(double) * G, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_sobol_main_effect(ctx, j, dt, G, zbuf, dc))) return rc;
+    GPB_HIP(hipMemcpyAsync(curve, dc, sizeof(double) * G * M, hipMemcpyDeviceToHost, ctx->stream));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -146,6 +146,11 @@ struct gpb_ctx {
     std::vector<int> h_cv;
     int64_t cv_n = 0, cv_nf = 0, cv_kmax = 0, cv_ints = 0;
     bool cv_loo = false, cv_has_idx = false;
+    // Sobol indices (gpb_sobol.hip): I | E tables [P][N][dpad] each, e partials [P][Np/64], then what the call needs (tile
+    // partials, staged results); the box of the planned call, lo [d] | hi [d]
+    double* sobol_ws = nullptr;
+    int64_t sobol_cap = 0;         // doubles
+    std::vector<double> h_sobol_box;
 
     // ---- emulator transform / likelihood ----------------------------------------
     int mode = 0;
@@ -310,6 +315,15 @@ int launch_vmat(gpb_ctx* ctx);     // gpb_cov.hip: vbuf = L^-1 K*^T of the curre
 // the fold covariance blocks [P][nf][kmax][kmax]
 int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, const int32_t* fold_ptr, int64_t nf, int64_t* kmax);
 int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64_t si, double* cov_dev);
+// closed-form Sobol indices (gpb_sobol.hip): sobol_plan checks state and box (GPB_E_STATE / GPB_E_ARG), keeps the box and sizes
+// ctx->sobol_ws for the tables plus `extra` doubles, which start at sobol_ws + sobol_tab_doubles; launch_sobol needs
+// sobol_part_doubles of them in front for its tile partials
+int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi, bool need_transform, int64_t extra);
+int64_t sobol_tab_doubles(const gpb_ctx* ctx);
+int64_t sobol_part_doubles(const gpb_ctx* ctx);
+int launch_sobol(gpb_ctx* ctx, double* e_dev, double* H_dev);
+int launch_sobol_obs(gpb_ctx* ctx, const double* e_dev, const double* H_dev, double* mean, double* var, double* first, double* total);
+int launch_sobol_main_effect(gpb_ctx* ctx, int64_t j, const double* t_dev, int64_t G, double* zbuf_dev, double* curve_dev);
 // likelihood (gpb_like.hip)
 int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev, double* cov_dev);
 // true when launch_loglike will take the block log-likelihood kernels that sum the partials themselves

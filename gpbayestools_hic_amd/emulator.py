@@ -45,6 +45,20 @@ def _check_random_state(seed):
     raise ValueError("%r cannot be used to seed a numpy.random.RandomState instance" % seed)
 
 
+class SobolIndices:
+    """Sobol decomposition of an emulator's posterior mean over a uniform box (Emulator.sobol_indices, Chain.sobol_indices):
+    mean [nobs] and variance [nobs] of every observable over the box, first_order [nobs, ndim] (the share of the variance
+    parameter j explains alone) and total [nobs, ndim] (its share with every interaction it takes part in); names: the
+    parameters' names where a parameter file gave them."""
+
+    def __init__(self, mean, variance, first_order, total, names=None):
+        self.mean, self.variance, self.first_order, self.total = mean, variance, first_order, total
+        self.names = None if names is None else list(names)
+
+    def __repr__(self):
+        return "SobolIndices(nobs=%d, ndim=%d)" % self.first_order.shape
+
+
 class FittedKernel:
     """`gp.kernel_` of a fitted GP: the sklearn composite `c * RBF|Matern(length_scale) + WhiteKernel(noise_level)`
     the reference builds (src/emulator.py:286-306), as a read-only view with the attributes and the printed form
@@ -689,6 +703,58 @@ class Emulator:
         for i0 in range(0, W, slab):
             out[i0:i0 + slab] = eng.emu_predict_jac(np.ascontiguousarray(X[i0:i0 + slab]))
         return out
+
+    def _sobol_engine(self, what, bounds, log_observable):
+        """the engine and the box (lo, hi) of a closed-form sensitivity call, or the reason there is no closed form"""
+        if self.parameterTrafoPCA_:
+            raise NotImplementedError("%s: a parameterTrafoPCA emulator's GPs see principal components of the parameters; the map "
+                                      "is not linear, a uniform box in the parameters is no box in the GP inputs" % what)
+        if not self._trained:
+            raise RuntimeError("Emulator is not trained")
+        if self.kernel_type_ != "RBF":
+            raise NotImplementedError("%s: the closed form needs a kernel that is a product over the input dimensions (RBF); the "
+                                      "%s kernel is a function of the full scaled distance and would need quadrature"
+                                      % (what, self.kernel_type_))
+        if self.exp_and_cov_diagonal_ and not log_observable:
+            raise ValueError("%s: with exp_and_cov_diagonal the emulator predicts exp(linear in the GPs); the closed form "
+                             "decomposes the log-observable, in front of the exp.  Pass log_observable=True to get that." % what)
+        eng = self._engine_ready()
+        if bounds is None:
+            lo, hi = self.design_min, self.design_max
+        else:
+            lo, hi = np.asarray(bounds, dtype=np.float64).reshape(-1, 2).T
+        return eng, np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+
+    def sobol_indices(self, bounds=None, log_observable=False):
+        """Global sensitivity of the emulator's posterior mean over a uniform box, in closed form on the device (gpb_emu_sobol):
+        which parameters drive which observable over the whole prior, alone (first-order index) and with interactions (total
+        index).  The global counterpart of predict_jacobian, which is the local response at one point.  No sampling: for the RBF
+        kernel every integral of the mean over a subset of the inputs is a sum of products of error functions.
+
+        bounds: [ndim, 2] (lower, upper) per parameter; None = design_min / design_max.  Returns a SobolIndices with mean,
+        variance [nobs], first_order, total [nobs, ndim].  With exp_and_cov_diagonal the decomposition is of the log-observable
+        (what is linear in the GPs): ValueError unless log_observable=True says the caller knows.  NotImplementedError for
+        Matern kernels and parameterTrafoPCA emulators (no closed form)."""
+        eng, lo, hi = self._sobol_engine("sobol_indices", bounds, log_observable)
+        mean, var, first, total = eng.emu_sobol(lo, hi)
+        names = list(self.pardict) if getattr(self, "pardict", None) else None
+        return SobolIndices(mean, var, first, total, names)
+
+    def main_effect(self, param, grid=None, bounds=None, log_observable=False):
+        """Main-effect curve of one parameter: the posterior mean averaged over all the others, E[f | x_param = t], in closed
+        form on the device (gpb_emu_main_effect).  param: an index or a name of pardict; grid: the values t (None: 101 points
+        across the parameter's bounds); bounds as in sobol_indices.  Returns (grid [G], curve [G, nobs])."""
+        eng, lo, hi = self._sobol_engine("main_effect", bounds, log_observable)
+        if isinstance(param, str):
+            names = list(self.pardict) if getattr(self, "pardict", None) else []
+            if param not in names:
+                raise ValueError("main_effect: no parameter named %r" % param)
+            param = names.index(param)
+        j = int(param)
+        if j < 0 or j >= lo.shape[0]:
+            raise ValueError("main_effect: parameter index %d outside [0, %d)" % (j, lo.shape[0]))
+        grid = np.linspace(lo[j], hi[j], 101) if grid is None else np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
+        return grid, eng.emu_main_effect(lo, hi, j, grid)
 
     def sample_y(self, X, n_samples=1, random_state=None):
         """Sample model output at X -> [n_samples_X, n_samples, nobs] (src/emulator.py:608-633): one

@@ -363,6 +363,52 @@ class GPEngine:
         self._ck(self.lib.gpb_emu_cv(self.h, nat.ptr(idx), n, nat.ptr(fptr), nf, 0, nat.ptr(mean), nat.ptr(cov)))
         return (mean, cov) if return_cov else mean
 
+    # ------------------------------------------------------------------ closed-form Sobol indices
+    def _box(self, lo, hi):
+        self._need_data()
+        self._track_stream()
+        lo, hi = nat.f64(lo).reshape(-1), nat.f64(hi).reshape(-1)
+        if lo.shape[0] != self.d or hi.shape[0] != self.d:
+            raise ValueError("sobol: lo and hi need one entry per input dimension (%d)" % self.d)
+        return lo, hi
+
+    def sobol(self, lo, hi, on_device=False):
+        """Closed-form integrals of the GPs' posterior means over the uniform box [lo, hi] (gpb_gp_sobol, RBF only):
+        e [P] = E[m_p] and H [P, P, 2d + 1] = E[E[m_p | x_S] E[m_q | x_S]] for the subsets S = {j} (slot j), all but j (slot d + j)
+        and all (slot 2d).  numpy out, or with on_device torch tensors on the engine's device (asynchronous)."""
+        lo, hi = self._box(lo, hi)
+        shapes = ((self.P,), (self.P, self.P, 2 * self.d + 1))
+        if on_device:
+            import torch
+            e, H = (torch.empty(s, dtype=torch.float64, device=torch.device("cuda", self.device)) for s in shapes)
+        else:
+            e, H = (np.empty(s) for s in shapes)
+        self._ck(self.lib.gpb_gp_sobol(self.h, nat.ptr(lo), nat.ptr(hi), 1 if on_device else 0, nat.ptr(e), nat.ptr(H)))
+        return e, H
+
+    def emu_sobol(self, lo, hi, on_device=False):
+        """Sobol indices of the observables' posterior mean through the installed (linear) transform (gpb_emu_sobol): mean [M],
+        variance [M], first-order indices [M, d], total indices [M, d] over the uniform box [lo, hi]; of the log-observable in
+        the two exp modes.  numpy out, or with on_device torch tensors on the engine's device (asynchronous)."""
+        lo, hi = self._box(lo, hi)
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = [torch.empty(s, dtype=torch.float64, device=dev) for s in ((self.M,), (self.M,), (self.M, self.d), (self.M, self.d))]
+        else:
+            out = [np.empty(s) for s in ((self.M,), (self.M,), (self.M, self.d), (self.M, self.d))]
+        self._ck(self.lib.gpb_emu_sobol(self.h, nat.ptr(lo), nat.ptr(hi), 1 if on_device else 0, *[nat.ptr(o) for o in out]))
+        return tuple(out)
+
+    def emu_main_effect(self, lo, hi, j, t):
+        """Main-effect curve E[f_m | x_j = t] of the observables' posterior mean on the grid t [G] over the box [lo, hi]
+        (gpb_emu_main_effect): curve [G, M], numpy out."""
+        lo, hi = self._box(lo, hi)
+        t = nat.f64(t).reshape(-1)
+        curve = np.empty((t.shape[0], self.M))
+        self._ck(self.lib.gpb_emu_main_effect(self.h, nat.ptr(lo), nat.ptr(hi), int(j), nat.ptr(t), t.shape[0], 0, nat.ptr(curve)))
+        return curve
+
     # ------------------------------------------------------------------ emulator transform
     def set_transform(self, mode, mu, A=None, cov_trunc=None, scale=None):
         mu = nat.f64(mu)

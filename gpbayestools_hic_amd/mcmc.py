@@ -347,6 +347,19 @@ class Chain:
             lp[inside] += EXTRA_STD_CONST
         return lp
 
+    def sobol_indices(self, log_observable=False):
+        """Sobol indices of every emulator of emuList over the chain's prior box (Emulator.sobol_indices with bounds = the
+        chain's min / max), concatenated along the observables in emuList order: a SobolIndices with mean, variance [nobs],
+        first_order, total [nobs, ndim].  NotImplementedError for foreign emulators (and what Emulator.sobol_indices refuses)."""
+        from .emulator import SobolIndices
+        if not self._native():
+            raise NotImplementedError("sobol_indices needs every emulator of the chain to be this package's Emulator (foreign "
+                                      "emulators expose no GP state to integrate)")
+        bounds = np.stack([self.min, self.max], axis=1)
+        parts = [e.sobol_indices(bounds, log_observable=log_observable) for e in self.emuList]
+        return SobolIndices(*[np.concatenate([getattr(r, k) for r in parts], axis=0)
+                              for k in ("mean", "variance", "first_order", "total")], names=list(self.pardict))
+
     grad_slab_rows = 1 << 14                     # most rows of one gradient evaluation (a row's numbers do not depend on it)
 
     def _log_prob_grad(self, X, outside):

@@ -186,6 +186,40 @@ GPB_API int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host /*[n_idx] or NULL*/
                const int32_t* fold_ptr_host /*[nf+1] or NULL*/, int64_t nf, int on_device,
                double* mean /*[n_idx,M]*/, double* cov /*[n_idx,M,M] or NULL*/);
 
+/* ---- closed-form Sobol sensitivity indices of the posterior mean over a uniform prior box --------------------------- *
+ * The global counterpart of gpb_emu_predict_jac (the reference's SensitivityAnalysis notebook is local: 2 d finite differences
+ * at one point).  The RBF kernel is a product over the input dimensions and the prior a box [lo, hi] (widths w = hi - lo), so every
+ * integral of the posterior mean over a subset of the inputs is a finite sum of products of error functions (Oakley & O'Hagan
+ * 2004); nothing is sampled.  GP p has the mean m_p(x) = c_p sum_i alpha_pi prod_l exp(-(x_l - x_il)^2 / 2 l_pl^2); with a = x_il,
+ * b = x_i'l, l = l_pl, l' = l_ql, s = 1/l^2 + 1/l'^2, c = (a/l^2 + b/l'^2) / s:
+ *   I^p_l(a)     = l sqrt(pi/2) / w_l [erf((hi_l - a) / (sqrt2 l)) - erf((lo_l - a) / (sqrt2 l))]
+ *   Q^pq_l(a, b) = exp(-(a - b)^2 / 2(l^2 + l'^2)) sqrt(pi / 2s) / w_l [erf((hi_l - c) sqrt(s/2)) - erf((lo_l - c) sqrt(s/2))]
+ *   e_p    = c_p sum_i alpha_pi prod_l I^p_l(x_il)                                                  = E[m_p]
+ *   H^pq_S = c_p c_q sum_ii' alpha_pi alpha_qi' prod_{l in S} Q^pq_l(x_il, x_i'l) prod_{l not in S} I^p_l(x_il) I^q_l(x_i'l)
+ *                                                                                                   = E[E[m_p | x_S] E[m_q | x_S]]
+ * gpb_gp_sobol: e [P] and H [P, P, 2d + 1] for the subsets {j} (slot j), all \ {j} (slot d + j) and all (slot 2d); H[p][q] ==
+ *   H[q][p] bit for bit, both filled.  A (p, q) block's bits do not depend on the other GPs of the context (no atomics, every sum
+ *   in a fixed order that depends on the padded design size alone).
+ * gpb_emu_sobol: through the linear observable transform f_m = mu_m + sum_p A_pm m_p (PCA modes: the transform's A; no-PCA modes:
+ *   scale_m on GP m alone): mean [M] = mu_m + sum_p A_pm e_p, var [M] = V_all, first [M, d] = V_{j} / V, total [M, d] =
+ *   1 - V_{all \ j} / V with V_S(m) = sum_pq A_pm A_qm (H^pq_S - e_p e_q).  In the two EXPDIAG modes these describe the
+ *   log-observable (the transform in front of the exp), which is what is linear in the GPs.
+ * gpb_emu_main_effect: curve [G, M] = E[f_m | x_j = t_g] = mu_m + sum_p A_pm c_p sum_i alpha_pi exp(-(t_g - x_ij)^2 / 2 l_pj^2)
+ *   prod_{l != j} I^p_l(x_il) on the grid t [G] (same convention for the EXPDIAG modes).
+ * lo_host / hi_host [d] are host arrays; on_device says where the outputs (and t) live (0: host, the call synchronises; 1: device
+ * memory, asynchronous).  Only the N design points are visited.  Length scales far below the box width make Q factors underflow to
+ * zero; the products are formed without quotients, so such terms are 0, never NaN.
+ * Errors: GPB_E_STATE without a factorisation, on a gpb_gp_set_multi context and (the gpb_emu_ calls) without a transform;
+ * GPB_E_ARG for a Matern kernel (a function of the full scaled distance, not a product over dimensions: no closed form), for a
+ * context with a parameter map (not linear in the original parameters), hi <= lo in any dimension, j outside [0, d), G < 1, more
+ * than 361 GPs or 16320 design points.  The factorisation, alpha and the predict workspace are untouched. */
+GPB_API int gpb_gp_sobol(gpb_ctx* ctx, const double* lo_host /*[d]*/, const double* hi_host /*[d]*/, int on_device,
+                 double* e /*[P]*/, double* H /*[P,P,2d+1]*/);
+GPB_API int gpb_emu_sobol(gpb_ctx* ctx, const double* lo_host /*[d]*/, const double* hi_host /*[d]*/, int on_device,
+                  double* mean /*[M]*/, double* var /*[M]*/, double* first /*[M,d]*/, double* total /*[M,d]*/);
+GPB_API int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host /*[d]*/, const double* hi_host /*[d]*/, int64_t j,
+                        const double* t /*[G]*/, int64_t G, int on_device, double* curve /*[G,M]*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
