@@ -8,14 +8,14 @@ src/mcmc.py log-posterior loop): hand-written HIP kernels for gfx950 behind a C 
 __version__ = "0.1.0"
 
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
-           "WalkerSharding", "rms_relative_error", "honesty"]
+           "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
     if name == "Emulator":
         from .emulator import Emulator
         return Emulator
-    if name in ("rms_relative_error", "honesty"):
+    if name in ("rms_relative_error", "honesty", "DesignProposal"):
         from . import emulator
         return getattr(emulator, name)
     if name in ("Chain", "mvn_loglike"):

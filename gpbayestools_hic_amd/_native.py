@@ -56,6 +56,9 @@ BOUNDARY = {
     "gpb_gp_sobol": (C.c_int, [VP, VP, VP, C.c_int, VP, VP]),
     "gpb_emu_sobol": (C.c_int, [VP, VP, VP, C.c_int, VP, VP, VP, VP]),
     "gpb_emu_main_effect": (C.c_int, [VP, VP, VP, c_i64, VP, c_i64, C.c_int, VP]),
+    "gpb_design_begin": (C.c_int, [VP, VP, c_i64, VP, c_i64, VP, VP]),
+    "gpb_chain_design_run": (C.c_int, [VP, C.c_int, c_i64, VP, VP, VP, VP]),
+    "gpb_design_end": (C.c_int, [VP]),
     "gpb_like_set": (C.c_int, [VP, VP, VP]),
     "gpb_loglike": (C.c_int, [VP, VP, c_i64, C.c_int, VP, C.c_int, VP]),
     "gpb_logpost": (C.c_int, [VP, VP, c_i64, VP, C.c_int, VP, VP, C.c_double, C.c_double]),

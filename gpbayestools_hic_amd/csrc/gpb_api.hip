@@ -141,7 +141,7 @@ extern "C" int gpb_ctx_destroy(gpb_ctx* ctx) {
     dev_free(&ctx->alpha); dev_free(&ctx->apart); dev_free(&ctx->info); dev_free(&ctx->lmlbuf);
     dev_free(&ctx->gpart); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->KsT); dev_free(&ctx->mpart);
     dev_free(&ctx->spart); dev_free(&ctx->mean_pc); dev_free(&ctx->var_pc); dev_free(&ctx->out_stage);
-    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->sobol_ws); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
+    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->sobol_ws); dev_free(&ctx->design_ws); dev_free(&ctx->design_run); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
     dev_free(&ctx->tile_trace);
     dev_free(&ctx->A); dev_free(&ctx->mu); dev_free(&ctx->scale); dev_free(&ctx->C0); dev_free(&ctx->yexp);
     dev_free(&ctx->Cexp); dev_free(&ctx->mvn_ws); dev_free(&ctx->notpd); dev_free(&ctx->tile_counter);
@@ -191,7 +191,7 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     ctx->N = N; ctx->d = d; ctx->P = ctx->Pstore = P; ctx->dpad = dpad; ctx->kind = kernel_id; ctx->alpha_reg = alpha;
     ctx->multi = multi; ctx->subset = false;
     ctx->Np = round_up(N, NB);
-    ctx->have_theta = ctx->factored = false;
+    ctx->have_theta = ctx->factored = ctx->design_ready = false;
     // whatever was installed for the previous GPs (observable transform sized [old P][M], likelihood block, low-rank
     // factors, parameter map) does not describe the new ones: it has to be set again
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
@@ -378,7 +378,7 @@ extern "C" int gpb_gp_set_theta(gpb_ctx* ctx, const double* theta_host) {
     GPB_HIP(hipMemcpyAsync(ctx->thblk, ctx->h_thblk, ctx->thblk_bytes, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = launch_scale_design(ctx))) return rc;
     ctx->have_theta = true;
-    ctx->factored = false;
+    ctx->factored = ctx->design_ready = false;
     return 0;
 }
 
@@ -426,6 +426,7 @@ extern "C" int gpb_gp_factor(gpb_ctx* ctx, int* info_host) {
     if (rc < 0) return rc;
     // a failed GP leaves NaNs in L, L^-1 and alpha: the predict / likelihood entry points refuse to run on them
     ctx->factored = rc == 0;
+    ctx->design_ready = false;                         // (a design workspace describes the factorisation it was begun on)
     if (rc > 0) ctx->err = "gpb_gp_factor: kernel matrix not positive definite (see info); no factorisation installed";
     return rc;
 }
@@ -512,6 +513,7 @@ static int lml_impl(gpb_ctx* ctx, const double* theta_host, double* lml_host, do
         if (info_host) info_host[p] = info_unpadded(ctx, p, info[p]);
     }
     ctx->factored = true;
+    ctx->design_ready = false;
     for (int64_t p = 0; p < P; ++p) if (info[p] != 0) ctx->factored = false;     // see gpb_gp_factor
     return 0;
 }
@@ -542,7 +544,7 @@ extern "C" int gpb_gp_lml_subset(gpb_ctx* ctx, int64_t n, const int32_t* gp_inde
     ctx->P = ctx->Pstore;
     ctx->subset = false;
     // the workspaces hold the subset's factorisation in their first slots and theta is the subset's: nothing to predict from
-    ctx->have_theta = ctx->factored = false;
+    ctx->have_theta = ctx->factored = ctx->design_ready = false;
     return rc;
 }
 
@@ -1240,7 +1242,7 @@ extern "C" int gpb_profile_fit_piece(gpb_ctx* ctx, int piece) {
     if (!ctx) return GPB_E_ARG;
     if (!ctx->have_theta) GPB_FAIL(GPB_E_STATE, "gpb_profile_fit_piece before gpb_gp_set_theta");
     GPB_HIP(hipSetDevice(ctx->device));
-    ctx->factored = false;
+    ctx->factored = ctx->design_ready = false;
     switch (piece) {
         case 0: return launch_kmat(ctx);
         case 1: return launch_potrf(ctx);

@@ -9,19 +9,6 @@
 
 namespace gpb {
 
-template <int KIND>
-__device__ __forceinline__ double shape_fn_c(double r2) {
-    if (KIND == GPB_KERNEL_RBF) {
-        return exp(-0.5 * r2);
-    } else if (KIND == GPB_KERNEL_MATERN15) {
-        const double t = sqrt(r2) * 1.7320508075688772;
-        return (1.0 + t) * exp(-t);
-    } else {
-        const double t = sqrt(r2) * 2.23606797749979;
-        return (1.0 + t + t * t / 3.0) * exp(-t);
-    }
-}
-
 // V[p][n][w] = sum_{k<=n} Linv[p][n][k] KsT[p][k][w]   (materialised, unlike k_predict)
 __global__ __launch_bounds__(256, 2) void k_vmat(const double* __restrict__ Linv, const double* __restrict__ KsT,
                                                  double* __restrict__ V, int64_t Np, int64_t Wld) {
@@ -83,13 +70,17 @@ __global__ void k_cov_pack(const double* __restrict__ src, double* __restrict__ 
     if (j < W) dst[((int64_t)p * W + i) * W + j] = src[((int64_t)p * Wld + i) * Wld + j];
 }
 
-// vbuf[p] = V_p = L_p^-1 K*_p^T of the current batch (fp64 K*^T: the caller of launch_predict set want_kst), ld = ctx->Wld
-int launch_vmat(gpb_ctx* ctx) {
+// vbuf[p] (or the caller's dst[p]) = V_p = L_p^-1 K*_p^T of the current batch (fp64 K*^T: the caller of launch_predict set
+// want_kst), ld = ctx->Wld
+int launch_vmat(gpb_ctx* ctx, double* dst) {
     const int64_t P = ctx->P, Np = ctx->Np, Wld = ctx->Wld;
     const int64_t need_v = P * Np * Wld;
-    if (int rc = pool_grow(ctx, &ctx->vbuf, &ctx->vbuf_cap, need_v)) return rc;
+    if (!dst) {
+        if (int rc = pool_grow(ctx, &ctx->vbuf, &ctx->vbuf_cap, need_v)) return rc;
+        dst = ctx->vbuf;
+    }
     dim3 gv((unsigned)(Wld / 128), (unsigned)((Np + 127) / 128), (unsigned)P);
-    hipLaunchKernelGGL(k_vmat, gv, dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, ctx->vbuf, Np, Wld);
+    hipLaunchKernelGGL(k_vmat, gv, dim3(256), 0, ctx->stream, ctx->Linv, ctx->KsT, dst, Np, Wld);
     GPB_HIP(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 // gpb_internal.h — context layout and launch prototypes shared by the .hip files.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string>
 #include <utility>
@@ -37,6 +38,20 @@ struct GpSel {
 // FRONT in whole 16-row units — the predict tiles' K-step: those leading zero rows of K*^T are skipped outright and their rows of V
 // fall into the lightest row block — and the remainder (< 16 rows) behind.
 __host__ __device__ __forceinline__ int64_t pad_front(int64_t Np, int64_t N) { return ((Np - N) / 16) * 16; }
+
+// c k(r) / c as a function of the squared scaled distance, plain libm form (the joint covariance and the sequential design)
+template <int KIND>
+__device__ __forceinline__ double shape_fn_c(double r2) {
+    if (KIND == GPB_KERNEL_RBF) {
+        return exp(-0.5 * r2);
+    } else if (KIND == GPB_KERNEL_MATERN15) {
+        const double t = sqrt(r2) * 1.7320508075688772;
+        return (1.0 + t) * exp(-t);
+    } else {
+        const double t = sqrt(r2) * 2.23606797749979;
+        return (1.0 + t + t * t / 3.0) * exp(-t);
+    }
+}
 
 struct LoopGroup;
 struct gpb_ctx {
@@ -151,6 +166,15 @@ struct gpb_ctx {
     double* sobol_ws = nullptr;
     int64_t sobol_cap = 0;         // doubles
     std::vector<double> h_sobol_box;
+    // sequential design (gpb_design.hip): gpb_design_begin's block x_c [C][d] | x_r [R][d] | w [Rp] | g [P] | s(c,c) [P][Cp] |
+    // V_c [P][Np][Cp] | V_r [P][Np][Rp] | S_rc [P][Rp][Cp] (Cp, Rp: C, R padded to 128), then gpb_chain_design_run's own
+    // (design_run: the picks' scaled rows u_c [T][P][Cp], the pending u_r [P][Rp], chunk partials, scores, denominators)
+    double* design_ws = nullptr;
+    int64_t design_cap = 0;        // doubles
+    double* design_run = nullptr;
+    int64_t design_run_cap = 0;    // doubles
+    int64_t design_C = 0, design_R = 0;
+    bool design_ready = false;     // begun and not yet consumed by a run (the run conditions S_rc in place)
 
     // ---- emulator transform / likelihood ----------------------------------------
     int mode = 0;
@@ -309,7 +333,7 @@ void sliced_free(gpb_ctx* ctx);
 int sliced_read_kstar(gpb_ctx* ctx, int64_t p, int64_t pad, int64_t N, int64_t W, double* out);
 constexpr int GPB_MAX_MULTI_GP = 96;      // GPs one batched launch can address (its table is a kernel argument)
 int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* cov_dev);
-int launch_vmat(gpb_ctx* ctx);     // gpb_cov.hip: vbuf = L^-1 K*^T of the current (fp64) batch
+int launch_vmat(gpb_ctx* ctx, double* dst = nullptr);     // gpb_cov.hip: vbuf (or dst [P][Np][Wld]) = L^-1 K*^T of the current (fp64) batch
 // closed-form cross-validation (gpb_cv.hip): cv_plan checks the folds (GPB_E_ARG / GPB_E_STATE) and uploads them, launch_cv
 // writes element (GP p, position q of idx) of the hold-out mean / variance at [p * sp + q * si] and, when cov_dev is given,
 // the fold covariance blocks [P][nf][kmax][kmax]

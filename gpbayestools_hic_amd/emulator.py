@@ -59,6 +59,43 @@ class SobolIndices:
         return "SobolIndices(nobs=%d, ndim=%d)" % self.first_order.shape
 
 
+class DesignProposal:
+    """Where the next model runs go (Emulator.propose_design, Chain.propose_design): points [n_new, ndim] = the picked candidates
+    in pick order, indices [n_new] into the candidates, gain [n_new] = the drop of the weighted reference-averaged posterior
+    variance each pick brings given the picks before it, variance0 = that variance before any pick (variance0 - gain.sum()
+    is what is left), scores [n_new, n_candidates] (every candidate's gain at every step, -inf once ineligible) when asked."""
+
+    def __init__(self, points, indices, gain, variance0, scores=None):
+        self.points, self.indices, self.gain, self.variance0, self.scores = points, indices, gain, variance0, scores
+
+    def __repr__(self):
+        return "DesignProposal(n_new=%d, variance0=%.6g, gain=%.6g)" % (len(self.indices), self.variance0, float(np.sum(self.gain)))
+
+
+def _design_inputs(who, n_new, candidates, reference, weights, ndim):
+    """the checked host inputs of a propose_design call: (n_new, candidates, reference, weights normalised to sum 1)"""
+    cand = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, dtype=np.float64)))
+    ref = cand if reference is None else np.ascontiguousarray(np.atleast_2d(np.asarray(reference, dtype=np.float64)))
+    for name, a in (("candidates", cand), ("reference", ref)):
+        if a.ndim != 2 or a.shape[1] != ndim or a.shape[0] < 1:
+            raise ValueError("%s: %s must be [n, %d], got %s" % (who, name, ndim, a.shape))
+        if not np.all(np.isfinite(a)):
+            raise ValueError("%s: %s holds non-finite values" % (who, name))
+    n_new = int(n_new)
+    if n_new < 1 or n_new > cand.shape[0]:
+        raise ValueError("%s: n_new = %d for %d candidates (need 1 <= n_new <= candidates)" % (who, n_new, cand.shape[0]))
+    if weights is None:
+        w = np.full(ref.shape[0], 1.0 / ref.shape[0])
+    else:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.shape[0] != ref.shape[0]:
+            raise ValueError("%s: %d weights for %d reference points" % (who, w.shape[0], ref.shape[0]))
+        if not np.all(w >= 0.0) or not np.isfinite(w.sum()) or w.sum() <= 0.0:
+            raise ValueError("%s: weights must be non-negative with a positive, finite sum" % who)
+        w = w / w.sum()
+    return n_new, cand, ref, w
+
+
 class FittedKernel:
     """`gp.kernel_` of a fitted GP: the sklearn composite `c * RBF|Matern(length_scale) + WhiteKernel(noise_level)`
     the reference builds (src/emulator.py:286-306), as a read-only view with the attributes and the printed form
@@ -755,6 +792,65 @@ class Emulator:
             raise ValueError("main_effect: parameter index %d outside [0, %d)" % (j, lo.shape[0]))
         grid = np.linspace(lo[j], hi[j], 101) if grid is None else np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
         return grid, eng.emu_main_effect(lo, hi, j, grid)
+
+    def _design_gp_weights(self, observable_weights=None):
+        """g_p of the sequential design: the weight of GP p's variance in sum_m u_m var(observable m).  PCA modes: observable m =
+        mu_m + sum_p A_pm z_p, so g_p = sum_m u_m A_pm^2 (u defaults to 1 / scaler.var_: every observable in units of its own
+        spread over the design); no-PCA modes: one GP per observable, g_p = u_p (default 1)."""
+        if observable_weights is None:
+            u = np.ones(self.nobs) if self.perform_no_PCA_ else 1.0 / self.scaler.var_
+        else:
+            u = np.asarray(observable_weights, dtype=np.float64).reshape(-1)
+            if u.shape[0] != self.nobs:
+                raise ValueError("propose_design: %d observable weights for %d observables" % (u.shape[0], self.nobs))
+            if not np.all(u >= 0.0):
+                raise ValueError("propose_design: observable weights must be non-negative")
+        return np.ascontiguousarray(u if self.perform_no_PCA_ else (self._A ** 2) @ u)
+
+    def _design_begin(self, cand_dev, ref_dev, w_dev, g):
+        """This emulator's half of a propose_design call: the points through its parameter map, the design workspace, and
+        variance0 = sum_p g_p sum_r w_r s_p(r, r) from the predict path (its variance less the White noise)."""
+        eng = self._engine_ready()
+        if self.parameterTrafoPCA_:
+            cand_dev, ref_dev = eng.param_map(cand_dev), eng.param_map(ref_dev)
+        _, var = eng.predict(ref_dev)
+        noise = np.exp(np.asarray(self.thetas_)[:, -1])
+        s_rr = var.cpu().numpy() - noise[None, :]
+        variance0 = float(np.dot(w_dev.cpu().numpy() @ s_rr, g))
+        eng.design_begin(cand_dev, ref_dev, w_dev, g)
+        return eng, variance0
+
+    def propose_design(self, n_new, candidates, reference=None, weights=None, observable_weights=None, log_observable=False,
+                       return_scores=False):
+        """Where should the next n_new model runs go?  Greedy minimisation of the emulator's posterior variance averaged over
+        the reference points, in closed form on the device (gpb_design_begin / gpb_chain_design_run): every step takes the
+        candidate whose run would lower sum_m u_m sum_r w_r var[observable m at x_r] the most, then conditions the GPs on it (a
+        run's output is not needed for that: a GP's variance depends on where the runs are, not on what they return).
+
+        candidates [C, ndim] and reference [R, ndim] (default: the candidates) in the original parameters, at most 8192 each;
+        weights [R] >= 0 (default uniform; normalised to sum 1) — posterior samples as reference concentrate the runs where a
+        calibration needs them; observable_weights u [nobs] >= 0 (default 1 / scaler.var_ with the output PCA, 1 without).
+        With exp_and_cov_diagonal the variance is that of the log-observable (what is linear in the GPs): ValueError unless
+        log_observable=True says the caller knows.  Returns a DesignProposal (points, indices, gain, variance0, scores with
+        return_scores).  The hyper-parameters stay those of the fit."""
+        if not self._trained:
+            raise RuntimeError("Emulator is not trained")
+        if self.exp_and_cov_diagonal_ and not log_observable:
+            raise ValueError("propose_design: with exp_and_cov_diagonal the emulator predicts exp(linear in the GPs); the design "
+                             "criterion is the variance of the log-observable, in front of the exp.  Pass log_observable=True "
+                             "to get that.")
+        import torch
+        n_new, cand, ref, w = _design_inputs("propose_design", n_new, candidates, reference, weights, self.design_points.shape[1])
+        g = self._design_gp_weights(observable_weights)
+        dev = torch.device("cuda", self.device)
+        eng = self._engine_ready()
+        try:
+            _, variance0 = self._design_begin(torch.as_tensor(cand, device=dev), torch.as_tensor(ref, device=dev),
+                                              torch.as_tensor(w, device=dev), g)
+            picks, gain, scores = eng.design_run(n_new, None, return_scores)
+        finally:
+            eng.design_end()
+        return DesignProposal(cand[picks], picks, gain, variance0, scores)
 
     def sample_y(self, X, n_samples=1, random_state=None):
         """Sample model output at X -> [n_samples_X, n_samples, nobs] (src/emulator.py:608-633): one

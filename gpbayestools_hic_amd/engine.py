@@ -409,6 +409,31 @@ class GPEngine:
         self._ck(self.lib.gpb_emu_main_effect(self.h, nat.ptr(lo), nat.ptr(hi), int(j), nat.ptr(t), t.shape[0], 0, nat.ptr(curve)))
         return curve
 
+    # ------------------------------------------------------------------ variance-reduction sequential design
+    def design_begin(self, candidates, reference, weights, g):
+        """Build the design workspace (gpb_design_begin): candidates [C, d], reference [R, d] and weights [R] (>= 0, sum 1) are
+        torch cuda tensors in the GPs' input space (behind param_map for a parameterTrafoPCA emulator), g [P] the GPs' weights
+        (host).  For every GP: S_rc = c k(x_r, x_c) - V_r^T V_c and s(c, c).  Overwrites the predict workspace; asynchronous."""
+        self._need_data()
+        Xc = self._check_cols(candidates, "candidates")
+        Xr = self._check_cols(reference, "reference")
+        w = self._dev(weights, (Xr.shape[0],), "weights", contiguous=False)
+        g = nat.f64(g).reshape(-1)
+        if g.shape[0] != self.P:
+            raise ValueError("design_begin: g needs one weight per GP (%d), got %d" % (self.P, g.shape[0]))
+        self._ck(self.lib.gpb_design_begin(self.h, nat.ptr(Xc), Xc.shape[0], nat.ptr(Xr), Xr.shape[0], nat.ptr(w), nat.ptr(g)))
+        self._design_C = int(Xc.shape[0])
+
+    def design_run(self, n_picks, eligible=None, return_scores=False):
+        """The greedy loop over this engine alone (the E = 1 chain call): see design_run() of this module."""
+        return design_run([self], n_picks, eligible, return_scores)
+
+    def design_end(self):
+        """Release the design workspace (gpb_design_end)."""
+        self._check_pid()
+        self._design_C = 0
+        self._ck(self.lib.gpb_design_end(self.h))
+
     # ------------------------------------------------------------------ emulator transform
     def set_transform(self, mode, mu, A=None, cov_trunc=None, scale=None):
         mu = nat.f64(mu)
@@ -667,3 +692,27 @@ class GPEngine:
         out = C.c_double(0.0)
         self._ck(self.lib.gpb_probe_fp64(self.h, int(mode), C.byref(out)))
         return out.value
+
+
+def design_run(engines, n_picks, eligible=None, return_scores=False):
+    """Greedy variance-reduction picks over the engines of a chain (gpb_chain_design_run), every one begun with design_begin on
+    the same number of candidates and reference points: step t takes the eligible candidate with the largest score summed over
+    the engines in order, then conditions every GP on it; enqueued as a whole, read back once.  eligible: torch uint8 cuda [C],
+    updated in place (None: all).  Returns (picks [T] int32, gain [T], scores [T, C] or None) as numpy arrays; a pick of -1 says
+    the eligible candidates ran out.  The run consumes the workspaces: design_begin again before another."""
+    import torch
+    e0 = engines[0]
+    T = int(n_picks)
+    Cn = int(getattr(e0, "_design_C", 0))
+    for g in engines:
+        g._need_data()
+        g._track_stream()
+    dev = torch.device("cuda", e0.device)
+    if eligible is not None:
+        eligible = e0._dev(eligible, (Cn,), "eligible", dtype="torch.uint8")
+    arr = (C.c_void_p * len(engines))(*[g.h for g in engines])
+    picks = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    gain = torch.empty(max(T, 1), dtype=torch.float64, device=dev)
+    scores = torch.empty((max(T, 1), max(Cn, 1)), dtype=torch.float64, device=dev) if return_scores else None
+    e0._ck(e0.lib.gpb_chain_design_run(arr, len(engines), T, nat.ptr(eligible), nat.ptr(picks), nat.ptr(gain), nat.ptr(scores)))
+    return picks.cpu().numpy(), gain.cpu().numpy(), (scores.cpu().numpy() if return_scores else None)

@@ -360,6 +360,49 @@ class Chain:
         return SobolIndices(*[np.concatenate([getattr(r, k) for r in parts], axis=0)
                               for k in ("mean", "variance", "first_order", "total")], names=list(self.pardict))
 
+    def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False):
+        """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
+        emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a
+        candidate is the sum of the emulators' scores in emuList order, each emulator seeing the points through its own
+        parameter map.  Observable m weighs 1 / expdata_cov[m, m]: variance in units of the experimental variance.
+
+        candidates [C, ndim]; those outside the open prior box are never picked.  reference [R, ndim] (default: the candidates)
+        is typically a set of posterior samples, weights [R] their weights (default uniform).  Returns a DesignProposal.
+        NotImplementedError for foreign emulators and for exp_and_cov_diagonal emulators (their design variance is that of the
+        log-observable, which the experimental variance does not measure)."""
+        from .emulator import DesignProposal, _design_inputs
+        from .engine import design_run
+        if not self._native():
+            raise NotImplementedError("propose_design needs every emulator of the chain to be this package's Emulator (foreign "
+                                      "emulators expose no GP state to condition)")
+        if any(e.exp_and_cov_diagonal_ for e in self.emuList):
+            raise NotImplementedError("propose_design: an exp_and_cov_diagonal emulator's design variance is that of the "
+                                      "log-observable; the experimental variance is in the observable's units")
+        import torch
+        n_new, cand, ref, w = _design_inputs("propose_design", n_new, candidates, reference, weights, self.ndim)
+        inside = np.all((cand > self.min) & (cand < self.max), axis=1)
+        if n_new > np.count_nonzero(inside):
+            raise ValueError("propose_design: n_new = %d, but only %d candidates lie inside the prior box"
+                             % (n_new, np.count_nonzero(inside)))
+        u = 1.0 / np.diag(self.expdata_cov)
+        if u.shape[0] != sum(e.nobs for e in self.emuList):
+            raise ValueError("emulators provide %d observables, experiment has %d" % (sum(e.nobs for e in self.emuList), u.shape[0]))
+        dev = torch.device("cuda", self.device)
+        cand_dev, ref_dev, w_dev = (torch.as_tensor(a, device=dev) for a in (cand, ref, w))
+        eligible = torch.as_tensor(inside.astype(np.uint8), device=dev)
+        engs, variance0, i0 = [], 0.0, 0
+        try:
+            for emu in self.emuList:
+                engs.append(emu._engine_ready())
+                _, v0 = emu._design_begin(cand_dev, ref_dev, w_dev, emu._design_gp_weights(u[i0:i0 + emu.nobs]))
+                variance0 += v0
+                i0 += emu.nobs
+            picks, gain, scores = design_run(engs, n_new, eligible, return_scores)
+        finally:
+            for g in engs:
+                g.design_end()
+        return DesignProposal(cand[picks], picks, gain, variance0, scores)
+
     grad_slab_rows = 1 << 14                     # most rows of one gradient evaluation (a row's numbers do not depend on it)
 
     def _log_prob_grad(self, X, outside):

@@ -220,6 +220,40 @@ GPB_API int gpb_emu_sobol(gpb_ctx* ctx, const double* lo_host /*[d]*/, const dou
 GPB_API int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host /*[d]*/, const double* hi_host /*[d]*/, int64_t j,
                         const double* t /*[G]*/, int64_t G, int on_device, double* curve /*[G,M]*/);
 
+/* ---- variance-reduction sequential design: where the next model runs go ------------------------------------------------ *
+ * (the reference's design.py is a one-shot space-filling generator; nothing there chooses a second wave from a fitted emulator.)
+ * Needs only what is resident after gpb_gp_factor — X, theta, L^-1 — and no training output.  For GP p, amplitude c, kernel k,
+ * tau = sigma_n^2 + alpha, v(a) = L^-1 k(X, a), the posterior covariance of the latent function (no White term) is
+ *   s(a, b) = c k(a, b) - v(a)^T v(b)
+ * and a new run at x, observed with the training runs' noise, conditions every GP of every context at once:
+ *   s'(a, b) = s(a, b) - s(a, x) s(x, b) / (s(x, x) + tau)
+ * With candidates x_c [C, d], reference points x_r [R, d] of weights w_r >= 0 (sum 1) and GP weights g_p >= 0 the score
+ *   J(c) = sum_p g_p [sum_r w_r s_p(r, c)^2] / (s_p(c, c) + tau_p)
+ * is exactly the drop of sum_p g_p sum_r w_r s_p(r, r) when x_c joins the design (active learning Cohn; Seo et al. 2000).
+ * gpb_design_begin builds the context's design workspace on its stream: V_c, V_r, S_rc = c k(x_r, x_c) - V_r^T V_c [P, R, C]
+ *   (an fp64 MFMA product over the design's rows; padding rows contribute exactly zero) and s(c, c).  All three kernel families.
+ *   The points are in the GPs' input space: a caller with a parameter map applies gpb_param_map first.  Xc, Xr, w are device
+ *   arrays (copied: they may be released after the call), g a host array.
+ * gpb_chain_design_run enqueues the whole greedy loop of T picks with no host synchronisation, over the E contexts of a chain
+ *   (E = 1: one emulator): J = fl(fl(J_1 + J_2) + J_3 ...) in the order of ctxs, each J_e summed over its GPs in index order;
+ *   step t takes the eligible candidate with the largest J (the lowest index on exact ties), clears its flag and conditions
+ *   every s_p on it by the rank-one formula.  eligible [C] (uint8, device, in/out; NULL: all), picks [T] (int32), gain [T] =
+ *   J_t(pick_t), scores [T, C] or NULL (ineligible entries -inf): device arrays, valid once the stream has run.  With fewer than T
+ *   eligible candidates the remaining picks are -1 and their gain NaN.  A run conditions the workspace in place: another run
+ *   needs another gpb_design_begin.  No floating-point atomics; every sum in an order fixed by the padded shapes alone — equal
+ *   inputs give equal bits, and step-0 scores do not depend on T; no [C, C] matrix is formed.
+ * gpb_design_end releases the workspace (synchronises the stream).
+ * Errors: GPB_E_STATE without a factorisation, on a gpb_gp_set_multi context, for a run before begin (or after a new
+ * factorisation, or a second run), for contexts begun with different C or R; GPB_E_ARG for C, R or T < 1, C or R > 8192, T > C,
+ * a negative g, more than 32 contexts, contexts on different streams.  The factorisation and alpha are untouched.  The predict
+ * workspace does NOT survive gpb_design_begin: it holds the reference points' K*^T afterwards and may have been re-allocated;
+ * later predict / likelihood calls recompute it and return what they would have returned before. */
+GPB_API int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev /*[C,d]*/, int64_t C, const double* Xr_dev /*[R,d]*/, int64_t R,
+                     const double* w_dev /*[R]*/, const double* g_host /*[P]*/);
+GPB_API int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint8_t* eligible_dev /*[C] or NULL*/,
+                         int32_t* picks_dev /*[T]*/, double* gain_dev /*[T]*/, double* scores_dev /*[T,C] or NULL*/);
+GPB_API int gpb_design_end(gpb_ctx* ctx);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
