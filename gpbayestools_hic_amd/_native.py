@@ -40,6 +40,7 @@ BOUNDARY = {
     "gpb_stream": (VP, [VP]),
     "gpb_gp_set": (C.c_int, [VP, c_i64, c_i64, c_i64, VP, VP, C.c_int, C.c_double]),
     "gpb_gp_set_multi": (C.c_int, [VP, c_i64, c_i64, VP, VP, VP, C.c_int, C.c_double]),
+    "gpb_gp_set_point_noise": (C.c_int, [VP, VP]),
     "gpb_gp_lml_subset": (C.c_int, [VP, c_i64, VP, VP, VP, VP, VP]),
     "gpb_gp_set_theta": (C.c_int, [VP, VP]),
     "gpb_gp_factor": (C.c_int, [VP, VP]),
@@ -57,6 +58,7 @@ BOUNDARY = {
     "gpb_emu_sobol": (C.c_int, [VP, VP, VP, C.c_int, VP, VP, VP, VP]),
     "gpb_emu_main_effect": (C.c_int, [VP, VP, VP, c_i64, VP, c_i64, C.c_int, VP]),
     "gpb_design_begin": (C.c_int, [VP, VP, c_i64, VP, c_i64, VP, VP]),
+    "gpb_design_set_noise": (C.c_int, [VP, VP]),
     "gpb_chain_design_run": (C.c_int, [VP, C.c_int, c_i64, VP, VP, VP, VP]),
     "gpb_design_end": (C.c_int, [VP]),
     "gpb_like_set": (C.c_int, [VP, VP, VP]),

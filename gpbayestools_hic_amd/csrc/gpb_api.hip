@@ -136,7 +136,7 @@ extern "C" int gpb_ctx_destroy(gpb_ctx* ctx) {
     ctx->ls = ctx->amp = ctx->noise = nullptr; ctx->gpform = ctx->gpmap = nullptr;         // (carved out of thblk)
     if (ctx->h_thblk) (void)hipHostFree(ctx->h_thblk);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    dev_free(&ctx->Z); dev_free(&ctx->K); dev_free(&ctx->Linv); dev_free(&ctx->T); dev_free(&ctx->yv);
+    dev_free(&ctx->Z); dev_free(&ctx->pnoise); dev_free(&ctx->K); dev_free(&ctx->Linv); dev_free(&ctx->T); dev_free(&ctx->yv);
     gpb::sliced_free(ctx);
     dev_free(&ctx->alpha); dev_free(&ctx->apart); dev_free(&ctx->info); dev_free(&ctx->lmlbuf);
     dev_free(&ctx->gpart); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->KsT); dev_free(&ctx->mpart);
@@ -192,6 +192,7 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     ctx->multi = multi; ctx->subset = false;
     ctx->Np = round_up(N, NB);
     ctx->have_theta = ctx->factored = ctx->design_ready = false;
+    dev_free(&ctx->pnoise);                            // the new GPs start without per-point noise (gpb_gp_set_point_noise)
     // whatever was installed for the previous GPs (observable transform sized [old P][M], likelihood block, low-rank
     // factors, parameter map) does not describe the new ones: it has to be set again
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
@@ -316,6 +317,39 @@ extern "C" int gpb_gp_set_multi(gpb_ctx* ctx, int64_t P, int64_t d, const int64_
         Np = np_;
     }
     return gp_set_impl(ctx, P, d, N_host, X_host, Z_host, true, kernel_id, alpha);
+}
+
+// Per-point simulation noise of the training diagonal (stochastic kriging): s_host[p] -> N_p variances of stored GP p, or NULL for
+// none.  Stored like Z ([Pstore][Np], design point i at pad_front + i, zero in the padding) and read through GpSel::q like Z, so the
+// copies of a restart batch and the slots of gpb_gp_lml_subset see their own rows.
+extern "C" int gpb_gp_set_point_noise(gpb_ctx* ctx, const double* const* s_host) {
+    if (!ctx) return GPB_E_ARG;
+    if (ctx->N == 0) GPB_FAIL(GPB_E_STATE, "gpb_gp_set_point_noise before gpb_gp_set");
+    const int64_t P = ctx->Pstore, Np = ctx->Np;
+    if (s_host)
+        for (int64_t p = 0; p < P; ++p) {
+            if (!s_host[p]) GPB_FAIL(GPB_E_ARG, "gpb_gp_set_point_noise: null row");
+            const int64_t Nq = ctx->multi ? (int64_t)ctx->h_N[(size_t)p] : ctx->N;
+            for (int64_t i = 0; i < Nq; ++i)
+                if (!(s_host[p][i] >= 0.0) || !isfinite(s_host[p][i]))
+                    GPB_FAIL(GPB_E_ARG, "gpb_gp_set_point_noise: a variance is negative or not finite");
+        }
+    GPB_HIP(hipSetDevice(ctx->device));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));        // nothing enqueued still reads the array that is replaced
+    ctx->factored = ctx->design_ready = false;         // the resident factorisation is of another diagonal
+    if (!s_host) {
+        dev_free(&ctx->pnoise);
+        return 0;
+    }
+    int rc;
+    if ((rc = dev_alloc(ctx, &ctx->pnoise, P * Np))) return rc;
+    std::vector<double> sp((size_t)(P * Np), 0.0);
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t Nq = ctx->multi ? (int64_t)ctx->h_N[(size_t)p] : ctx->N, pad = pad_front(Np, Nq);
+        for (int64_t i = 0; i < Nq; ++i) sp[(size_t)(p * Np + pad + i)] = s_host[p][i];
+    }
+    GPB_HIP(hipMemcpy(ctx->pnoise, sp.data(), sizeof(double) * sp.size(), hipMemcpyHostToDevice));
+    return 0;
 }
 
 // The distance form of every GP, from theta and the design's extents alone — never from a batch's size or a rank's share, so a

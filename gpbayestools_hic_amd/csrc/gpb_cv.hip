@@ -1,10 +1,11 @@
 // gpb_cv.hip — closed-form leave-one-out / leave-k-out cross-validation of the factored GPs (gpb_gp_cv, gpb_emu_cv).
 //
-// With Ky = K + (sigma_n^2 + alpha_reg) I = L L^T and a fold F of k design points (Rasmussen & Williams, section 5.4.2, for blocks):
+// With Ky = K + sigma_n^2 I + diag(t) = L L^T, t_i = alpha_reg + s_i (s: the per-point simulation noise of gpb_gp_set_point_noise, zero
+// when none is installed), and a fold F of k design points (Rasmussen & Williams, section 5.4.2, for blocks):
 //     G_F = (Ky^-1)_FF = (L^-1[:, F])^T (L^-1[:, F])                  a k x k Gram matrix over rows of L^-1
 //     mean of the GP refitted without F (same theta) at X_F           = z_F - G_F^-1 alpha_F
-//     its GPR.predict(X_F, return_cov=True)                           = G_F^-1 - alpha_reg I
-// (sklearn's predictive prior carries the White noise but not `alpha`: sk:_gpr.py:441-469).  Nothing of size N is factored: L^-1
+//     its GPR.predict(X_F, return_cov=True)                           = G_F^-1 - diag(t_F)
+// (sklearn's predictive prior carries the White noise but not `alpha`, scalar or per point: sk:_gpr.py:441-469).  Nothing of size N is factored: L^-1
 // and alpha stay resident after gpb_gp_factor.  Design point i lives at stored row / column pad_front(Np, N) + i.
 //
 // General path (k_cv_fold): one workgroup per (fold, GP) walks the rows of L^-1 from the fold's smallest stored column down in 64-row
@@ -37,10 +38,11 @@ struct CvOut {
 __global__ __launch_bounds__(CHOL_THREADS) void k_cv_fold(const double* __restrict__ Linv, const double* __restrict__ alpha,
                                                           const double* __restrict__ Z, const int* __restrict__ idx,
                                                           const int* __restrict__ fold_ptr, int64_t Np, int pad, double alpha_reg,
-                                                          int nf, CvOut out, int* __restrict__ notpd) {
+                                                          const double* __restrict__ pnoise, int nf, CvOut out,
+                                                          int* __restrict__ notpd) {
     __shared__ CholLds s;
     __shared__ int scol[64];
-    __shared__ double sa[64], sz[64], su[64];
+    __shared__ double sa[64], sz[64], su[64], st[64];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int f = blockIdx.x, p = blockIdx.y;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_cv_fold(const double* __restri
         scol[tid] = c;
         sa[tid] = tid < k ? alpha[(int64_t)p * Np + c] : 0.0;
         sz[tid] = tid < k ? Z[(int64_t)p * Np + c] : 0.0;
+        st[tid] = (tid < k && pnoise) ? alpha_reg + pnoise[(int64_t)p * Np + c] : alpha_reg;      // t_i: alpha + s_i first (k_kmat)
     }
     __syncthreads();
     int cmin = (int)Np;
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_cv_fold(const double* __restri
         }
         const int64_t o = (int64_t)p * out.sp + (int64_t)(q0 + tid) * out.si;
         out.mean[o] = bad ? nan : sz[tid] - w;
-        if (out.var) out.var[o] = bad ? nan : g - alpha_reg;
+        if (out.var) out.var[o] = bad ? nan : g - st[tid];
     }
     if (out.cov) {
         const int km = out.kmax;
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_cv_fold(const double* __restri
             double g = 0.0;
             if (i < k && j < k) {
                 for (int m = max(i, j); m < 64; ++m) g = fma(s.x[m][i], s.x[m][j], g);
-                g = bad ? nan : (i == j ? g - alpha_reg : g);
+                g = bad ? nan : (i == j ? g - st[i] : g);
             }
             C[e] = g;
         }
@@ -148,8 +151,8 @@ __global__ __launch_bounds__(256) void k_cv_colsq(const double* __restrict__ Lin
 
 __global__ __launch_bounds__(256) void k_cv_loo(const double* __restrict__ part, const double* __restrict__ alpha,
                                                 const double* __restrict__ Z, const int* __restrict__ idx, int64_t n_idx,
-                                                int64_t Np, int nI, int pad, double alpha_reg, CvOut out,
-                                                int* __restrict__ notpd) {
+                                                int64_t Np, int nI, int pad, double alpha_reg,
+                                                const double* __restrict__ pnoise, CvOut out, int* __restrict__ notpd) {
     const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int p = blockIdx.y;
     if (q >= n_idx) return;
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(256) void k_cv_loo(const double* __restrict__ part,
     const double nan = __builtin_nan("");
     const double ginv = 1.0 / g;
     const int64_t o = (int64_t)p * out.sp + q * out.si;
-    const double var = bad ? nan : ginv - alpha_reg;
+    const double var = bad ? nan : ginv - (pnoise ? alpha_reg + pnoise[(int64_t)p * Np + col] : alpha_reg);
     out.mean[o] = bad ? nan : Z[(int64_t)p * Np + col] - alpha[(int64_t)p * Np + col] * ginv;
     if (out.var) out.var[o] = var;
     if (out.cov) out.cov[(int64_t)p * n_idx + q] = var;           // kmax = 1, nf = n_idx
@@ -239,10 +242,10 @@ int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64
         double* part = reinterpret_cast<double*>(reinterpret_cast<int*>(ctx->cv_ws) + ctx->cv_ints);
         hipLaunchKernelGGL(k_cv_colsq, dim3((unsigned)nI, (unsigned)nI, (unsigned)P), dim3(256), 0, ctx->stream, ctx->Linv, part, Np, nI);
         hipLaunchKernelGGL(k_cv_loo, dim3((unsigned)((n_idx + 255) / 256), (unsigned)P), dim3(256), 0, ctx->stream, part, ctx->alpha,
-                           ctx->Z, idx, n_idx, Np, nI, pad, ctx->alpha_reg, out, ctx->notpd);
+                           ctx->Z, idx, n_idx, Np, nI, pad, ctx->alpha_reg, ctx->pnoise, out, ctx->notpd);
     } else {
         hipLaunchKernelGGL(k_cv_fold, dim3((unsigned)nf, (unsigned)P), dim3(CHOL_THREADS), 0, ctx->stream, ctx->Linv, ctx->alpha,
-                           ctx->Z, idx, idx + n_idx, Np, pad, ctx->alpha_reg, (int)nf, out, ctx->notpd);
+                           ctx->Z, idx, idx + n_idx, Np, pad, ctx->alpha_reg, ctx->pnoise, (int)nf, out, ctx->notpd);
     }
     GPB_HIP(hipGetLastError());
     return 0;

@@ -2,7 +2,8 @@
 // model runs go, from what is already resident (X, theta, L^-1).  No training output enters.
 //
 // For GP p: v(a) = L^-1 k(X, a) and the posterior covariance of the latent function s(a, b) = c k(a, b) - v(a)^T v(b) (no White
-// term).  A run at x, observed with the training runs' noise tau = sigma_n^2 + alpha, conditions every GP:
+// term).  A run at x, observed with the training runs' noise tau = sigma_n^2 + alpha — or, after gpb_design_set_noise, with candidate
+// c's own tau_p(c) = sigma_n^2 + (alpha + s_c[p][c]), the sum alpha + s first as on the training diagonal — conditions every GP:
 //     s'(a, b) = s(a, b) - s(a, x) s(x, b) / (s(x, x) + tau)
 // and lowers the reference-averaged variance sum_p g_p sum_r w_r s_p(r, r) by
 //     J(x) = sum_p g_p [sum_r w_r s_p(r, x)^2] / (s_p(x, x) + tau_p)                     (active learning Cohn; Seo et al. 2000)
@@ -124,10 +125,12 @@ __global__ __launch_bounds__(256) void k_design_score(double* __restrict__ S, co
     if (!half) part[((int64_t)p * gridDim.y + blockIdx.y) * Cp + c] = acc + sh[threadIdx.x];
 }
 
-// J[c] = sum_p g_p [sum_chunks part[p][chunk][c]] / (dg[p][c] + tau_p): chunks, then GPs, in index order; a GP of weight 0 is left out
+// J[c] = sum_p g_p [sum_chunks part[p][chunk][c]] / (dg[p][c] + tau_p): chunks, then GPs, in index order; a GP of weight 0 is left out.
+// sc (gpb_design_set_noise, or nullptr): the candidates' simulation noise [P][Cp], tau_p(c) = sigma_n^2 + (alpha + sc[p][c]).
 __global__ __launch_bounds__(256) void k_design_combine(const double* __restrict__ part, const double* __restrict__ dg,
                                                         const double* __restrict__ g, const double* __restrict__ noise, double alpha_reg,
-                                                        int P, int nch, int64_t Cp, int C, double* __restrict__ J) {
+                                                        const double* __restrict__ sc, int P, int nch, int64_t Cp, int C,
+                                                        double* __restrict__ J) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= Cp) return;
     double j = 0.0;
@@ -136,7 +139,8 @@ __global__ __launch_bounds__(256) void k_design_combine(const double* __restrict
             if (g[p] == 0.0) continue;
             double q = 0.0;
             for (int ch = 0; ch < nch; ++ch) q += part[((int64_t)p * nch + ch) * Cp + c];
-            j += g[p] * (q / (dg[(int64_t)p * Cp + c] + (noise[p] + alpha_reg)));
+            const double a = sc ? alpha_reg + sc[(int64_t)p * Cp + c] : alpha_reg;
+            j += g[p] * (q / (dg[(int64_t)p * Cp + c] + (noise[p] + a)));
         }
     }
     J[c] = j;
@@ -190,14 +194,15 @@ __global__ __launch_bounds__(1024) void k_design_pick(const DesignTab tab, int C
 
 // u_r[p][r] = S[p][r][c*] / sqrt(den_p), den_p = s_p(c*, c*) + tau_p, kept in den[p] for k_design_row (which changes s(c*, c*))
 __global__ __launch_bounds__(256) void k_design_ur(const double* __restrict__ S, const double* __restrict__ dg, const double* __restrict__ noise,
-                                                   double alpha_reg, const int* __restrict__ pick, int64_t Rp, int64_t Cp, int R,
-                                                   double* __restrict__ ur, double* __restrict__ den) {
+                                                   double alpha_reg, const double* __restrict__ sc, const int* __restrict__ pick,
+                                                   int64_t Rp, int64_t Cp, int R, double* __restrict__ ur, double* __restrict__ den) {
     const int p = blockIdx.y, cs = *pick;
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= Rp) return;
     double u = 0.0, dn = 1.0;
     if (cs >= 0) {
-        dn = dg[(int64_t)p * Cp + cs] + (noise[p] + alpha_reg);
+        const double a = sc ? alpha_reg + sc[(int64_t)p * Cp + cs] : alpha_reg;
+        dn = dg[(int64_t)p * Cp + cs] + (noise[p] + a);
         if (r < R) u = S[((int64_t)p * Rp + r) * Cp + cs] / sqrt(dn);
     }
     ur[(int64_t)p * Rp + r] = u;
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(256) void k_design_row(const double* __restrict__ V
 
 // the begin block's layout (doubles; every part starts on an even offset: the GEMM's operands are read two at a time)
 struct DesignLayout {
-    int64_t Cp, Rp, xc, xr, w, g, dg, vc, vr, s, total;
+    int64_t Cp, Rp, xc, xr, w, g, dg, vc, vr, s, sc, total;
 };
 DesignLayout design_layout(const gpb_ctx* ctx, int64_t C, int64_t R) {
     DesignLayout L;
@@ -249,7 +254,8 @@ DesignLayout design_layout(const gpb_ctx* ctx, int64_t C, int64_t R) {
     L.vc = L.dg + P * L.Cp;
     L.vr = L.vc + P * Np * L.Cp;
     L.s = L.vr + P * Np * L.Rp;
-    L.total = L.s + P * L.Rp * L.Cp;
+    L.sc = L.s + P * L.Rp * L.Cp;                     // the candidates' simulation noise [P][Cp] (gpb_design_set_noise)
+    L.total = L.sc + P * L.Cp;
     return L;
 }
 
@@ -262,7 +268,7 @@ using namespace gpb;
 extern "C" int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev, int64_t C, const double* Xr_dev, int64_t R, const double* w_dev,
                                 const double* g_host) {
     if (!ctx) return GPB_E_ARG;
-    ctx->design_ready = false;
+    ctx->design_ready = ctx->design_noise = false;
     if (ctx->N == 0) GPB_FAIL(GPB_E_STATE, "gpb_design_begin before gpb_gp_set");
     if (ctx->multi) GPB_FAIL(GPB_E_STATE, "gpb_design_begin: a gpb_gp_set_multi context is fit-only (its GPs have different designs)");
     if (!ctx->factored) GPB_FAIL(GPB_E_STATE, "gpb_design_begin before gpb_gp_factor");
@@ -311,6 +317,24 @@ extern "C" int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev, int64_t C, c
     ctx->design_C = C;
     ctx->design_R = R;
     ctx->design_ready = true;
+    return 0;
+}
+
+extern "C" int gpb_design_set_noise(gpb_ctx* ctx, const double* s_c_dev) {
+    if (!ctx) return GPB_E_ARG;
+    if (!ctx->design_ready) GPB_FAIL(GPB_E_STATE, "gpb_design_set_noise before gpb_design_begin (or after the run that consumed it)");
+    if (!s_c_dev) {                                    // back to the training runs' tau_p
+        ctx->design_noise = false;
+        return 0;
+    }
+    GPB_HIP(hipSetDevice(ctx->device));
+    const int64_t C = ctx->design_C, P = ctx->P;
+    const DesignLayout L = design_layout(ctx, C, ctx->design_R);
+    double* sc = ctx->design_ws + L.sc;
+    GPB_HIP(hipMemsetAsync(sc, 0, sizeof(double) * (size_t)(P * L.Cp), ctx->stream));
+    GPB_HIP(hipMemcpy2DAsync(sc, sizeof(double) * (size_t)L.Cp, s_c_dev, sizeof(double) * (size_t)C, sizeof(double) * (size_t)C, (size_t)P,
+                             hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->design_noise = true;
     return 0;
 }
 
@@ -378,7 +402,7 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
                 hipLaunchKernelGGL(k_design_score<true>, gs, dim3(256), 0, st, ws + L.s, run[e].ur, run[e].U + (t - 1) * P * Cp, ws + L.w,
                                    run[e].part, Rp, Cp);
             hipLaunchKernelGGL(k_design_combine, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, st, run[e].part, ws + L.dg, ws + L.g,
-                               c->noise, c->alpha_reg, P, nch, Cp, (int)C, run[e].J);
+                               c->noise, c->alpha_reg, c->design_noise ? ws + L.sc : nullptr, P, nch, Cp, (int)C, run[e].J);
         }
         hipLaunchKernelGGL(k_design_pick, dim3(1), dim3(1024), 0, st, tab, (int)C, elig, (int)t, pick, picks_dev, gain_dev, scores_dev);
         if (t + 1 == T) break;                         // (nothing reads the last pick's downdate)
@@ -389,7 +413,7 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
             const int P = (int)c->P;
             const int64_t k0 = pad_front(c->Np, c->N);
             hipLaunchKernelGGL(k_design_ur, dim3((unsigned)((Rp + 255) / 256), (unsigned)P), dim3(256), 0, st, ws + L.s, ws + L.dg, c->noise,
-                               c->alpha_reg, pick, Rp, Cp, (int)R, run[e].ur, run[e].den);
+                               c->alpha_reg, c->design_noise ? ws + L.sc : nullptr, pick, Rp, Cp, (int)R, run[e].ur, run[e].den);
             const dim3 gr((unsigned)(Cp / 64), (unsigned)P);
 #define GPB_DS_ROW(KIND)                                                                                                          \
     hipLaunchKernelGGL(k_design_row<KIND>, gr, dim3(256), 0, st, ws + L.vc, run[e].U, ws + L.xc, c->ls, c->amp, run[e].den, pick,  \
@@ -407,7 +431,7 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
 
 extern "C" int gpb_design_end(gpb_ctx* ctx) {
     if (!ctx) return GPB_E_ARG;
-    ctx->design_ready = false;
+    ctx->design_ready = ctx->design_noise = false;
     ctx->design_C = ctx->design_R = 0;
     if (!ctx->design_ws && !ctx->design_run) return 0;
     GPB_HIP(hipSetDevice(ctx->device));

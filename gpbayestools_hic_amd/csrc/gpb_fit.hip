@@ -83,8 +83,8 @@ int launch_scale_design(gpb_ctx* ctx) {
 template <int KIND>
 __global__ __launch_bounds__(256) void k_kmat(const double* __restrict__ Xsc, const double* __restrict__ amp,
                                               const double* __restrict__ noise, double alpha_reg,
-                                              double* __restrict__ K, const GpSel sel, int64_t Np, int dpad,
-                                              const int* __restrict__ form) {
+                                              const double* __restrict__ pnoise, double* __restrict__ K, const GpSel sel,
+                                              int64_t Np, int dpad, const int* __restrict__ form) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int p = blockIdx.z;
     const int64_t pad = pad_front(Np, sel.Nq(sel.q(p))), hi = pad + sel.Nq(sel.q(p));      // the design: rows [pad, hi)
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k_kmat(const double* __restrict__ Xsc, co
                 r2[a][b] = fma(df, df, r2[a][b]);
             }
     }
-    const double c = amp[p], dg = amp[p] + noise[p] + alpha_reg;
+    const double c = amp[p], dg0 = amp[p] + noise[p], dg = dg0 + alpha_reg;
     double* Kp = K + (int64_t)p * Np * Np;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -134,6 +134,17 @@ __global__ __launch_bounds__(256) void k_kmat(const double* __restrict__ Xsc, co
             else v = c * shape_fn<KIND>(r2[a][b]);
             Kp[i * Np + j] = v;
         }
+    // per-point simulation noise (gpb_gp_set_point_noise): the design's diagonal entries again, by the threads that wrote them
+    // above, as c + sigma_n^2 + (alpha + s_i) — alpha + s_i formed first, so that s = 0 gives the scalar's bits.  Apart from the
+    // loop above, which stays the code it was (inside it the sixteen loads were hoisted: 34 more VGPRs, 4 waves per SIMD for 6).
+    if (pnoise && blockIdx.x == blockIdx.y && ty == tx) {
+        const double* pn = pnoise + sel.q(p) * Np;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int64_t i = i0 + ty + 16 * a;
+            if (i >= pad && i < hi) Kp[i * Np + i] = dg0 + (alpha_reg + pn[i]);
+        }
+    }
 }
 
 // The same matrix, organised for throughput (the GPs in the Gram form: all of them unless a length scale is extreme):
@@ -158,8 +169,9 @@ __device__ __forceinline__ double kmat_pair(double ab, double si, double sj) {
 template <int KIND, int DPAD>
 __global__ __launch_bounds__(256) void k_kmat_mfma(const double* __restrict__ Xc, const double* __restrict__ dnorm,
                                                    const double* __restrict__ amp, const double* __restrict__ noise,
-                                                   double alpha_reg, double* __restrict__ K, const GpSel sel, int64_t Np,
-                                                   const int* __restrict__ form, const int2* __restrict__ tiles) {
+                                                   double alpha_reg, const double* __restrict__ pnoise, double* __restrict__ K,
+                                                   const GpSel sel, int64_t Np, const int* __restrict__ form,
+                                                   const int2* __restrict__ tiles) {
     if (form && form[blockIdx.y] != 0) return;         // a difference-form GP: k_kmat's
     const int64_t pad = pad_front(Np, sel.Nq(sel.q(blockIdx.y))), hi = pad + sel.Nq(sel.q(blockIdx.y));     // the design: rows [pad, hi)
     // the tile's two operand blocks (64 design rows x DPAD each, contiguous in Xc) are staged in LDS by coalesced 16-byte
@@ -229,7 +241,9 @@ __global__ __launch_bounds__(256) void k_kmat_mfma(const double* __restrict__ Xc
             }
         return;
     }
-    const double dg = amp[p] + noise[p] + alpha_reg;
+    // (only here, in the tiles with a diagonal: alpha + s_i first, see k_kmat)
+    const double dg0 = amp[p] + noise[p];
+    const double* pn = pnoise ? pnoise + sel.q(p) * Np : nullptr;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -240,7 +254,7 @@ __global__ __launch_bounds__(256) void k_kmat_mfma(const double* __restrict__ Xc
                 const int64_t i = i0 + m0 + 16 * a + lk + 4 * r, j = j0 + n0 + 16 * b + lr;
                 double v;
                 if (i < pad || j < pad || i >= hi || j >= hi) v = (i == j) ? 1.0 : 0.0;      // the padding (gp_set_impl): identity
-                else if (i == j) v = dg;
+                else if (i == j) v = dg0 + (pn ? alpha_reg + pn[i] : alpha_reg);
                 else v = c * kmat_pair<KIND>(acc[a][b][r], sdi[m0 + 16 * a + lk + 4 * r], dj);
                 Kp[i * Np + j] = v;
             }
@@ -254,7 +268,8 @@ static void launch_kmat_mfma(gpb_ctx* ctx) {
     dim3 grid((unsigned)(nb * (nb + 1) / 2), (unsigned)ctx->P);
 #define GPB_KM(DP)                                                                                                  \
     hipLaunchKernelGGL((k_kmat_mfma<KIND, DP>), grid, dim3(256), 0, ctx->stream, ctx->Xc, ctx->dnorm, ctx->amp,     \
-                       ctx->noise, ctx->alpha_reg, ctx->K, ctx->sel(), ctx->Np, ctx->n_diff > 0 ? ctx->gpform : nullptr,     \
+                       ctx->noise, ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np,                            \
+                       ctx->n_diff > 0 ? ctx->gpform : nullptr,                                                     \
                        reinterpret_cast<const int2*>(ctx->kmtiles))
     switch (ctx->dpad) {
         case 8: GPB_KM(8); break;
@@ -273,7 +288,7 @@ static void launch_kmat_diff(gpb_ctx* ctx, const int* form) {
     const size_t sh = 2 * 64 * (ctx->dpad + 1) * sizeof(double);
 #define GPB_KMAT(KIND)                                                                          \
     hipLaunchKernelGGL(k_kmat<KIND>, grid, dim3(256), sh, ctx->stream, ctx->Xsc, ctx->amp,       \
-                       ctx->noise, ctx->alpha_reg, ctx->K, ctx->sel(), ctx->Np, (int)ctx->dpad, form)
+                       ctx->noise, ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np, (int)ctx->dpad, form)
     if (ctx->kind == GPB_KERNEL_RBF) GPB_KMAT(GPB_KERNEL_RBF);
     else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_KMAT(GPB_KERNEL_MATERN15);
     else GPB_KMAT(GPB_KERNEL_MATERN25);

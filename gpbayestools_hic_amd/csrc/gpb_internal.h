@@ -96,6 +96,9 @@ struct gpb_ctx {
     double* amp = nullptr;         // [P] c
     double* noise = nullptr;       // [P] sigma_n^2
     double* Z = nullptr;           // [P][Np]
+    // per-point simulation noise (gpb_gp_set_point_noise; nullptr: none): s [Pstore][Np], laid out and indexed like Z (design point i
+    // of stored GP q at [q * Np + pad_front + i], zero in the padding).  The training diagonal is c + sigma_n^2 + (alpha_reg + s).
+    double* pnoise = nullptr;
     double* K = nullptr;           // [P][Np][Np]  K, overwritten by L (lower) in gp_factor
     double* Linv = nullptr;        // [P][Np][Np]
     // sliced-integer predict (gpb_sliced.hip, option key 51): int8 digit planes of L^-1 (made on first use after a factorisation)
@@ -175,6 +178,7 @@ struct gpb_ctx {
     int64_t design_run_cap = 0;    // doubles
     int64_t design_C = 0, design_R = 0;
     bool design_ready = false;     // begun and not yet consumed by a run (the run conditions S_rc in place)
+    bool design_noise = false;     // gpb_design_set_noise: the begin block's s_c [P][Cp] holds the candidates' simulation noise
 
     // ---- emulator transform / likelihood ----------------------------------------
     int mode = 0;

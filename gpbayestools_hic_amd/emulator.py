@@ -202,8 +202,12 @@ class Emulator:
     def __init__(self, training_set_path=".", parameter_file="ABCD.txt",
                  npc=10, nrestarts=0, logTrafo=False, parameterTrafoPCA=False,
                  max_rel_uncertainty_data=0.1, exp_and_cov_diagonal=False,
-                 perform_no_PCA=False, device=0):
+                 perform_no_PCA=False, device=0, simulation_error=False):
         self.logTrafo_ = logTrafo
+        # stochastic kriging: every training event's statistical error (model_data_err) goes on its own entry of the GPs'
+        # training diagonal (_project_errors) — the GP core of the reference's EmulatorBAND(method='PCSK')
+        self.simulation_error_ = bool(simulation_error)
+        self.point_noise_ = None
         self.parameterTrafoPCA_ = parameterTrafoPCA
         self.max_rel_uncertainty_data_ = max_rel_uncertainty_data
         self._load_training_data_pickle(training_set_path)
@@ -241,13 +245,16 @@ class Emulator:
             self.paramTrafoScaler_yloss, self.paramTrafoPCA_yloss = yloss.scaler, yloss.pca
 
     @classmethod
-    def from_reference(cls, ref, device=0):
+    def from_reference(cls, ref, device=0, simulation_error=False):
         """Take over a TRAINED emulator object of the reference (`src.emulator.Emulator` after `trainEmulator`: what the dill
         pickles of examples/EmulatorTraining.ipynb hold and `Chain.loadEmulator` reads, src/mcmc.py:145-150) without retraining:
         its fitted scaler and PCA, the GPs' training inputs, targets and hyper-parameters (`gp.X_train_`, `gp.y_train_`,
         `gp.kernel_.theta`, `gp.alpha`: sk:_gpr.py:260-364), its flags and — with parameterTrafoPCA — its three fitted parameter
         maps go into a drop-in `Emulator`; the factorisation is redone on the device at first use.  Nothing of `ref` is called:
-        attributes are read (duck-typed), so the reference package is needed only to unpickle `ref`.  Raises ValueError for an
+        attributes are read (duck-typed), so the reference package is needed only to unpickle `ref`.  GPs fitted with a per-point
+        `alpha` (an array: stochastic kriging) are refused as before unless `simulation_error=True` says the caller means it: then
+        arrays with one entry per training point, possibly another array per GP, are adopted as alpha = 0 plus that array as
+        `point_noise_`; any other shape, or scalars and arrays mixed, is refused either way.  Raises ValueError for an
         object that is not a trained emulator of that kind (an `EmulatorBAND`, a kernel outside RBF / Matern-3/2 / 5/2, GPs
         over different inputs)."""
         gps = list(getattr(ref, "gps", None) or [])
@@ -275,14 +282,22 @@ class Emulator:
             ym, ys = np.asarray(getattr(g, "_y_train_mean", 0.0)), np.asarray(getattr(g, "_y_train_std", 1.0))
             if bool(getattr(g, "normalize_y", False)) or np.any(ym != 0.0) or np.any(ys != 1.0):
                 raise ValueError("from_reference: a GP was fitted with normalize_y (_y_train_mean / _y_train_std are not 0 / 1)")
-            if np.ndim(g.alpha) != 0:
-                raise ValueError("from_reference: a GP has a per-point alpha (array), not the reference's scalar")
+            if np.ndim(g.alpha) not in (0, 1) or (np.ndim(g.alpha) == 1 and np.shape(g.alpha)[0] != np.shape(g.X_train_)[0]):
+                raise ValueError("from_reference: a GP's alpha is neither a scalar nor an array with one entry per training point "
+                                 "(shape %s for %d points)" % (np.shape(g.alpha), np.shape(g.X_train_)[0]))
+        vector_alpha = [np.ndim(g.alpha) == 1 for g in gps]
+        if any(vector_alpha) and not all(vector_alpha):
+            raise ValueError("from_reference: the GPs mix a scalar alpha and a per-point alpha (array)")
+        vector_alpha = vector_alpha[0]
+        if vector_alpha and not simulation_error:
+            raise ValueError("from_reference: a GP has a per-point alpha (array), not the reference's scalar; pass "
+                             "simulation_error=True to adopt the arrays as per-point simulation noise (stochastic kriging)")
         want = int(np.shape(ref.model_data)[1]) if bool(getattr(ref, "perform_no_PCA_", False)) else int(ref.npc)
         if len(gps) != want:
             raise ValueError("from_reference: %d GPs for %d %s" % (len(gps), want, "observables (perform_no_PCA)" if bool(
                 getattr(ref, "perform_no_PCA_", False)) else "principal components (npc)"))
         X = np.ascontiguousarray(gps[0].X_train_, dtype=np.float64)
-        if len(kinds) != 1 or len({float(g.alpha) for g in gps}) != 1 or \
+        if len(kinds) != 1 or (not vector_alpha and len({float(g.alpha) for g in gps}) != 1) or \
                 any(np.shape(g.X_train_) != X.shape or not np.array_equal(g.X_train_, X) for g in gps[1:]):
             raise ValueError("from_reference: the GPs differ in kernel family, alpha or training inputs")
         thetas = np.array([np.asarray(g.kernel_.theta, dtype=np.float64) for g in gps])
@@ -309,7 +324,13 @@ class Emulator:
             for name in ("mean_", "components_", "explained_variance_", "explained_variance_ratio_"):
                 setattr(emu.pca, name, np.array(getattr(ref.pca, name), dtype=np.float64))
             emu.pca.n_components_ = int(ref.pca.n_components_)
-        emu.device, emu.alpha = device, float(gps[0].alpha)
+        # GPR(alpha=<array>) (stochastic kriging, sk:_gpr.py:347): adopted as alpha = 0 plus the array as per-point noise — the
+        # training diagonal c + sigma_n^2 + (0 + alpha_i) is sklearn's
+        emu.device, emu.alpha = device, 0.0 if vector_alpha else float(gps[0].alpha)
+        emu.simulation_error_ = bool(vector_alpha)
+        emu.point_noise_ = np.ascontiguousarray([np.asarray(g.alpha, dtype=np.float64) for g in gps]) if vector_alpha else None
+        if vector_alpha and not (np.all(np.isfinite(emu.point_noise_)) and np.all(emu.point_noise_ >= 0.0)):
+            raise ValueError("from_reference: a per-point alpha has a negative or non-finite entry")
         emu._engine, emu._like_key, emu.fit_sharding = None, None, None
         if emu.parameterTrafoPCA_:
             from . import param_pca as _pp
@@ -434,6 +455,21 @@ class Emulator:
         self._train_events = np.flatnonzero(mask)                         # rows of model_data behind the design points
         self.kernel_type_ = kernel_type
         self._ngp = self._Z_train.shape[0]
+        self.point_noise_ = self._project_errors(self.model_data_err[mask]) if getattr(self, "simulation_error_", False) else None
+
+    def _project_errors(self, E):
+        """Statistical errors E [n, nobs] of events (model_data_err's units) as variances s [ngp, n] of the GPs' targets, with
+        the FITTED scaler and PCA: independent observable errors through the standardisation and the whitened projection,
+        s[k, i] = sum_m (E[i, m] / scale[m])^2 comp[k, m]^2 / ev[k]; without the PCA s[m, i] = (E[i, m] / scale[m])^2."""
+        return project_errors(E, self.scaler.scale_, None if self.perform_no_PCA_ else self.pca.components_,
+                              None if self.perform_no_PCA_ else self.pca.explained_variance_, self.npc)
+
+    def _noise_rows(self, idx=None):
+        """the per-point noise an engine over the GPs `idx` (default: all) takes, None without simulation_error"""
+        pn = getattr(self, "point_noise_", None)
+        if pn is None:
+            return None
+        return pn if idx is None else [pn[i] for i in idx]
 
     def _finish_training(self, eng, thetas, lml):
         """the final factorisation at theta*, the observable transform and the per-GP scores (src/emulator.py:316-363)"""
@@ -459,7 +495,7 @@ class Emulator:
     def _search_engine(self, idx, copies):
         """a fit-only context holding the GPs `idx` of this emulator `copies` times (the starts of their searches)"""
         return _SearchEngine(self.device, [self._X_train] * len(idx), [self._Z_train[i] for i in idx],
-                             _KERNELS[self.kernel_type_][0], self.alpha, copies)
+                             _KERNELS[self.kernel_type_][0], self.alpha, copies, self._noise_rows(idx))
 
     def _optimise(self, eng, kernel_type, draws=None):
         """argmax LML per GP with scipy L-BFGS-B (sk:_gpr.py:296-337,654-670).  The P searches — and, with
@@ -482,7 +518,7 @@ class Emulator:
             if copies > 1:
                 return self._search_engine(idx, copies)
             sub = GPEngine(self.device)
-            sub.set_data(self._X_train, self._Z_train[idx], _KERNELS[kernel_type][0], self.alpha)
+            sub.set_data(self._X_train, self._Z_train[idx], _KERNELS[kernel_type][0], self.alpha, self._noise_rows(idx))
             return sub
         return search_hyperparameters(sub_engine, self._ngp, theta0, bounds, self.nrestarts, sh, close=True, draws=draws)
 
@@ -527,7 +563,7 @@ class Emulator:
             self._engine._check_pid()
             self._engine.close()
         eng = GPEngine(self.device)
-        eng.set_data(self._X_train, self._Z_train, _KERNELS[self.kernel_type_][0], self.alpha)
+        eng.set_data(self._X_train, self._Z_train, _KERNELS[self.kernel_type_][0], self.alpha, self._noise_rows())
         which = getattr(self, "predict_arithmetic", None)
         if which is not None:                        # (not set: the engine's own default, or what GPB_PREDICT_SLICED says)
             eng.tune("predict_sliced", _PREDICT_ARITHMETIC[which])
@@ -595,6 +631,9 @@ class Emulator:
         if self.parameterTrafoPCA_:          # the parameter-space map in front of the GPs (src/emulator.py:492-551)
             for g in self._ppca.groups:
                 arrs += [g.scaler.mean_, g.scaler.scale_, g.pca.mean_, g.pca.components_]
+        if getattr(self, "point_noise_", None) is not None:      # (none: the digests of emulators without simulation_error)
+            h.update(b"point_noise")
+            arrs += [self.point_noise_]
         for a in arrs:
             a = np.ascontiguousarray(a, dtype=np.float64)
             h.update(repr(a.shape).encode()); h.update(a.tobytes())
@@ -612,6 +651,8 @@ class Emulator:
     def __setstate__(self, st):
         self.__dict__.update(st)
         self.__dict__.setdefault("fit_sharding", None)
+        self.__dict__.setdefault("simulation_error_", False)      # (states pickled before stochastic kriging existed)
+        self.__dict__.setdefault("point_noise_", None)
         self._state_serial = next(_STATE_SERIAL)
         if self._trained:
             self.gps = [FittedGP(self, i) for i in range(self._ngp)]
@@ -626,8 +667,12 @@ class Emulator:
         after the other; here the five folds of one train size (same padded size) and all GPs are ONE lock-step batch on the
         device.  The reference refits `self.scaler` / `self.pca` on all events as a side effect; the drop-in works on copies and
         leaves a trained emulator as it is."""
-        S = Standardizer().fit_transform(self.model_data)
-        Z = WhitenedPCA().fit_transform(S)[:, :self.npc]
+        sc, pc = Standardizer(), WhitenedPCA()
+        S = sc.fit_transform(self.model_data)
+        Z = pc.fit_transform(S)[:, :self.npc]
+        # simulation_error: the events' own noise, projected with the curve's scaler and PCA; every fit takes its rows
+        pn = project_errors(self.model_data_err, sc.scale_, pc.components_, pc.explained_variance_, self.npc) \
+            if getattr(self, "simulation_error_", False) else None
         X = np.ascontiguousarray(self.PCA_new_design_points if self.parameterTrafoPCA_ else self.design_points, dtype=np.float64)
         ptp = self.design_max - self.design_min
         d, P, n = ptp.shape[0], Z.shape[1], X.shape[0]
@@ -652,12 +697,12 @@ class Emulator:
             rows = [tr[:m] for tr, _ in folds]
             # the searches of all folds and GPs at this size: virtual GP f * P + i = fold f, GP i
             se = _SearchEngine(self.device, [X[r] for r in rows for _ in range(P)], [Z[r, i] for r in rows for i in range(P)],
-                               "RBF", 0.0)
+                               "RBF", 0.0, 1, None if pn is None else [pn[i, r] for r in rows for i in range(P)])
             thetas, _ = search_hyperparameters(lambda idx: se, nfold * P, theta0, bounds, 0, close=True)
             for f, (r, (_, te)) in enumerate(zip(rows, folds)):
                 eng = GPEngine(self.device)
                 try:
-                    eng.set_data(X[r], Z[r].T, "RBF", 0.0)
+                    eng.set_data(X[r], Z[r].T, "RBF", 0.0, None if pn is None else pn[:, r])
                     eng.set_theta(thetas[f * P:(f + 1) * P])
                     info = np.asarray(eng.factor(raise_on_fail=False))
                     good = np.nonzero(info == 0)[0]
@@ -669,7 +714,7 @@ class Emulator:
                                     np.nonzero(info != 0)[0].tolist(), m, f)
                         train[si, f], test[si, f] = np.nan, np.nan
                         if len(good):
-                            eng.set_data(X[r], Z[r][:, good].T, "RBF", 0.0)
+                            eng.set_data(X[r], Z[r][:, good].T, "RBF", 0.0, None if pn is None else pn[good][:, r])
                             eng.set_theta(thetas[f * P:(f + 1) * P][good])
                             eng.factor()
                     if len(good):
@@ -807,7 +852,20 @@ class Emulator:
                 raise ValueError("propose_design: observable weights must be non-negative")
         return np.ascontiguousarray(u if self.perform_no_PCA_ else (self._A ** 2) @ u)
 
-    def _design_begin(self, cand_dev, ref_dev, w_dev, g):
+    def _design_candidate_noise(self, candidate_error, C):
+        """s_c [ngp, C] of a propose_design call, or None for the training runs' tau: candidate_error [C, nobs] projected like
+        the training errors; None on a simulation_error emulator = every GP's mean training noise at every candidate"""
+        pn = getattr(self, "point_noise_", None)
+        if candidate_error is None:
+            return None if pn is None else np.ascontiguousarray(np.repeat(pn.mean(axis=1)[:, None], C, axis=1))
+        E = np.asarray(candidate_error, dtype=np.float64)
+        if E.shape != (C, self.nobs):
+            raise ValueError("propose_design: candidate_error must be [%d candidates, %d observables], got %s" % (C, self.nobs, E.shape))
+        if not (np.all(np.isfinite(E)) and np.all(E >= 0.0)):
+            raise ValueError("propose_design: candidate_error must be finite and non-negative")
+        return np.ascontiguousarray(self._project_errors(E))
+
+    def _design_begin(self, cand_dev, ref_dev, w_dev, g, candidate_noise=None):
         """This emulator's half of a propose_design call: the points through its parameter map, the design workspace, and
         variance0 = sum_p g_p sum_r w_r s_p(r, r) from the predict path (its variance less the White noise)."""
         eng = self._engine_ready()
@@ -817,11 +875,11 @@ class Emulator:
         noise = np.exp(np.asarray(self.thetas_)[:, -1])
         s_rr = var.cpu().numpy() - noise[None, :]
         variance0 = float(np.dot(w_dev.cpu().numpy() @ s_rr, g))
-        eng.design_begin(cand_dev, ref_dev, w_dev, g)
+        eng.design_begin(cand_dev, ref_dev, w_dev, g, candidate_noise)
         return eng, variance0
 
     def propose_design(self, n_new, candidates, reference=None, weights=None, observable_weights=None, log_observable=False,
-                       return_scores=False):
+                       return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go?  Greedy minimisation of the emulator's posterior variance averaged over
         the reference points, in closed form on the device (gpb_design_begin / gpb_chain_design_run): every step takes the
         candidate whose run would lower sum_m u_m sum_r w_r var[observable m at x_r] the most, then conditions the GPs on it (a
@@ -832,7 +890,11 @@ class Emulator:
         calibration needs them; observable_weights u [nobs] >= 0 (default 1 / scaler.var_ with the output PCA, 1 without).
         With exp_and_cov_diagonal the variance is that of the log-observable (what is linear in the GPs): ValueError unless
         log_observable=True says the caller knows.  Returns a DesignProposal (points, indices, gain, variance0, scores with
-        return_scores).  The hyper-parameters stay those of the fit."""
+        return_scores).  The hyper-parameters stay those of the fit.
+        candidate_error [C, nobs] (optional): the statistical errors the runs at the candidates would have, in model_data_err's
+        units (relative errors under logTrafo), projected like the training errors: candidate c is observed with its own noise
+        (gpb_design_set_noise).  None: on a simulation_error emulator every GP's mean training noise, else the training runs'
+        common noise — exactly the call without the keyword."""
         if not self._trained:
             raise RuntimeError("Emulator is not trained")
         if self.exp_and_cov_diagonal_ and not log_observable:
@@ -846,7 +908,8 @@ class Emulator:
         eng = self._engine_ready()
         try:
             _, variance0 = self._design_begin(torch.as_tensor(cand, device=dev), torch.as_tensor(ref, device=dev),
-                                              torch.as_tensor(w, device=dev), g)
+                                              torch.as_tensor(w, device=dev), g,
+                                              self._design_candidate_noise(candidate_error, cand.shape[0]))
             picks, gain, scores = eng.design_run(n_new, None, return_scores)
         finally:
             eng.design_end()
@@ -972,6 +1035,18 @@ class Emulator:
         return self._holdout(nTestPoints, on_training=True, thetas=thetas)
 
 
+def project_errors(E, scale, components=None, explained_variance=None, npc=None):
+    """Variances s [ngp, n] of the GPs' targets from independent statistical errors E [n, nobs] of the observables (stochastic
+    kriging's per-point noise).  With the whitened output PCA (rows `components`, `explained_variance`, the first npc kept):
+    s[k, i] = sum_m (E[i, m] / scale[m])^2 components[k, m]^2 / explained_variance[k] — the variance of the whitened PC k; without
+    (components None): s[m, i] = (E[i, m] / scale[m])^2."""
+    V = (np.asarray(E, dtype=np.float64) / np.asarray(scale, dtype=np.float64)) ** 2
+    if components is None:
+        return np.ascontiguousarray(V.T)
+    comp, ev = np.asarray(components, dtype=np.float64)[:npc], np.asarray(explained_variance, dtype=np.float64)[:npc]
+    return np.ascontiguousarray((comp ** 2 @ V.T) / ev[:, None])
+
+
 def rms_relative_error(pred, truth):
     """per observable: sqrt(mean over the validation points of ((pred - truth) / truth)^2) — the emulator's relative error as
     examples/EmulatorValidation.ipynb tabulates it; pred, truth [n, nobs] -> [nobs]"""
@@ -1031,7 +1106,10 @@ def train_emulators(emulators, eventMasks=None, kernel_type="RBF"):
                 emu = emulators[i]
                 results[i] = emu._optimise_with_points(kernel_type, t0b[i], draws[i])
             continue
-        Xs, Zs, start, bnd, owner = [], [], [], [], []
+        # per-point noise: every virtual GP carries its own row (zeros for an emulator without simulation_error next to one with:
+        # alpha + 0 gives the scalar's bits), so the group key stays valid
+        noisy = any(emulators[i]._noise_rows() is not None for i in members)
+        Xs, Zs, Ss, start, bnd, owner = [], [], [], [], [], []
         for s_ in range(smax):                       # virtual GPs start-major: the first block is every GP's theta0 start
             for i in members:
                 emu = emulators[i]
@@ -1039,11 +1117,13 @@ def train_emulators(emulators, eventMasks=None, kernel_type="RBF"):
                     continue
                 for g in range(emu._ngp):
                     Xs.append(emu._X_train); Zs.append(emu._Z_train[g])
+                    if noisy:
+                        Ss.append(emu.point_noise_[g] if emu._noise_rows() is not None else np.zeros(emu._X_train.shape[0]))
                     start.append(t0b[i][0] if s_ == 0 else draws[i][g, s_ - 1])
                     bnd.append(t0b[i][1]); owner.append((i, g, s_))
         eng = GPEngine(emulators[members[0]].device)
         try:
-            eng.set_data_multi(Xs, Zs, kern, float(emulators[members[0]].alpha))
+            eng.set_data_multi(Xs, Zs, kern, float(emulators[members[0]].alpha), Ss if noisy else None)
             th, val = _batched_lbfgsb(eng, np.array(start), np.array(bnd))
         finally:
             eng.close()
@@ -1113,11 +1193,12 @@ class _SearchEngine:
     targets of GP i — of one emulator or of several — each stored `copies` times (the starts of its search).  `.lml(theta[V])`
     evaluates all V = copies x n virtual GPs, `.lml_active(idx, theta)` the ones still searching."""
 
-    def __init__(self, device, Xs, Zs, kernel, alpha, copies=1):
+    def __init__(self, device, Xs, Zs, kernel, alpha, copies=1, point_noise=None):
         self.n = len(Xs)
         self.copies = int(copies)
         self.eng = GPEngine(device)
-        self.eng.set_data_multi(list(Xs) * self.copies, list(Zs) * self.copies, kernel, alpha)
+        self.eng.set_data_multi(list(Xs) * self.copies, list(Zs) * self.copies, kernel, alpha,
+                                None if point_noise is None else list(point_noise) * self.copies)
 
     def restart_batch(self, copies):
         assert copies == self.copies

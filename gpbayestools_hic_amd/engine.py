@@ -173,8 +173,29 @@ class GPEngine:
         return torch.as_tensor(es, device=torch.device("cuda", self.device))
 
     # ------------------------------------------------------------------ GP state
-    def set_data(self, X, Z, kernel="RBF", alpha=0.1):
-        """X[N,d] design, Z[P,N] targets (one row per GP)."""
+    def set_point_noise(self, point_noise):
+        """Per-point simulation noise of the training diagonal (gpb_gp_set_point_noise, stochastic kriging): one row of
+        variances >= 0 per GP — [P, N] for set_data, a list of P arrays [N_p] for set_data_multi — or None for none.  The
+        diagonal of GP p becomes c + sigma_n^2 + (alpha + s[p, i]); the context is left without a factorisation.  ValueError for a
+        wrong shape; GPBError (GPB_E_ARG) for a negative or non-finite entry, the context stays as it was."""
+        self._check_pid()
+        if point_noise is None:
+            self._ck(self.lib.gpb_gp_set_point_noise(self.h, None))
+            return
+        import ctypes
+        rows = [nat.f64(r).reshape(-1) for r in point_noise]
+        if len(rows) != self.P:
+            raise ValueError("point_noise: %d rows for %d GPs" % (len(rows), self.P))
+        Ns = getattr(self, "_Ns", None)
+        for p, r in enumerate(rows):
+            want = self.N if Ns is None else int(Ns[p])
+            if r.shape[0] != want:
+                raise ValueError("point_noise: row %d has %d entries for %d design points" % (p, r.shape[0], want))
+        sp = (ctypes.c_void_p * self.P)(*[r.ctypes.data for r in rows])
+        self._ck(self.lib.gpb_gp_set_point_noise(self.h, sp))
+
+    def set_data(self, X, Z, kernel="RBF", alpha=0.1, point_noise=None):
+        """X[N,d] design, Z[P,N] targets (one row per GP); point_noise [P,N] (optional): see set_point_noise."""
         self._check_pid()
         X, Z = nat.f64(X), nat.f64(Z)
         self.N, self.d = X.shape
@@ -183,10 +204,14 @@ class GPEngine:
         kid = KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
         self.M, self.pmap_d_in, self.pmap_d_out = 0, -1, -1       # gpb_gp_set drops the transform, likelihood and map
         self._ck(self.lib.gpb_gp_set(self.h, self.N, self.d, self.P, nat.ptr(X), nat.ptr(Z), kid, float(alpha)))
+        self._Ns = None
+        if point_noise is not None:
+            self.set_point_noise(point_noise)
 
-    def set_data_multi(self, Xs, Zs, kernel="RBF", alpha=0.1):
+    def set_data_multi(self, Xs, Zs, kernel="RBF", alpha=0.1, point_noise=None):
         """P GPs, each over its own design: Xs[p] [N_p, d], Zs[p] [N_p] (gpb_gp_set_multi: the GPs of several emulators or
-        the restarts of a search side by side; the designs must pad to the same multiple of 64 points).  Fit-only."""
+        the restarts of a search side by side; the designs must pad to the same multiple of 64 points).  Fit-only.
+        point_noise (optional): a list of P arrays [N_p], see set_point_noise."""
         self._check_pid()
         import ctypes
         Xs = [nat.f64(x) for x in Xs]
@@ -203,6 +228,9 @@ class GPEngine:
         xp = (ctypes.c_void_p * self.P)(*[x.ctypes.data for x in Xs])
         zp = (ctypes.c_void_p * self.P)(*[z.ctypes.data for z in Zs])
         self._ck(self.lib.gpb_gp_set_multi(self.h, self.P, self.d, nat.ptr(Ns), xp, zp, kid, float(alpha)))
+        self._Ns = Ns
+        if point_noise is not None:
+            self.set_point_noise(point_noise)
 
     def lml_subset(self, idx, theta, eval_gradient=True):
         """LML (and gradient) of the stored GPs `idx` at theta[len(idx), d+2] in one launch sequence (gpb_gp_lml_subset);
@@ -410,10 +438,11 @@ class GPEngine:
         return curve
 
     # ------------------------------------------------------------------ variance-reduction sequential design
-    def design_begin(self, candidates, reference, weights, g):
+    def design_begin(self, candidates, reference, weights, g, candidate_noise=None):
         """Build the design workspace (gpb_design_begin): candidates [C, d], reference [R, d] and weights [R] (>= 0, sum 1) are
         torch cuda tensors in the GPs' input space (behind param_map for a parameterTrafoPCA emulator), g [P] the GPs' weights
-        (host).  For every GP: S_rc = c k(x_r, x_c) - V_r^T V_c and s(c, c).  Overwrites the predict workspace; asynchronous."""
+        (host).  For every GP: S_rc = c k(x_r, x_c) - V_r^T V_c and s(c, c).  Overwrites the predict workspace; asynchronous.
+        candidate_noise [P, C] (optional, host or torch cuda): see design_set_noise."""
         self._need_data()
         Xc = self._check_cols(candidates, "candidates")
         Xr = self._check_cols(reference, "reference")
@@ -423,7 +452,29 @@ class GPEngine:
             raise ValueError("design_begin: g needs one weight per GP (%d), got %d" % (self.P, g.shape[0]))
         self._ck(self.lib.gpb_design_begin(self.h, nat.ptr(Xc), Xc.shape[0], nat.ptr(Xr), Xr.shape[0], nat.ptr(w), nat.ptr(g)))
         self._design_C = int(Xc.shape[0])
+        if candidate_noise is not None:
+            self.design_set_noise(candidate_noise)
 
+    def design_set_noise(self, candidate_noise):
+        """The candidates' own simulation noise (gpb_design_set_noise, between design_begin and design_run): candidate_noise
+        [P, C] variances >= 0 in the GPs' target units, numpy or a torch cuda tensor; candidate c is then observed with
+        tau_p(c) = sigma_n^2 + (alpha + s_c[p, c]).  None: back to the training runs' tau_p.  ValueError for a wrong shape or a
+        negative / non-finite entry."""
+        self._need_data()
+        if candidate_noise is None:
+            self._ck(self.lib.gpb_design_set_noise(self.h, None))
+            return
+        import torch
+        C = int(getattr(self, "_design_C", 0))
+        if C < 1:
+            self._ck(self.lib.gpb_design_set_noise(self.h, None))   # (no workspace: the library's GPB_E_STATE and its message)
+            return
+        if not _is_torch(candidate_noise):
+            candidate_noise = torch.as_tensor(nat.f64(candidate_noise), device=torch.device("cuda", self.device))
+        sc = self._dev(candidate_noise, (self.P, C), "candidate_noise")
+        if not bool(torch.all(torch.isfinite(sc) & (sc >= 0.0))):
+            raise ValueError("design_set_noise: candidate_noise must be finite and non-negative")
+        self._ck(self.lib.gpb_design_set_noise(self.h, nat.ptr(sc)))
     def design_run(self, n_picks, eligible=None, return_scores=False):
         """The greedy loop over this engine alone (the E = 1 chain call): see design_run() of this module."""
         return design_run([self], n_picks, eligible, return_scores)

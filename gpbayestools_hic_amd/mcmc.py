@@ -360,7 +360,7 @@ class Chain:
         return SobolIndices(*[np.concatenate([getattr(r, k) for r in parts], axis=0)
                               for k in ("mean", "variance", "first_order", "total")], names=list(self.pardict))
 
-    def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False):
+    def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a
         candidate is the sum of the emulators' scores in emuList order, each emulator seeing the points through its own
@@ -368,6 +368,8 @@ class Chain:
 
         candidates [C, ndim]; those outside the open prior box are never picked.  reference [R, ndim] (default: the candidates)
         is typically a set of posterior samples, weights [R] their weights (default uniform).  Returns a DesignProposal.
+        candidate_error [C, nobs of all emulators] (optional): the candidates' statistical errors, its columns split per emulator
+        in emuList order (Emulator.propose_design); None: each emulator's own default.
         NotImplementedError for foreign emulators and for exp_and_cov_diagonal emulators (their design variance is that of the
         log-observable, which the experimental variance does not measure)."""
         from .emulator import DesignProposal, _design_inputs
@@ -390,11 +392,18 @@ class Chain:
         dev = torch.device("cuda", self.device)
         cand_dev, ref_dev, w_dev = (torch.as_tensor(a, device=dev) for a in (cand, ref, w))
         eligible = torch.as_tensor(inside.astype(np.uint8), device=dev)
+        if candidate_error is not None:
+            candidate_error = np.asarray(candidate_error, dtype=np.float64)
+            if candidate_error.shape != (cand.shape[0], u.shape[0]):
+                raise ValueError("propose_design: candidate_error must be [%d candidates, %d observables], got %s"
+                                 % (cand.shape[0], u.shape[0], candidate_error.shape))
         engs, variance0, i0 = [], 0.0, 0
         try:
             for emu in self.emuList:
                 engs.append(emu._engine_ready())
-                _, v0 = emu._design_begin(cand_dev, ref_dev, w_dev, emu._design_gp_weights(u[i0:i0 + emu.nobs]))
+                ce = None if candidate_error is None else candidate_error[:, i0:i0 + emu.nobs]
+                _, v0 = emu._design_begin(cand_dev, ref_dev, w_dev, emu._design_gp_weights(u[i0:i0 + emu.nobs]),
+                                          emu._design_candidate_noise(ce, cand.shape[0]))
                 variance0 += v0
                 i0 += emu.nobs
             picks, gain, scores = design_run(engs, n_new, eligible, return_scores)

@@ -106,6 +106,21 @@ GPB_API int gpb_gp_set(gpb_ctx* ctx, int64_t N, int64_t d, int64_t P,
 GPB_API int gpb_gp_set_multi(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_host /*[P]*/,
                      const double* const* X_host /*[P] pointers to [N_p,d]*/,
                      const double* const* Z_host /*[P] pointers to [N_p]*/, int kernel_id, double alpha);
+/* gpb_gp_set_point_noise <- GPR(kernel, alpha=<array of length N>): a known variance per training point on the diagonal of K
+ * (sk:_gpr.py:347, `K[np.diag_indices_from(K)] += self.alpha` with an array) — stochastic kriging, the GP core of the reference's
+ * EmulatorBAND(method='PCSK'), which hands the training events' statistical errors to surmise as `simsd`; NOT a port of surmise's PCSK.
+ * s_host: P pointers to the N_p variances s[p][i] >= 0 of stored GP p, or NULL for none (what gpb_gp_set / gpb_gp_set_multi leave,
+ * both of which reset the context to none).  The training diagonal of GP p becomes c + sigma_n^2 + (alpha + s[p][i]); the sum
+ * alpha + s is formed first, so that s = 0 gives the bits of no call, a uniform s = s0 those of the scalar alpha' = fl(alpha + s0),
+ * and sklearn's / the oracle's vector alpha_i = alpha + s_i the same diagonal.  The White level stays a hyper-parameter: the
+ * homoscedastic remainder.  Valid on gpb_gp_set and gpb_gp_set_multi contexts; call it after either and before the next
+ * gpb_gp_factor / gpb_gp_lml / gpb_gp_lml_subset (whose subsets and whose restart copies read their own GP's row).  Leaves the
+ * context without a factorisation, as gpb_gp_lml_subset does.  Read by the K assembly, gpb_gp_cv / gpb_emu_cv (cov = G_F^-1 -
+ * diag(alpha + s_F)) and nothing else: as in sklearn the per-point term is on the TRAINING diagonal only — the predictive prior
+ * c + sigma_n^2, gpb_gp_predict / _cov / _grad, the Sobol indices and the likelihood kernels read L^-1 and alpha_ and are untouched.
+ * Errors: GPB_E_STATE before gpb_gp_set; GPB_E_ARG for a null row or a negative or non-finite entry (nothing is changed then: the
+ * context stays as it was). */
+GPB_API int gpb_gp_set_point_noise(gpb_ctx* ctx, const double* const* s_host /*[P] pointers to [N_p], or NULL: none*/);
 GPB_API int gpb_gp_lml_subset(gpb_ctx* ctx, int64_t n, const int32_t* gp_index /*[n]*/, const double* theta_host /*[n,d+2]*/,
                       double* lml_host /*[n]*/, double* grad_host /*[n,d+2] or NULL*/, int* info_host /*[n] or NULL*/);
 GPB_API int gpb_gp_set_theta(gpb_ctx* ctx, const double* theta_host /*[P,d+2]*/);
@@ -242,14 +257,22 @@ GPB_API int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host /*[d]*/, con
  *   eligible candidates the remaining picks are -1 and their gain NaN.  A run conditions the workspace in place: another run
  *   needs another gpb_design_begin.  No floating-point atomics; every sum in an order fixed by the padded shapes alone — equal
  *   inputs give equal bits, and step-0 scores do not depend on T; no [C, C] matrix is formed.
+ * gpb_design_set_noise (optional, between gpb_design_begin and gpb_chain_design_run): candidate c is observed with its own
+ *   tau_p(c) = sigma_n^2 + (alpha + s_c[p][c]) in J's denominator and in the rank-one conditioning — a candidate run with larger
+ *   statistical errors teaches less (the design counterpart of gpb_gp_set_point_noise; sklearn has none).  s_c_dev [P, C]: device
+ *   array of variances >= 0 in GP p's target units (copied; the caller checks its values: a negative or NaN entry gives that
+ *   candidate a meaningless score, nothing worse), NULL: back to tau_p.  Not called: tau_p, the same bits as before; a zero array
+ *   gives those bits too (alpha + 0 first).  gpb_design_begin resets it.
  * gpb_design_end releases the workspace (synchronises the stream).
  * Errors: GPB_E_STATE without a factorisation, on a gpb_gp_set_multi context, for a run before begin (or after a new
  * factorisation, or a second run), for contexts begun with different C or R; GPB_E_ARG for C, R or T < 1, C or R > 8192, T > C,
- * a negative g, more than 32 contexts, contexts on different streams.  The factorisation and alpha are untouched.  The predict
+ * a negative g, more than 32 contexts, contexts on different streams; gpb_design_set_noise: GPB_E_STATE before gpb_design_begin or
+ * after the run that consumed it.  The factorisation and alpha are untouched.  The predict
  * workspace does NOT survive gpb_design_begin: it holds the reference points' K*^T afterwards and may have been re-allocated;
  * later predict / likelihood calls recompute it and return what they would have returned before. */
 GPB_API int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev /*[C,d]*/, int64_t C, const double* Xr_dev /*[R,d]*/, int64_t R,
                      const double* w_dev /*[R]*/, const double* g_host /*[P]*/);
+GPB_API int gpb_design_set_noise(gpb_ctx* ctx, const double* s_c_dev /*[P,C] or NULL*/);
 GPB_API int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint8_t* eligible_dev /*[C] or NULL*/,
                          int32_t* picks_dev /*[T]*/, double* gain_dev /*[T]*/, double* scores_dev /*[T,C] or NULL*/);
 GPB_API int gpb_design_end(gpb_ctx* ctx);
