@@ -14,30 +14,13 @@ using namespace gpb;
 
 namespace {
 
-// (through the buffer cache of gpb_pool.hip: contexts come and go with every training)
-template <typename T>
-int dev_alloc(gpb_ctx* ctx, T** p, int64_t count) {
-    if (*p) {        // a buffer that is replaced goes back to the cache: nothing may still be using it (callers have synchronised
-        if (ctx->side_stream) GPB_HIP(hipStreamSynchronize(ctx->side_stream));      // ctx->stream; the look-ahead stream here)
-        pool_free(*p); *p = nullptr;
-    }
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(p), sizeof(T) * (size_t)(count > 0 ? count : 1)));
-    return 0;
-}
-template <typename T>
-void dev_free(T** p) {
-    if (*p) { pool_free(*p); *p = nullptr; }
-}
-
 int pick_dpad(int64_t d) {
     const int opts[] = {8, 16, 20, 24, 32, 48, 64};     // 20: the reference's analyses have 17-20 model parameters
     for (int o : opts) if (d <= o) return o;
     return -1;
 }
 
-int ensure_out(gpb_ctx* ctx, int64_t count) {
-    return pool_grow(ctx, &ctx->out_stage, &ctx->out_cap, count);
-}
+int ensure_out(gpb_ctx* ctx, int64_t count) { return ctx_grow(ctx, ctx->out_stage, count); }
 
 // [P][Wld] -> [W][P]
 __global__ void k_transpose_pw(const double* __restrict__ src, double* __restrict__ dst, int64_t W, int64_t Wld,
@@ -98,15 +81,15 @@ extern "C" int gpb_ctx_create(int device, void* stream, gpb_ctx** out) {
         }
         ctx->own_stream = true;
     }
-    if (pool_malloc_t(&ctx->notpd, sizeof(int)) != hipSuccess ||
+    if (ctx->notpd.alloc(1) != hipSuccess ||
         hipMemsetAsync(ctx->notpd, 0, sizeof(int), ctx->stream) != hipSuccess ||
-        pool_malloc_t(&ctx->rows_live, sizeof(unsigned long long)) != hipSuccess ||
+        ctx->rows_live.alloc(1) != hipSuccess ||
         hipMemsetAsync(ctx->rows_live, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess ||
-        pool_malloc_t(&ctx->n_nan, sizeof(long long)) != hipSuccess ||
+        ctx->n_nan.alloc(1) != hipSuccess ||
         hipMemsetAsync(ctx->n_nan, 0, sizeof(long long), ctx->stream) != hipSuccess ||
-        pool_malloc_t(&ctx->tile_counter, 129 * sizeof(unsigned)) != hipSuccess ||
+        ctx->tile_counter.alloc(129) != hipSuccess ||
         hipMemsetAsync(ctx->tile_counter, 0, 129 * sizeof(unsigned), ctx->stream) != hipSuccess) {
-        delete ctx;
+        gpb_ctx_destroy(ctx);       // (after synchronising the stream: a memset may be in flight on a buffer it gives back)
         return GPB_E_ALLOC;
     }
     // optional: without it the tile rule sizes compacted batches by their upper bound
@@ -129,28 +112,13 @@ extern "C" int gpb_ctx_destroy(gpb_ctx* ctx) {
     // (the look-ahead stream of the factorisation reads and writes K and L^-1: gpb_chol.hip)
     if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
     gpb_dist_finalize(ctx);
-    free(ctx->h_theta);
-    dev_free(&ctx->lr_R); dev_free(&ctx->lr_v0); dev_free(&ctx->lr_blocks);
-    dev_free(&ctx->xmean); dev_free(&ctx->muS); dev_free(&ctx->Xc); dev_free(&ctx->dnorm); dev_free(&ctx->kmtiles); dev_free(&ctx->gpN);
-    dev_free(&ctx->X); dev_free(&ctx->Xsc); dev_free(&ctx->thblk);
-    ctx->ls = ctx->amp = ctx->noise = nullptr; ctx->gpform = ctx->gpmap = nullptr;         // (carved out of thblk)
     if (ctx->h_thblk) (void)hipHostFree(ctx->h_thblk);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    dev_free(&ctx->Z); dev_free(&ctx->pnoise); dev_free(&ctx->K); dev_free(&ctx->Linv); dev_free(&ctx->T); dev_free(&ctx->yv);
-    gpb::sliced_free(ctx);
-    dev_free(&ctx->alpha); dev_free(&ctx->apart); dev_free(&ctx->info); dev_free(&ctx->lmlbuf);
-    dev_free(&ctx->gpart); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->KsT); dev_free(&ctx->mpart);
-    dev_free(&ctx->spart); dev_free(&ctx->mean_pc); dev_free(&ctx->var_pc); dev_free(&ctx->out_stage);
-    dev_free(&ctx->vbuf); dev_free(&ctx->gbuf); dev_free(&ctx->covbuf); dev_free(&ctx->cv_ws); dev_free(&ctx->sobol_ws); dev_free(&ctx->design_ws); dev_free(&ctx->design_run); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
-    dev_free(&ctx->tile_trace);
-    dev_free(&ctx->A); dev_free(&ctx->mu); dev_free(&ctx->scale); dev_free(&ctx->C0); dev_free(&ctx->yexp);
-    dev_free(&ctx->Cexp); dev_free(&ctx->mvn_ws); dev_free(&ctx->notpd); dev_free(&ctx->tile_counter);
-    dev_free(&ctx->n_nan); dev_free(&ctx->mc_ws); dev_free(&ctx->ptl_ws); dev_free(&ctx->smc_ws); dev_free(&ctx->bal_ws); dev_free(&ctx->rows_live); dev_free(&ctx->cmp_idx); dev_free(&ctx->cmp_X);
     if (ctx->live_hint) (void)hipHostFree(ctx->live_hint);
     for (hipEvent_t e : ctx->chol_events) (void)hipEventDestroy(e);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;        // every DevBuf member goes back to the buffer cache here: the streams that used them are idle
     return 0;
 }
 
@@ -188,34 +156,36 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     for (int64_t p = 0; p < P; ++p) N = N_p[p] > N ? N_p[p] : N;
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->N = N; ctx->d = d; ctx->P = ctx->Pstore = P; ctx->dpad = dpad; ctx->kind = kernel_id; ctx->alpha_reg = alpha;
+    if (ctx->side_stream) GPB_HIP(hipStreamSynchronize(ctx->side_stream));
+    ctx->N = 0;        // no GPs until the last buffer is in place and filled (the rule of ctx_replace): raised at the end
+    ctx->d = d; ctx->P = ctx->Pstore = P; ctx->dpad = dpad; ctx->kind = kernel_id; ctx->alpha_reg = alpha;
     ctx->multi = multi; ctx->subset = false;
     ctx->Np = round_up(N, NB);
     ctx->have_theta = ctx->factored = ctx->design_ready = false;
-    dev_free(&ctx->pnoise);                            // the new GPs start without per-point noise (gpb_gp_set_point_noise)
+    ctx->pnoise.release();                            // the new GPs start without per-point noise (gpb_gp_set_point_noise)
     // whatever was installed for the previous GPs (observable transform sized [old P][M], likelihood block, low-rank
     // factors, parameter map) does not describe the new ones: it has to be set again
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
     ctx->M = 0;
-    dev_free(&ctx->A); dev_free(&ctx->mu); dev_free(&ctx->scale); dev_free(&ctx->C0); dev_free(&ctx->yexp);
-    dev_free(&ctx->Cexp); dev_free(&ctx->lr_R); dev_free(&ctx->lr_v0); dev_free(&ctx->pmap_int); dev_free(&ctx->pmap_tab);
+    ctx->A.release(); ctx->mu.release(); ctx->scale.release(); ctx->C0.release(); ctx->yexp.release();
+    ctx->Cexp.release(); ctx->lr_R.release(); ctx->lr_v0.release(); ctx->pmap_int.release(); ctx->pmap_tab.release();
     ctx->h_A.clear(); ctx->h_mu.clear(); ctx->h_C0.clear();
     ctx->pmap_d_in = ctx->pmap_d_out = 0; ctx->pmap_groups = ctx->pmap_maxpc = 0;
     const int64_t Np = ctx->Np, PX = multi ? P : 1;
     // workspaces sized by (Np, P) are stale now
-    dev_free(&ctx->KsT); dev_free(&ctx->mpart); dev_free(&ctx->spart); dev_free(&ctx->mean_pc);
-    dev_free(&ctx->var_pc); dev_free(&ctx->Xs); dev_free(&ctx->estd); dev_free(&ctx->cmp_idx); dev_free(&ctx->cmp_X);
-    ctx->Wcap = 0; ctx->cmp_X_cap = 0; ctx->last_W = 0;
+    ctx->KsT.release(); ctx->mpart.release(); ctx->spart.release(); ctx->mean_pc.release();
+    ctx->var_pc.release(); ctx->Xs.release(); ctx->estd.release(); ctx->cmp_idx.release(); ctx->cmp_X.release();
+    ctx->Wcap = 0; ctx->last_W = 0;
     int rc;
-    if ((rc = dev_alloc(ctx, &ctx->X, PX * Np * dpad))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->Xsc, P * Np * dpad))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->xmean, PX * dpad))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->muS, P * dpad))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->Xc, P * Np * dpad))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->dnorm, P * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->X, PX * Np * dpad))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->Xsc, P * Np * dpad))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->xmean, PX * dpad))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->muS, P * dpad))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->Xc, P * Np * dpad))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->dnorm, P * Np))) return rc;
     {   // one block: [ls P x dpad | amp P | noise P] doubles, then [gpform P | gpmap P] ints; its page-locked twin on the host
         const size_t nd = (size_t)(P * dpad + 2 * P), bytes = sizeof(double) * nd + sizeof(int) * 2 * (size_t)P;
-        if ((rc = dev_alloc(ctx, &ctx->thblk, (int64_t)((bytes + 7) / 8)))) return rc;
+        if ((rc = ctx_replace(ctx, ctx->thblk, (int64_t)((bytes + 7) / 8)))) return rc;
         ctx->ls = ctx->thblk; ctx->amp = ctx->ls + P * dpad; ctx->noise = ctx->amp + P;
         ctx->gpform = reinterpret_cast<int*>(ctx->noise + P); ctx->gpmap = ctx->gpform + P;
         if (ctx->h_thblk) { (void)hipHostFree(ctx->h_thblk); ctx->h_thblk = nullptr; }
@@ -226,23 +196,22 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
         memset(ctx->h_thblk, 0, bytes);
         ctx->thblk_bytes = bytes;
     }
-    if ((rc = dev_alloc(ctx, &ctx->Z, P * Np))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->K, P * Np * Np))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->Linv, P * Np * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->Z, P * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->K, P * Np * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->Linv, P * Np * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->T, P * Np * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->yv, P * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->alpha, P * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->info, P))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->lmlbuf, P * 4 + P * (d + 2)))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->gpN, P))) return rc;
+    const int64_t nb64 = ctx->Np / 64;
+    if ((rc = ctx_replace(ctx, ctx->kmtiles, nb64 * (nb64 + 1)))) return rc;
     gpb::sliced_free(ctx);                             // the digit planes follow the new shape on their next use
     // zeroed ONCE: the factorisation writes the diagonal blocks (with zeros above the diagonal) and the blocks below
     // them, never the blocks above — and the 128-wide tiles of the predict / K^-1 products read those as zeros
     GPB_HIP(hipMemsetAsync(ctx->Linv, 0, sizeof(double) * P * Np * Np, ctx->stream));
-    if ((rc = dev_alloc(ctx, &ctx->T, P * Np * Np))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->yv, P * Np))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->alpha, P * Np))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->info, P))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->lmlbuf, P * 4 + P * (d + 2)))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->gpN, P))) return rc;
-    const int64_t nb64 = ctx->Np / 64;
-    if ((rc = dev_alloc(ctx, &ctx->kmtiles, nb64 * (nb64 + 1)))) return rc;
-    free(ctx->h_theta);
-    ctx->h_theta = (double*)calloc((size_t)(P * (d + 2)), sizeof(double));
+    ctx->h_theta.assign((size_t)(P * (d + 2)), 0.0);
     std::vector<double> xp((size_t)(PX * Np * dpad), 0.0), zp((size_t)(P * Np), 0.0), xm((size_t)(PX * dpad), 0.0);
     ctx->h_ext.assign((size_t)(PX * d), 0.0);
     ctx->h_N.assign((size_t)P, 0);
@@ -290,6 +259,7 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     GPB_HIP(hipMemcpy(ctx->xmean, xm.data(), sizeof(double) * xm.size(), hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->X, xp.data(), sizeof(double) * xp.size(), hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->Z, zp.data(), sizeof(double) * zp.size(), hipMemcpyHostToDevice));
+    ctx->N = N;
     return 0;
 }
 
@@ -338,11 +308,11 @@ extern "C" int gpb_gp_set_point_noise(gpb_ctx* ctx, const double* const* s_host)
     GPB_HIP(hipStreamSynchronize(ctx->stream));        // nothing enqueued still reads the array that is replaced
     ctx->factored = ctx->design_ready = false;         // the resident factorisation is of another diagonal
     if (!s_host) {
-        dev_free(&ctx->pnoise);
+        ctx->pnoise.release();
         return 0;
     }
     int rc;
-    if ((rc = dev_alloc(ctx, &ctx->pnoise, P * Np))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->pnoise, P * Np))) return rc;
     std::vector<double> sp((size_t)(P * Np), 0.0);
     for (int64_t p = 0; p < P; ++p) {
         const int64_t Nq = ctx->multi ? (int64_t)ctx->h_N[(size_t)p] : ctx->N, pad = pad_front(Np, Nq);
@@ -362,7 +332,7 @@ int gpb::choose_forms(gpb_ctx* ctx, bool upload) {
     const int64_t P = ctx->P, d = ctx->d;
     int ndiff = 0;
     for (int64_t p = 0; p < P; ++p) {
-        const double* th = ctx->h_theta + p * (d + 2);
+        const double* th = ctx->h_theta.data() + p * (d + 2);
         const int64_t gq = ctx->multi ? (ctx->subset ? ctx->h_map[(size_t)p] : p) : 0;      // whose design
         double S = 0.0;
         for (int64_t k = 0; k < d; ++k) {
@@ -387,7 +357,7 @@ extern "C" int gpb_gp_set_theta(gpb_ctx* ctx, const double* theta_host) {
     const int64_t P = ctx->P, d = ctx->d, dpad = ctx->dpad;
     for (int64_t i = 0; i < P * (d + 2); ++i)
         if (!isfinite(theta_host[i])) GPB_FAIL(GPB_E_ARG, "gpb_gp_set_theta: non-finite theta");
-    memcpy(ctx->h_theta, theta_host, sizeof(double) * P * (d + 2));
+    memcpy(ctx->h_theta.data(), theta_host, sizeof(double) * P * (d + 2));
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));     // the previous block's copy out of the page-locked twin is done
     int rc = choose_forms(ctx, false);
@@ -650,18 +620,18 @@ extern "C" int gpb_emu_set_transform(gpb_ctx* ctx, int mode, int64_t M, const do
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t P = ctx->P;
+    ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
     int rc;
-    if ((rc = dev_alloc(ctx, &ctx->A, P * M))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->mu, M))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->scale, M))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->C0, M * M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->A, P * M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->mu, M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->scale, M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->C0, M * M))) return rc;
     std::vector<double> zeros((size_t)(M * M > P * M ? M * M : P * M), 0.0), ones((size_t)M, 1.0);
     GPB_HIP(hipMemcpy(ctx->A, A_host ? A_host : zeros.data(), sizeof(double) * P * M, hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->mu, mu_host, sizeof(double) * M, hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->scale, scale_host ? scale_host : ones.data(), sizeof(double) * M, hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->C0, cov_trunc_host ? cov_trunc_host : zeros.data(), sizeof(double) * M * M, hipMemcpyHostToDevice));
-    ctx->mode = mode; ctx->M = M; ctx->have_transform = true; ctx->have_like = false;
-    ctx->lr_ok = false;
+    ctx->mode = mode; ctx->M = M; ctx->have_transform = true;
     ctx->h_A.assign(A_host ? A_host : zeros.data(), (A_host ? A_host : zeros.data()) + P * M);
     ctx->h_mu.assign(mu_host, mu_host + M);
     ctx->h_C0.assign(cov_trunc_host ? cov_trunc_host : zeros.data(), (cov_trunc_host ? cov_trunc_host : zeros.data()) + M * M);
@@ -750,7 +720,7 @@ static bool lowrank_setup(gpb_ctx* ctx, const double* yexp, const double* cexp) 
         vh[i] = (double)v0[i];
         for (int64_t j = i; j < P; ++j) Rh[i * 16 + j] = (double)R[i * P + j];
     }
-    if (dev_alloc(ctx, &ctx->lr_R, 256) || dev_alloc(ctx, &ctx->lr_v0, 16)) return false;
+    if (ctx_replace(ctx, ctx->lr_R, 256) || ctx_replace(ctx, ctx->lr_v0, 16)) return false;
     if (hipMemcpy(ctx->lr_R, Rh, sizeof(Rh), hipMemcpyHostToDevice) != hipSuccess) return false;
     if (hipMemcpy(ctx->lr_v0, vh, sizeof(vh), hipMemcpyHostToDevice) != hipSuccess) return false;
     ctx->lr_cperp = (double)cperp;
@@ -896,9 +866,10 @@ extern "C" int gpb_like_set(gpb_ctx* ctx, const double* yexp_host, const double*
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t M = ctx->M;
+    ctx->have_like = ctx->lr_ok = false;
     int rc;
-    if ((rc = dev_alloc(ctx, &ctx->yexp, M))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->Cexp, M * M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->yexp, M))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->Cexp, M * M))) return rc;
     GPB_HIP(hipMemcpy(ctx->yexp, yexp_host, sizeof(double) * M, hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->Cexp, cov_exp_host, sizeof(double) * M * M, hipMemcpyHostToDevice));
     ctx->lr_ok = lowrank_setup(ctx, yexp_host, cov_exp_host);
@@ -1179,18 +1150,15 @@ extern "C" int gpb_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, cons
     if (!ctx || !A_host || !B_host || !C_host) return GPB_E_ARG;
     if (M < 2 || N < 2 || K < 16 || (K % 16) || (M % 2) || (N % 2)) GPB_FAIL(GPB_E_ARG, "gpb_test_gemm: K%16, M%2, N%2");
     GPB_HIP(hipSetDevice(ctx->device));
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-    GPB_HIP(hipMalloc(&dA, sizeof(double) * M * K));
-    GPB_HIP(hipMalloc(&dB, sizeof(double) * K * N));
-    GPB_HIP(hipMalloc(&dC, sizeof(double) * M * N));
+    DevBuf<double> dA, dB, dC;
+    GPB_HIP(dA.alloc(M * K));
+    GPB_HIP(dB.alloc(K * N));
+    GPB_HIP(dC.alloc(M * N));
     GPB_HIP(hipMemcpy(dA, A_host, sizeof(double) * M * K, hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(dB, B_host, sizeof(double) * K * N, hipMemcpyHostToDevice));
-    int rc = launch_test_gemm(ctx, M, N, K, dA, dB, dC, b_trans);
-    if (rc == 0) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-        GPB_HIP(hipMemcpy(C_host, dC, sizeof(double) * M * N, hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
+    const int rc = launch_test_gemm(ctx, M, N, K, dA, dB, dC, b_trans);
+    GPB_HIP(hipStreamSynchronize(ctx->stream));        // (also: before the three buffers go back to the cache)
+    if (rc == 0) GPB_HIP(hipMemcpy(C_host, dC, sizeof(double) * M * N, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1329,10 +1297,10 @@ extern "C" int gpb_debug_tile_trace(gpb_ctx* ctx, int64_t capacity) {
     if (!ctx || capacity < 0 || capacity > (1 << 22)) return GPB_E_ARG;
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
-    dev_free(&ctx->tile_trace);
+    ctx->tile_trace.release();
     if (capacity == 0) return 0;
     const size_t n = 8 + 8 * (size_t)capacity;
-    GPB_HIP(pool_malloc_t(&ctx->tile_trace, n * sizeof(unsigned)));
+    GPB_HIP(ctx->tile_trace.alloc((int64_t)n));
     GPB_HIP(hipMemset(ctx->tile_trace, 0, n * sizeof(unsigned)));
     const unsigned cap = (unsigned)capacity;
     GPB_HIP(hipMemcpy(ctx->tile_trace + 1, &cap, sizeof(unsigned), hipMemcpyHostToDevice));

@@ -76,7 +76,7 @@ int launch_vmat(gpb_ctx* ctx, double* dst) {
     const int64_t P = ctx->P, Np = ctx->Np, Wld = ctx->Wld;
     const int64_t need_v = P * Np * Wld;
     if (!dst) {
-        if (int rc = pool_grow(ctx, &ctx->vbuf, &ctx->vbuf_cap, need_v)) return rc;
+        if (int rc = ctx_grow(ctx, ctx->vbuf, need_v)) return rc;
         dst = ctx->vbuf;
     }
     dim3 gv((unsigned)(Wld / 128), (unsigned)((Np + 127) / 128), (unsigned)P);
@@ -89,7 +89,7 @@ int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* co
     // Wc: padded extent of this batch (cov's own ld); launch_predict lays the batch out with ld = Wc
     const int64_t P = ctx->P, Np = ctx->Np, Wc = round_up(W, WPAD);
     const int64_t need_c = P * Wc * Wc;
-    if (int rc = pool_grow(ctx, &ctx->covbuf, &ctx->covbuf_cap, need_c)) return rc;
+    if (int rc = ctx_grow(ctx, ctx->covbuf, need_c)) return rc;
     ctx->want_kst = true;                                    // (the joint covariance reads the fp64 K*^T itself: no digit planes here)
     int rc = launch_predict(ctx, Xs_dev, W, false);          // K*^T and the mean
     ctx->want_kst = false;

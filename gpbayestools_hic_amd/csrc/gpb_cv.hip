@@ -170,16 +170,6 @@ __global__ __launch_bounds__(256) void k_cv_loo(const double* __restrict__ part,
     if (bad) atomicAdd(notpd, 1);
 }
 
-int cv_reserve(gpb_ctx* ctx, size_t bytes) {
-    if ((int64_t)bytes <= ctx->cv_cap) return 0;
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->cv_ws) { pool_free(ctx->cv_ws); ctx->cv_ws = nullptr; }
-    ctx->cv_cap = 0;
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->cv_ws), bytes));
-    ctx->cv_cap = (int64_t)bytes;
-    return 0;
-}
-
 }  // namespace
 
 // Checks the folds of a cross-validation call and stores them in the context (device copy included); *kmax = the largest fold.
@@ -216,10 +206,9 @@ int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, co
         ctx->cv_loo = *kmax == 1;
     }
     const int64_t Np = ctx->Np, nI = Np / 64;
-    const size_t ints = (size_t)round_up((idx ? n_idx + nf + 1 : 0), 2);
-    const size_t bytes = ints * sizeof(int) + (ctx->cv_loo ? sizeof(double) * (size_t)(ctx->P * nI * Np) : 0);
+    const int64_t ints = round_up((idx ? n_idx + nf + 1 : 0), 2);      // (even: the doubles behind them stay aligned)
     GPB_HIP(hipSetDevice(ctx->device));
-    if (const int rc = cv_reserve(ctx, bytes)) return rc;
+    if (const int rc = ctx_grow(ctx, ctx->cv_ws, ints + (ctx->cv_loo ? 2 * ctx->P * nI * Np : 0))) return rc;
     if (idx) {
         // the host copy lives in the context: the previous call's upload must have left it before it is overwritten
         GPB_HIP(hipStreamSynchronize(ctx->stream));
@@ -227,7 +216,7 @@ int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, co
         for (int64_t f = 0; f <= nf; ++f) ctx->h_cv.push_back(fold_ptr ? fold_ptr[f] : (int)f);
         GPB_HIP(hipMemcpyAsync(ctx->cv_ws, ctx->h_cv.data(), sizeof(int) * ctx->h_cv.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    ctx->cv_n = n_idx; ctx->cv_nf = nf; ctx->cv_kmax = *kmax; ctx->cv_ints = (int64_t)ints;
+    ctx->cv_n = n_idx; ctx->cv_nf = nf; ctx->cv_kmax = *kmax; ctx->cv_ints = ints;
     return 0;
 }
 
@@ -235,11 +224,11 @@ int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, co
 int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64_t si, double* cov_dev) {
     const int64_t Np = ctx->Np, P = ctx->P, n_idx = ctx->cv_n, nf = ctx->cv_nf;
     const int nI = (int)(Np / 64), pad = (int)pad_front(Np, ctx->N);
-    const int* idx = ctx->cv_has_idx ? reinterpret_cast<const int*>(ctx->cv_ws) : nullptr;
+    const int* idx = ctx->cv_has_idx ? reinterpret_cast<const int*>(ctx->cv_ws.get()) : nullptr;
     const CvOut out{mean_dev, var_dev, sp, si, cov_dev, (int)ctx->cv_kmax};
     if (P > 65535 || nI > 65535) GPB_FAIL(GPB_E_ARG, "gpb: cross-validation of more than 65535 GPs or 4 million design points");
     if (ctx->cv_loo) {
-        double* part = reinterpret_cast<double*>(reinterpret_cast<int*>(ctx->cv_ws) + ctx->cv_ints);
+        double* part = reinterpret_cast<double*>(reinterpret_cast<int*>(ctx->cv_ws.get()) + ctx->cv_ints);
         hipLaunchKernelGGL(k_cv_colsq, dim3((unsigned)nI, (unsigned)nI, (unsigned)P), dim3(256), 0, ctx->stream, ctx->Linv, part, Np, nI);
         hipLaunchKernelGGL(k_cv_loo, dim3((unsigned)((n_idx + 255) / 256), (unsigned)P), dim3(256), 0, ctx->stream, part, ctx->alpha,
                            ctx->Z, idx, n_idx, Np, nI, pad, ctx->alpha_reg, ctx->pnoise, out, ctx->notpd);

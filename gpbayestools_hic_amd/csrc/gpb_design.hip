@@ -282,7 +282,7 @@ extern "C" int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev, int64_t C, c
     GPB_HIP(hipSetDevice(ctx->device));
     const DesignLayout L = design_layout(ctx, C, R);
     int rc;
-    if ((rc = pool_grow(ctx, &ctx->design_ws, &ctx->design_cap, L.total))) return rc;
+    if ((rc = ctx_grow(ctx, ctx->design_ws, L.total))) return rc;
     if ((rc = ensure_wcap(ctx, C > R ? C : R))) return rc;
     double* ws = ctx->design_ws;
     hipStream_t st = ctx->stream;
@@ -374,7 +374,7 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
         const int64_t P = c->P;
         const int64_t nU = T * P * Cp, nur = P * Rp, npart = P * nch * Cp, nden = round_up(P, 2);
         const int64_t need = nU + nur + npart + Cp + nden + (e == 0 ? 2 + Cp / 8 : 0);
-        if (const int rc = pool_grow(c, &c->design_run, &c->design_run_cap, need)) { ctx->err = c->err; return rc; }
+        if (const int rc = ctx_grow(c, c->design_run, need)) { ctx->err = c->err; return rc; }
         run[e].U = c->design_run;
         run[e].ur = run[e].U + nU;
         run[e].part = run[e].ur + nur;
@@ -436,9 +436,7 @@ extern "C" int gpb_design_end(gpb_ctx* ctx) {
     if (!ctx->design_ws && !ctx->design_run) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->design_ws) pool_free(ctx->design_ws);
-    if (ctx->design_run) pool_free(ctx->design_run);
-    ctx->design_ws = ctx->design_run = nullptr;
-    ctx->design_cap = ctx->design_run_cap = 0;
+    ctx->design_ws.release();
+    ctx->design_run.release();
     return 0;
 }

@@ -270,7 +270,7 @@ static void launch_kmat_mfma(gpb_ctx* ctx) {
     hipLaunchKernelGGL((k_kmat_mfma<KIND, DP>), grid, dim3(256), 0, ctx->stream, ctx->Xc, ctx->dnorm, ctx->amp,     \
                        ctx->noise, ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np,                            \
                        ctx->n_diff > 0 ? ctx->gpform : nullptr,                                                     \
-                       reinterpret_cast<const int2*>(ctx->kmtiles))
+                       reinterpret_cast<const int2*>(ctx->kmtiles.get()))
     switch (ctx->dpad) {
         case 8: GPB_KM(8); break;
         case 16: GPB_KM(16); break;
@@ -689,11 +689,7 @@ int launch_lml_grad(gpb_ctx* ctx, double* grad_dev) {
     const int64_t nt64 = ctx->Np / 64;
     const int ntiles = (int)(nt64 * (nt64 + 1) / 2);
     const int64_t need = (int64_t)ctx->P * ntiles * (ctx->d + 2);
-    if (need > ctx->gpart_cap) {
-        if (ctx->gpart) pool_free(ctx->gpart);
-        GPB_HIP(pool_malloc_t(&ctx->gpart, need * sizeof(double)));
-        ctx->gpart_cap = need;
-    }
+    if (int rc = ctx_grow(ctx, ctx->gpart, need)) return rc;
     if (ctx->kind == GPB_KERNEL_RBF) launch_grad_kind<GPB_KERNEL_RBF>(ctx, ntiles, grad_dev);
     else if (ctx->kind == GPB_KERNEL_MATERN15) launch_grad_kind<GPB_KERNEL_MATERN15>(ctx, ntiles, grad_dev);
     else launch_grad_kind<GPB_KERNEL_MATERN25>(ctx, ntiles, grad_dev);

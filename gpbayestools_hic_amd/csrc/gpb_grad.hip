@@ -426,7 +426,7 @@ int grad_ws(gpb_ctx* ctx, int64_t W, bool need_beta, bool need_like, int64_t n_o
                             ctx->pmap_d_in > 0 ? W * d * din : 0, lw_global ? W * like_w_doubles(ctx) : 0, W * (din > d ? din : d), n_out};
     int64_t need = 0;
     for (int i = 0; i < 10; ++i) need += round_up(sz[i], 32);
-    if (int rc = pool_grow(ctx, &ctx->gbuf, &ctx->gbuf_cap, need)) return rc;
+    if (int rc = ctx_grow(ctx, ctx->gbuf, need)) return rc;
     double* q = ctx->gbuf;
     double** dst[10] = {&g.bt, &g.dm, &g.dv, &g.wmu, &g.wv, &g.xg, &g.jm, &g.lw, &g.xin, &g.out};
     for (int i = 0; i < 10; ++i) {

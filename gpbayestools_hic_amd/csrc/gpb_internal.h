@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/gpbayes.h"
 #include "../../include/gpbayes_debug.h"
+#include "dev_buf.h"
 
 namespace gpb {
 
@@ -65,23 +66,23 @@ struct gpb_ctx {
     int kind = 0;
     double alpha_reg = 0.0;
     bool have_theta = false, factored = false;
-    double* h_theta = nullptr;     // host [P][d+2]
+    std::vector<double> h_theta;   // host [P][d+2]
     bool multi = false;            // gpb_gp_set_multi: every GP has its own design (fit-only context: no predict / likelihood)
     int64_t Pstore = 0;            // GPs stored (P is the number a launch covers: Pstore, or the subset's size inside gpb_gp_lml_subset)
-    int* gpN = nullptr;            // device [Pstore] design points per GP (multi)
+    gpb::DevBuf<int> gpN;            // device [Pstore] design points per GP (multi)
     int* gpmap = nullptr;          // device [Pstore] slot -> stored GP of the current subset evaluation
     bool subset = false;           // inside gpb_gp_lml_subset
     std::vector<int> h_N;          // host [Pstore]
     std::vector<int> h_map;        // host [P] of the current subset
     GpSel sel() const {
-        return GpSel{subset ? gpmap : nullptr, multi ? gpN : nullptr, (int)N, multi ? Np * dpad : 0, multi ? dpad : 0};
+        return GpSel{subset ? gpmap : nullptr, multi ? gpN.get() : nullptr, (int)N, multi ? Np * dpad : 0, multi ? dpad : 0};
     }
-    double* X = nullptr;           // [Np][dpad]   raw design (pad rows/cols zero); multi: [Pstore][Np][dpad]
-    double* Xsc = nullptr;         // [P][Np][dpad] design / length_scale_p
-    double* xmean = nullptr;       // [dpad] column means of the design (0 in the padding); multi: [Pstore][dpad]
-    double* muS = nullptr;         // [P][dpad] xmean / length_scale_p
-    double* Xc = nullptr;          // [P][Np][dpad] Xsc - muS: centred scaled design (dot-product form of k_kcross)
-    double* dnorm = nullptr;       // [P][Np] squared norms of the rows of Xc
+    gpb::DevBuf<double> X;           // [Np][dpad]   raw design (pad rows/cols zero); multi: [Pstore][Np][dpad]
+    gpb::DevBuf<double> Xsc;         // [P][Np][dpad] design / length_scale_p
+    gpb::DevBuf<double> xmean;       // [dpad] column means of the design (0 in the padding); multi: [Pstore][dpad]
+    gpb::DevBuf<double> muS;         // [P][dpad] xmean / length_scale_p
+    gpb::DevBuf<double> Xc;          // [P][Np][dpad] Xsc - muS: centred scaled design (dot-product form of k_kcross)
+    gpb::DevBuf<double> dnorm;       // [P][Np] squared norms of the rows of Xc
     // Distance form per GP (chosen from theta alone: gpb_gp_set_theta -> choose_forms).  0 = Gram form r^2 = |a|^2 + |b|^2 - 2 a.b
     // on the centred design (k_kcross<DOT>, k_kmat_mfma), 1 = difference form sum ((a_k - b_k))^2 on X / l as sklearn's cdist
     // computes it (sk:kernels.py:1556,1564,1711-1716).  The Gram form's cancellation costs ~eps (|a|^2 + |b|^2) absolute in
@@ -89,93 +90,80 @@ struct gpb_ctx {
     std::vector<double> h_ext;     // host [d] column extents (max - min) of the design; multi: [Pstore][d]
     std::vector<int> h_form;       // host [P]
     int* gpform = nullptr;         // device [P]
-    int* kmtiles = nullptr;        // device [Np/64 (Np/64 + 1) / 2][2]: (row block, column block) of tile t of the lower block triangle (k_kmat_mfma)
+    gpb::DevBuf<int> kmtiles;        // device [Np/64 (Np/64 + 1) / 2][2]: (row block, column block) of tile t of the lower block triangle (k_kmat_mfma)
     int n_diff = 0;                // GPs in the difference form
     double gram_limit = 1024.0;    // S above this: difference form (r^2 within ~1e-13 absolute, K within ~2e-13, below it)
     double* ls = nullptr;          // [P][dpad]    length scales (1 in pad columns)
     double* amp = nullptr;         // [P] c
     double* noise = nullptr;       // [P] sigma_n^2
-    double* Z = nullptr;           // [P][Np]
+    gpb::DevBuf<double> Z;           // [P][Np]
     // per-point simulation noise (gpb_gp_set_point_noise; nullptr: none): s [Pstore][Np], laid out and indexed like Z (design point i
     // of stored GP q at [q * Np + pad_front + i], zero in the padding).  The training diagonal is c + sigma_n^2 + (alpha_reg + s).
-    double* pnoise = nullptr;
-    double* K = nullptr;           // [P][Np][Np]  K, overwritten by L (lower) in gp_factor
-    double* Linv = nullptr;        // [P][Np][Np]
+    gpb::DevBuf<double> pnoise;
+    gpb::DevBuf<double> K;           // [P][Np][Np]  K, overwritten by L (lower) in gp_factor
+    gpb::DevBuf<double> Linv;        // [P][Np][Np]
     // sliced-integer predict (gpb_sliced.hip, option key 51): int8 digit planes of L^-1 (made on first use after a factorisation)
     // and of the current K*^T batch, row / column scales
     // 0 = fp64 kernel always; 1 = six digit planes where their rule admits the context; 2 = six, rule off (tests);
     // 3 (default) = seven digit planes (fp64-accurate) wherever the int32 sums stay exact (Np <= 16384)
     int predict_sliced = 3;
-    int8_t* slA = nullptr;         // [P][D][Np/16][Np128][16], room for D = 7 planes per GP
-    int8_t* slB = nullptr;         // [P][D][Np/16][Wcap][16] (leading dimension of a batch: Wld), room for D = 7
-    double* sl_scale = nullptr;    // rowscale [P][Np128] | colscale [P] | rowexp (int) [P][Np128]
+    gpb::DevBuf<int8_t> slA;         // [P][D][Np/16][Np128][16], room for D = 7 planes per GP
+    gpb::DevBuf<int8_t> slB;         // [P][D][Np/16][Wcap][16] (leading dimension of a batch: Wld), room for D = 7
+    gpb::DevBuf<double> sl_scale;    // rowscale [P][Np128] | colscale [P] | rowexp (int) [P][Np128]
     bool slA_valid = false;
     int slA_depth = 0;             // digit planes per operand of the planes in slA (6 or 7)
-    int64_t slB_cap = 0;
     int batch_sliced = 0;          // the current batch's K*^T exists as this many digit planes (launch_kcross), 0: as fp64
     bool want_kst = false;         // the caller of launch_kcross needs the fp64 K*^T itself (joint covariance)
-    double* T = nullptr;           // [P][Np][Np]  workspace (trtri / K^-1)
-    double* yv = nullptr;          // [P][Np]      L^-1 z
-    double* alpha = nullptr;       // [P][Np]      K^-1 z
-    double* apart = nullptr;       // [Np/256][P][Np] alpha partials
-    int* info = nullptr;           // [P]
-    double* lmlbuf = nullptr;      // [P][4]
-    double* gpart = nullptr;       // gradient partials
-    int64_t gpart_cap = 0;
+    gpb::DevBuf<double> T;           // [P][Np][Np]  workspace (trtri / K^-1)
+    gpb::DevBuf<double> yv;          // [P][Np]      L^-1 z
+    gpb::DevBuf<double> alpha;       // [P][Np]      K^-1 z
+    gpb::DevBuf<int> info;           // [P]
+    gpb::DevBuf<double> lmlbuf;      // [P][4]
+    gpb::DevBuf<double> gpart;       // gradient partials
 
     // ---- predict workspace ------------------------------------------------------
     int64_t Wcap = 0;              // padded capacity (multiple of WPAD)
     int64_t last_W = 0;            // rows of the most recent K*^T batch (gpb_gp_get GPB_GET_KSTAR)
     int64_t Wld = 0;               // leading dimension of the current batch's workspaces (set by launch_predict: the padded batch)
-    double* Xs = nullptr;          // [Wcap][d] staged inputs (when caller passes host memory)
-    double* estd = nullptr;        // [Wcap]
-    double* KsT = nullptr;         // [P][Np][Wcap]
-    double* mpart = nullptr;       // [Np/KX_CHUNK][P][Wcap]
-    double* spart = nullptr;       // [Np/64][P][Wcap]  sum-of-squares partials per 64-row block
-    double* mean_pc = nullptr;     // [P][Wcap]
-    double* var_pc = nullptr;      // [P][Wcap]
+    gpb::DevBuf<double> Xs;          // [Wcap][d] staged inputs (when caller passes host memory)
+    gpb::DevBuf<double> estd;        // [Wcap]
+    gpb::DevBuf<double> KsT;         // [P][Np][Wcap]
+    gpb::DevBuf<double> mpart;       // [Np/KX_CHUNK][P][Wcap]
+    gpb::DevBuf<double> spart;       // [Np/64][P][Wcap]  sum-of-squares partials per 64-row block
+    gpb::DevBuf<double> mean_pc;     // [P][Wcap]
+    gpb::DevBuf<double> var_pc;      // [P][Wcap]
     unsigned long long* live_hint = nullptr;   // pinned host memory: (batch rows << 32) | live rows of the last finished compaction
     gpb_ctx* hint_from = nullptr;  // whose live_hint sizes this context's tile rule (the chain's first emulator compacts)
     int fuse_accept_propose = 1;   // tune key 30: accept of a half-step + proposal of the next in one launch (needs premark 2)
     int balance_shards = 0;        // tune key 36: sharded C loop takes equal slices of the ordered live-row list (1: from 8 ranks on, 2: always; default off)
-    int* bal_ws = nullptr;         // its flags / ranks / scatter lists
-    int64_t bal_cap = 0;
+    gpb::DevBuf<int> bal_ws;         // its flags / ranks / scatter lists
     int sim_rank = 0;              // tune key 32: which rank of sim_ranks the measurement hook plays
     int tile_by_live = 1;          // tune key 28
     int premark = 2;               // tune key 29: the C-driven loop's proposal kernel takes the prior-box test (1) and gathers the rows inside (2)
-    double* cmp_X = nullptr;       // the rows of the current batch inside the prior box, gathered in order [Wcap][chain ndim]
-    int64_t cmp_X_cap = 0;
-    int* cmp_idx = nullptr;        // compaction of a log-posterior batch to the rows inside the prior box: [0] = count, [4..] = row indices
+    gpb::DevBuf<double> cmp_X;       // the rows of the current batch inside the prior box, gathered in order [Wcap][chain ndim]
+    gpb::DevBuf<int> cmp_idx;        // compaction of a log-posterior batch to the rows inside the prior box: [0] = count, [4..] = row indices
     int compact = 1;               // gpb_logpost / gpb_emcee_run evaluate the rows inside the box only (the reference: src/mcmc.py:278-283)
-    unsigned long long* rows_live = nullptr;   // device counter: rows evaluated by compacted launches while profiling
+    gpb::DevBuf<unsigned long long> rows_live;   // device counter: rows evaluated by compacted launches while profiling
     bool prof_compacted = false;
-    double* vbuf = nullptr;        // [P][Np][Wcap] V = L^-1 K*^T (covariance path only)
-    int64_t vbuf_cap = 0;
-    double* gbuf = nullptr;        // gradient path (gpb_grad.hip): beta^T = (K^-1 K*^T)^T [P][Wld][Np], then per-row pieces
-    int64_t gbuf_cap = 0;
-    double* covbuf = nullptr;      // [P][Wc][Wc]
-    int64_t covbuf_cap = 0;
-    double* out_stage = nullptr;   // staging for host outputs
-    int64_t out_cap = 0;
+    gpb::DevBuf<double> vbuf;        // [P][Np][Wcap] V = L^-1 K*^T (covariance path only)
+    gpb::DevBuf<double> gbuf;        // gradient path (gpb_grad.hip): beta^T = (K^-1 K*^T)^T [P][Wld][Np], then per-row pieces
+    gpb::DevBuf<double> covbuf;      // [P][Wc][Wc]
+    gpb::DevBuf<double> out_stage;   // staging for host outputs
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
-    int* cv_ws = nullptr;
-    int64_t cv_cap = 0;            // bytes
+    gpb::DevBuf<int> cv_ws;
     std::vector<int> h_cv;
     int64_t cv_n = 0, cv_nf = 0, cv_kmax = 0, cv_ints = 0;
     bool cv_loo = false, cv_has_idx = false;
     // Sobol indices (gpb_sobol.hip): I | E tables [P][N][dpad] each, e partials [P][Np/64], then what the call needs (tile
     // partials, staged results); the box of the planned call, lo [d] | hi [d]
-    double* sobol_ws = nullptr;
-    int64_t sobol_cap = 0;         // doubles
+    gpb::DevBuf<double> sobol_ws;
     std::vector<double> h_sobol_box;
     // sequential design (gpb_design.hip): gpb_design_begin's block x_c [C][d] | x_r [R][d] | w [Rp] | g [P] | s(c,c) [P][Cp] |
     // V_c [P][Np][Cp] | V_r [P][Np][Rp] | S_rc [P][Rp][Cp] (Cp, Rp: C, R padded to 128), then gpb_chain_design_run's own
     // (design_run: the picks' scaled rows u_c [T][P][Cp], the pending u_r [P][Rp], chunk partials, scores, denominators)
-    double* design_ws = nullptr;
-    int64_t design_cap = 0;        // doubles
-    double* design_run = nullptr;
-    int64_t design_run_cap = 0;    // doubles
+    gpb::DevBuf<double> design_ws;
+    gpb::DevBuf<double> design_run;
     int64_t design_C = 0, design_R = 0;
     bool design_ready = false;     // begun and not yet consumed by a run (the run conditions S_rc in place)
     bool design_noise = false;     // gpb_design_set_noise: the begin block's s_c [P][Cp] holds the candidates' simulation noise
@@ -187,43 +175,38 @@ struct gpb_ctx {
     // host copies of the observable transform (PCA modes) for the low-rank form of the likelihood
     std::vector<double> h_A, h_mu, h_C0;
     // low-rank likelihood (gpb_like.hip, k_loglike_lowrank): C = C0 + A^T D A with C0 = C_trunc + C_exp fixed
-    double* lr_R = nullptr;        // [16][16] upper-triangular R of  L0^-1 A^T = Q R  (zero padded)
-    double* lr_v0 = nullptr;       // [16]     Q^T L0^-1 (mu - yexp)
+    gpb::DevBuf<double> lr_R;        // [16][16] upper-triangular R of  L0^-1 A^T = Q R  (zero padded)
+    gpb::DevBuf<double> lr_v0;       // [16]     Q^T L0^-1 (mu - yexp)
     double lr_cperp = 0.0;         // |(I - Q Q^T) L0^-1 (mu - yexp)|^2
     double lr_logdet0 = 0.0;       // log det C0
     bool lr_ok = false;
     int lowrank = 1;               // use it when it applies (tune key 23)
     int lr_split = 1;              // option key 49: a chain's block likelihoods as one workgroup per (walker tile, emulator) + an ordered sum
-    double* lr_blocks = nullptr;   // [E][Wcap] the emulators' blocks of a chain's batch (chain's first context)
-    int64_t lr_blocks_cap = 0;
-    double* A = nullptr;           // [P][M]
-    double* mu = nullptr;          // [M]
-    double* scale = nullptr;       // [M]
-    double* C0 = nullptr;          // [M][M] cov_trunc (zeros if absent)
-    double* yexp = nullptr;        // [M]
-    double* Cexp = nullptr;        // [M][M]
-    double* mvn_ws = nullptr;      // global fallback for M > 128: [Wcap][M][M]
-    int64_t mvn_ws_cap = 0;
-    int* notpd = nullptr;          // device counter
-    long long* n_nan = nullptr;    // device counter: NaN log-probabilities seen by the stretch move's accept step
-    double* mc_ws = nullptr;       // gpb_emcee_run: proposals q[nh][d], factor[nh], log-probabilities lpq[nh]
-    int64_t mc_cap = 0;
-    double* ptl_ws = nullptr;      // gpb_chain_ptlmc_run: draws, proposals, their lp / gradient, the other state buffers
-    int64_t ptl_cap = 0;
-    double* smc_ws = nullptr;      // gpb_chain_smc_*: weights, their scan, the gathered / proposed particles, moments
-    int64_t smc_cap = 0;
+    gpb::DevBuf<double> lr_blocks;   // [E][Wcap] the emulators' blocks of a chain's batch (chain's first context)
+    gpb::DevBuf<double> A;           // [P][M]
+    gpb::DevBuf<double> mu;          // [M]
+    gpb::DevBuf<double> scale;       // [M]
+    gpb::DevBuf<double> C0;          // [M][M] cov_trunc (zeros if absent)
+    gpb::DevBuf<double> yexp;        // [M]
+    gpb::DevBuf<double> Cexp;        // [M][M]
+    gpb::DevBuf<double> mvn_ws;      // global fallback for M > 128: [Wcap][M][M]
+    gpb::DevBuf<int> notpd;          // device counter
+    gpb::DevBuf<long long> n_nan;    // device counter: NaN log-probabilities seen by the stretch move's accept step
+    gpb::DevBuf<double> mc_ws;       // gpb_emcee_run: proposals q[nh][d], factor[nh], log-probabilities lpq[nh]
+    gpb::DevBuf<double> ptl_ws;      // gpb_chain_ptlmc_run: draws, proposals, their lp / gradient, the other state buffers
+    gpb::DevBuf<double> smc_ws;      // gpb_chain_smc_*: weights, their scan, the gathered / proposed particles, moments
     int sim_ranks = 0;             // measurement hook: gpb_emcee_run evaluates 1/sim_ranks of every batch (one rank's share)
     int num_cu = 256;               // multiprocessor count of the device
     int64_t narrow_switch = 1280;   // 64x64 tiles when at least this many of them exist per 256 CUs, else 64x32
     int chain_batch = 1;            // tune key 40: a chain's emulators of equal padded size share one predict launch
-    unsigned* tile_counter = nullptr;   // 8 ticket queues (stride 16) + done counter [128]; re-armed by the kernel
+    gpb::DevBuf<unsigned> tile_counter;   // 8 ticket queues (stride 16) + done counter [128]; re-armed by the kernel
     int64_t chol_outer = 0;        // outer panel width of the two-level blocked Cholesky (0 = chosen by size, gpb_chol.hip)
     int chol_pair = 1;             // option key 47: column pairs — every second trailing update by two columns at once (k_chol_update2):
                                    // 1 = where measured faster (1024 <= Np <= 3072), 2 = always, 0 = never
     int chol_lookahead = 1;        // far part of a panel's trailing update on a side stream, under the next panel's chain
     // ls / amp / noise / gpform / gpmap are carved out of ONE device block (thblk) so that a new theta goes up in ONE asynchronous
     // copy from its page-locked twin (h_thblk) — round 5: an LML evaluation made 6 blocking copies and 5 synchronisations
-    double* thblk = nullptr;
+    gpb::DevBuf<double> thblk;
     double* h_thblk = nullptr;
     size_t thblk_bytes = 0;
     double* h_res = nullptr;       // page-locked: [lmlbuf doubles | info ints] of an LML evaluation's read-back
@@ -234,7 +217,7 @@ struct gpb_ctx {
     int kinv_tile = 0;             // option key 50: tile of K^-1 = L^-T L^-1 (LML gradient; 0 = by fill, 64, 128)
     int chol_inner_tile = 64;      // tile of the K=64 trailing updates inside an outer panel (64 or 128)
     int resident_order = 2;         // static 64-row predict launches: order of the tiles over the CUs, 1-3 (2 = snake)
-    unsigned* tile_trace = nullptr; // debug hook: [count, capacity, pad x6][capacity][8] records of k_predict tiles
+    gpb::DevBuf<unsigned> tile_trace; // debug hook: [count, capacity, pad x6][capacity][8] records of k_predict tiles
     int tile_priority = 1;         // k_predict: wave priority by K-loop length (s_setprio)
     int kcross_chunks = 0;         // 64-row chunks of the design per k_kcross workgroup (0 = by grid size)
     int kcross_wpl = 2;            // walkers per lane of k_kcross (1 or 2)
@@ -251,8 +234,8 @@ struct gpb_ctx {
     int64_t mvn_wg_switch = 768;   // batches up to this size use one workgroup per walker (32 < M <= 64)
 
     // ---- parameterTrafoPCA input map (gpb_pmap.hip) ------------------------------------
-    int* pmap_int = nullptr;       // col_src[d_out] | group descriptors [G][6]
-    double* pmap_tab = nullptr;    // [G][4 + maxpc][100]
+    gpb::DevBuf<int> pmap_int;       // col_src[d_out] | group descriptors [G][6]
+    gpb::DevBuf<double> pmap_tab;    // [G][4 + maxpc][100]
     int64_t pmap_d_in = 0, pmap_d_out = 0;
     int pmap_groups = 0, pmap_maxpc = 0;
 
@@ -284,25 +267,27 @@ struct gpb_ctx {
     } while (0)
 
 namespace gpb {
-// cache of freed device buffers (gpb_pool.hip): every pointer from pool_malloc must go back through pool_free
-hipError_t pool_malloc(void** p, size_t bytes);
-void pool_free(void* p);
-void pool_trim();
+// The device buffers of a context: DevBuf members (dev_buf.h), allocated through these two and given back by `delete ctx`
+// once gpb_ctx_destroy has idled the streams.  Before a held buffer goes back to the cache, the context's stream and its
+// look-ahead stream are synchronised: nothing enqueued still uses it.  (Nothing is synchronised for an empty buffer or one
+// that is large enough — the steady state.)  A failure leaves the buffer empty, never dangling.
+// THE RULE for an entry point that replaces buffers: lower the flags and sizes that declare them valid (N, have_*, Wcap,
+// pmap_d_in, ...) BEFORE its first allocation and raise them after its last, so a failure half-way leaves a context that
+// its checks reject, not one that launches on a null pointer.
+// ctx_replace: exactly n elements, now (contents undefined)
 template <typename T>
-inline hipError_t pool_malloc_t(T** p, size_t bytes) { return pool_malloc(reinterpret_cast<void**>(p), bytes); }
-// A workspace of the context grown on demand to `need` elements (never shrunk; the contents are not kept).  The stream is
-// synchronised before the old buffer goes back to the cache, and pointer and capacity are cleared before the allocation
-// that may fail, so that a failure leaves an empty workspace, not a dangling one.
-template <typename T>
-inline int pool_grow(gpb_ctx* ctx, T** p, int64_t* cap, int64_t need) {
-    if (*cap >= need) return 0;
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) pool_free(*p);
-    *p = nullptr;
-    *cap = 0;
-    GPB_HIP(pool_malloc_t(p, sizeof(T) * (size_t)need));
-    *cap = need;
+inline int ctx_replace(gpb_ctx* ctx, DevBuf<T>& b, int64_t n) {
+    if (b) {
+        GPB_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->side_stream) GPB_HIP(hipStreamSynchronize(ctx->side_stream));
+    }
+    GPB_HIP(b.alloc(n));
     return 0;
+}
+// ctx_grow: a workspace of at least `need` elements (never shrunk; the contents are not kept)
+template <typename T>
+inline int ctx_grow(gpb_ctx* ctx, DevBuf<T>& b, int64_t need) {
+    return b.cap >= need ? 0 : ctx_replace(ctx, b, need);
 }
 // fit side (gpb_fit.hip)
 int launch_scale_design(gpb_ctx* ctx);

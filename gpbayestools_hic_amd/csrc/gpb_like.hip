@@ -767,7 +767,7 @@ __global__ __launch_bounds__(256) void k_lowrank_sum(const double* __restrict__ 
 // the per-emulator blocks of a chain's log-likelihood, [E][Wcap] in the chain's first context (k_loglike_lowrank_multi / k_lowrank_sum)
 int ensure_lr_blocks(gpb_ctx* ctx, int E) {
     if (E < 2 || !ctx->lr_split) return 0;
-    return pool_grow(ctx, &ctx->lr_blocks, &ctx->lr_blocks_cap, (int64_t)E * ctx->Wcap);
+    return ctx_grow(ctx, ctx->lr_blocks, (int64_t)E * ctx->Wcap);
 }
 
 // The block log-likelihoods of a chain's compacted batch, added up in emuList order, when every block takes the low-rank
@@ -792,7 +792,7 @@ int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double*
     tab.E = E;
     // one workgroup per (walker tile, emulator) + the ordered sum, when the blocks' buffer is there (ensure_lr_blocks;
     // option key 49 = 0: the one-launch walk — the A/B, and the bit-identity test)
-    double* blocks = (ctx->lr_split && ctx->lr_blocks && ctx->lr_blocks_cap >= (int64_t)E * ctx->Wld) ? ctx->lr_blocks : nullptr;
+    double* blocks = (ctx->lr_split && ctx->lr_blocks.cap >= (int64_t)E * ctx->Wld) ? ctx->lr_blocks : nullptr;
     const dim3 grid((unsigned)((W + 63) / 64), blocks ? (unsigned)E : 1u);
 #define GPB_LRM(PPV)                                                                                             \
     hipLaunchKernelGGL(k_loglike_lowrank_multi<PPV>, grid, dim3(lr_threads<PPV>()), 0, ctx->stream, tab, ctx->Wld, W, ll_dev, cmpv, inside_const, blocks)
@@ -837,7 +837,7 @@ static int mvn_storage(gpb_ctx* ctx, int64_t W, int64_t M, size_t small, double*
     *gws = nullptr;
     *sh = small + (size_t)(M + 1) * (M + 1) * sizeof(double);
     if (*sh <= 150 * 1024) return 0;
-    int rc = pool_grow(ctx, &ctx->mvn_ws, &ctx->mvn_ws_cap, W * (M + 1) * (M + 1));
+    int rc = ctx_grow(ctx, ctx->mvn_ws, W * (M + 1) * (M + 1));
     if (rc) return rc;
     *gws = ctx->mvn_ws;
     *sh = small;
@@ -1035,8 +1035,8 @@ int launch_compact(gpb_ctx* ctx, const double* X_dev, int64_t W, int64_t dx, con
 
 // the buffer of gathered rows [Wcap][dx], grown on demand
 int ensure_cmp_rows(gpb_ctx* ctx, int64_t dx) {
-    if (ctx->cmp_X_cap >= ctx->Wcap * dx) return 0;    // (tested here as well: the memset below is for a NEW buffer only)
-    int rc = pool_grow(ctx, &ctx->cmp_X, &ctx->cmp_X_cap, ctx->Wcap * dx);
+    if (ctx->cmp_X.cap >= ctx->Wcap * dx) return 0;    // (tested here as well: the memset below is for a NEW buffer only)
+    int rc = ctx_grow(ctx, ctx->cmp_X, ctx->Wcap * dx);
     if (rc) return rc;
     GPB_HIP(hipMemsetAsync(ctx->cmp_X, 0, sizeof(double) * (size_t)(ctx->Wcap * dx), ctx->stream));   // rows past the count are read (not used) by the upper-bound launches
     return 0;

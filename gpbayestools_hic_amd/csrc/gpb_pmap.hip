@@ -146,12 +146,11 @@ extern "C" int gpb_param_map_set(gpb_ctx* ctx, int64_t d_in, int64_t d_out, cons
     }
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->pmap_int) { pool_free(ctx->pmap_int); ctx->pmap_int = nullptr; }
-    if (ctx->pmap_tab) { pool_free(ctx->pmap_tab); ctx->pmap_tab = nullptr; }
-    const size_t ni = (size_t)d_out + 6 * (size_t)n_groups;
+    ctx->pmap_d_in = ctx->pmap_d_out = 0;       // no map until both tables are in place (the rule of ctx_replace)
     const size_t nt = (size_t)n_groups * (4 + maxpc) * PMAP_GRID;
-    GPB_HIP(pool_malloc_t(&ctx->pmap_int, ni * sizeof(int)));
-    GPB_HIP(pool_malloc_t(&ctx->pmap_tab, nt * sizeof(double)));
+    int rc;
+    if ((rc = ctx_replace(ctx, ctx->pmap_int, d_out + 6 * (int64_t)n_groups))) return rc;
+    if ((rc = ctx_replace(ctx, ctx->pmap_tab, (int64_t)nt))) return rc;
     GPB_HIP(hipMemcpy(ctx->pmap_int, col_src, (size_t)d_out * sizeof(int), hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->pmap_int + d_out, group_desc, 6 * (size_t)n_groups * sizeof(int), hipMemcpyHostToDevice));
     GPB_HIP(hipMemcpy(ctx->pmap_tab, tables, nt * sizeof(double), hipMemcpyHostToDevice));
@@ -161,7 +160,7 @@ extern "C" int gpb_param_map_set(gpb_ctx* ctx, int64_t d_in, int64_t d_out, cons
 
 extern "C" int gpb_param_map(gpb_ctx* ctx, const double* X_dev, int64_t W, double* out_dev) {
     if (!ctx || !X_dev || !out_dev || W < 0) return GPB_E_ARG;
-    if (!ctx->pmap_int) GPB_FAIL(GPB_E_STATE, "gpb_param_map before gpb_param_map_set");
+    if (ctx->pmap_d_in == 0) GPB_FAIL(GPB_E_STATE, "gpb_param_map before gpb_param_map_set");
     if (W == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
     const int d_out = (int)ctx->pmap_d_out;

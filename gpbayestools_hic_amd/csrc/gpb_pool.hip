@@ -112,3 +112,14 @@ void pool_trim() {
 }
 
 }  // namespace gpb
+
+#ifdef GPB_DEBUG_VARIANTS
+extern "C" int gpb_debug_pool_live(int64_t* buffers, int64_t* bytes) {
+    if (!buffers || !bytes) return GPB_E_ARG;
+    std::lock_guard<std::mutex> lk(gpb::g_m);
+    *buffers = (int64_t)gpb::g_live.size();
+    *bytes = 0;
+    for (const auto& kv : gpb::g_live) *bytes += (int64_t)kv.second.bytes;
+    return 0;
+}
+#endif

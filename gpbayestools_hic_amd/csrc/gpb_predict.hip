@@ -613,26 +613,17 @@ __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ mpa
 int ensure_wcap(gpb_ctx* ctx, int64_t W) {
     const int64_t need = round_up(W < 1 ? 1 : W, WPAD);
     if (need <= ctx->Wcap) return 0;
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    double** bufs[] = {&ctx->Xs, &ctx->estd, &ctx->KsT, &ctx->mpart, &ctx->spart, &ctx->mean_pc, &ctx->var_pc};
-    for (auto b : bufs) {
-        if (*b) { pool_free(*b); *b = nullptr; }
-    }
-    ctx->Wcap = 0;
+    ctx->Wcap = 0;         // (raised again once every workspace has its new size)
     const int64_t P = ctx->P, Np = ctx->Np;
     const int64_t nchunk = (Np + KX_CHUNK - 1) / KX_CHUNK, nI64 = Np / 64;
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->Xs), sizeof(double) * need * ctx->d));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->estd), sizeof(double) * need));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->KsT), sizeof(double) * P * Np * need));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->mpart), sizeof(double) * nchunk * P * need));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->spart), sizeof(double) * nI64 * P * need));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->mean_pc), sizeof(double) * P * need));
-    GPB_HIP(pool_malloc(reinterpret_cast<void**>(&ctx->var_pc), sizeof(double) * P * need));
-    if (ctx->cmp_idx) { pool_free(ctx->cmp_idx); ctx->cmp_idx = nullptr; }
-    if (ctx->cmp_X) { pool_free(ctx->cmp_X); ctx->cmp_X = nullptr; }
-    ctx->cmp_X_cap = 0;
-    // [0] = number of rows inside the box, [4..] = their indices; then the compaction's scratch: ranks, workgroup counts
-    GPB_HIP(pool_malloc_t(&ctx->cmp_idx, sizeof(int) * (size_t)(4 + 2 * need + need / 256 + 8)));
+    int rc;
+    if ((rc = ctx_replace(ctx, ctx->Xs, need * ctx->d)) || (rc = ctx_replace(ctx, ctx->estd, need)) ||
+        (rc = ctx_replace(ctx, ctx->KsT, P * Np * need)) || (rc = ctx_replace(ctx, ctx->mpart, nchunk * P * need)) ||
+        (rc = ctx_replace(ctx, ctx->spart, nI64 * P * need)) || (rc = ctx_replace(ctx, ctx->mean_pc, P * need)) ||
+        (rc = ctx_replace(ctx, ctx->var_pc, P * need)) ||
+        // [0] = number of rows inside the box, [4..] = their indices; then the compaction's scratch: ranks, workgroup counts
+        (rc = ctx_replace(ctx, ctx->cmp_idx, 4 + 2 * need + need / 256 + 8)))
+        return rc;
     ctx->Wcap = need;
     return 0;
 }

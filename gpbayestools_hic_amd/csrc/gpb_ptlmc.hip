@@ -291,7 +291,7 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
     // workspace: rvalo, thetap, grad, the other theta / dfval buffers [T, nd] each; lp, the other fval, the accept flags [T]
     // each; the mapped parameters of the per-emulator sequence
     const int64_t need = 5 * T * nd + 3 * T + nxg;
-    if (int rc = pool_grow(ctx, &ctx->ptl_ws, &ctx->ptl_cap, need)) return rc;
+    if (int rc = ctx_grow(ctx, ctx->ptl_ws, need)) return rc;
     double* rvalo = ctx->ptl_ws;
     double* thetap = rvalo + T * nd;
     double* gbuf = thetap + T * nd;

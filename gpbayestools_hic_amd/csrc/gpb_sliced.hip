@@ -318,7 +318,7 @@ __global__ __launch_bounds__(512, 2) void k_predict_sliced_multi(const SlTable t
 // log sn2]); 2: D = 6, theta rule off (accuracy probes).  Fit-only multi contexts and the tile trace (a hook of the fp64 kernel)
 // always take the fp64 kernel.
 int sliced_applies(const gpb_ctx* ctx) {
-    if (!ctx->predict_sliced || ctx->multi || !ctx->h_theta || !ctx->have_theta) return 0;
+    if (!ctx->predict_sliced || ctx->multi || ctx->h_theta.empty() || !ctx->have_theta) return 0;
     if (ctx->tile_trace) return 0;
     if (ctx->Np > SL_NP_MAX) return 0;
     if (ctx->predict_sliced == 3) return 7;
@@ -332,16 +332,13 @@ int sliced_applies(const gpb_ctx* ctx) {
 }
 
 void sliced_free(gpb_ctx* ctx) {
-    if (ctx->slA) { pool_free(ctx->slA); ctx->slA = nullptr; }
-    if (ctx->slB) { pool_free(ctx->slB); ctx->slB = nullptr; }
-    if (ctx->sl_scale) { pool_free(ctx->sl_scale); ctx->sl_scale = nullptr; }
+    ctx->slA.release(); ctx->slB.release(); ctx->sl_scale.release();
     ctx->slA_valid = false;
     ctx->slA_depth = 0;
-    ctx->slB_cap = 0;
 }
 
 const double* sliced_colscale(const gpb_ctx* ctx) {
-    return reinterpret_cast<const double*>(ctx->sl_scale) + ctx->P * round_up(ctx->Np, 128);
+    return reinterpret_cast<const double*>(ctx->sl_scale.get()) + ctx->P * round_up(ctx->Np, 128);
 }
 
 // Buffers of the sliced path (room for SL_DMAX planes, whichever depth runs); the planes of L^-1 follow a new factorisation or a
@@ -349,14 +346,18 @@ const double* sliced_colscale(const gpb_ctx* ctx) {
 int sliced_prepare(gpb_ctx* ctx, int depth) {
     if (depth != 6 && depth != 7) GPB_FAIL(GPB_E_STATE, "gpb: internal: sliced_prepare at a depth other than 6 or 7");
     const int64_t Np = ctx->Np, Np128 = round_up(Np, 128), P = ctx->P;
-    const size_t a_bytes = (size_t)P * SL_DMAX * (size_t)Np * (size_t)Np128;
-    if (!ctx->slA) {
-        GPB_HIP(pool_malloc_t(&ctx->slA, a_bytes));
-        GPB_HIP(hipMemsetAsync(ctx->slA, 0, a_bytes, ctx->stream));       // the upper triangle and the rows behind Np: zero for good
-        GPB_HIP(pool_malloc_t(&ctx->sl_scale, sizeof(double) * (size_t)(P * Np128 + P) + sizeof(int) * (size_t)(P * Np128)));
+    const int64_t a_bytes = P * SL_DMAX * Np * Np128;
+    int rc;
+    if (!ctx->slA) {       // (each of the two when it is missing: a failure between them must not hide the second for good)
         ctx->slA_valid = false;
+        if ((rc = ctx_replace(ctx, ctx->slA, a_bytes))) return rc;
+        GPB_HIP(hipMemsetAsync(ctx->slA, 0, (size_t)a_bytes, ctx->stream));       // the upper triangle and the rows behind Np: zero for good
     }
-    double* rowscale = reinterpret_cast<double*>(ctx->sl_scale);
+    if (!ctx->sl_scale) {  // doubles [P][Np128] + [P], then P * Np128 ints
+        ctx->slA_valid = false;
+        if ((rc = ctx_replace(ctx, ctx->sl_scale, P * Np128 + P + (P * Np128 + 1) / 2))) return rc;
+    }
+    double* rowscale = reinterpret_cast<double*>(ctx->sl_scale.get());
     double* colscale = rowscale + P * Np128;
     int* rowexp = reinterpret_cast<int*>(colscale + P);
     if (!ctx->slA_valid || ctx->slA_depth != depth) {
@@ -370,11 +371,7 @@ int sliced_prepare(gpb_ctx* ctx, int depth) {
         ctx->slA_valid = true;
         ctx->slA_depth = depth;
     }
-    if (ctx->slB_cap < ctx->Wcap || !ctx->slB) {
-        if (ctx->slB) { GPB_HIP(hipStreamSynchronize(ctx->stream)); pool_free(ctx->slB); ctx->slB = nullptr; }
-        GPB_HIP(pool_malloc_t(&ctx->slB, (size_t)P * SL_DMAX * (size_t)Np * (size_t)ctx->Wcap));
-        ctx->slB_cap = ctx->Wcap;
-    }
+    if ((rc = ctx_grow(ctx, ctx->slB, P * SL_DMAX * Np * ctx->Wcap))) return rc;
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -448,7 +445,7 @@ int launch_vsq_sliced(gpb_ctx* ctx, int64_t W, const int* nrows_dev, int kskip) 
     const int depth = ctx->batch_sliced;
     if (!ctx->slA || !ctx->slA_valid || !ctx->slB || ctx->slA_depth != depth)
         GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced before sliced_prepare");
-    const double* rowscale = reinterpret_cast<const double*>(ctx->sl_scale);
+    const double* rowscale = reinterpret_cast<const double*>(ctx->sl_scale.get());
     const double* colscale = rowscale + P * Np128;
     const int nI = (int)(Np128 / SL_BM);
     const int wtn = sliced_wtn(ctx, depth, P, nI, W, nrows_dev);
@@ -468,7 +465,7 @@ int launch_vsq_sliced_multi(gpb_ctx* const* ctxs, int E, int64_t W, const int* n
         gpb_ctx* c = ctxs[e];
         if (!c->slA || !c->slA_valid || !c->slB || c->Np != Np || c->Wld != Wld || c->batch_sliced != depth || c->slA_depth != depth)
             GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced_multi over a context that is not prepared");
-        const double* rowscale = reinterpret_cast<const double*>(c->sl_scale);
+        const double* rowscale = reinterpret_cast<const double*>(c->sl_scale.get());
         const double* colscale = rowscale + c->P * Np128;
         for (int p = 0; p < (int)c->P; ++p, ++G) {
             if (G >= SL_MAX_GP) GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced_multi: too many GPs for one table");

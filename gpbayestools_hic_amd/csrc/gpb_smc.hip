@@ -389,7 +389,7 @@ int smc_check(gpb_ctx* const* ctxs, int E, int64_t N, const char* who, int64_t& 
 // reweighting, the proposals of a move step); cov [nd, nd]; mean [nd]; the mapped parameters of the per-emulator sequence
 int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd, int64_t nxg) {
     const int64_t need = 3 * N + N * nd + nd * nd + nd + nxg;
-    return pool_grow(ctx, &ctx->smc_ws, &ctx->smc_cap, need);
+    return ctx_grow(ctx, ctx->smc_ws, need);
 }
 }  // namespace
 }  // namespace gpb

@@ -366,7 +366,7 @@ int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi
     ctx->h_sobol_box.insert(ctx->h_sobol_box.end(), hi, hi + ctx->d);
     if (extra < 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    return pool_grow(ctx, &ctx->sobol_ws, &ctx->sobol_cap, sobol_tab_doubles(ctx) + extra);
+    return ctx_grow(ctx, ctx->sobol_ws, sobol_tab_doubles(ctx) + extra);
 }
 
 // doubles behind the tables that launch_sobol needs: tile partials [P (P + 1) / 2][Np/64][Np/64][2d + 1]

@@ -416,7 +416,7 @@ extern "C" int gpb_stretch_accept(gpb_ctx* ctx, double* pos_dev, double* lp_dev,
     lpq.lpq = lpq_dev;
     hipLaunchKernelGGL(k_accept, dim3((unsigned)((nh * 32 + 255) / 256)), dim3(256), 0, ctx->stream, pos_dev, lp_dev, en, half,
                        (uint32_t)step, q_dev, factor_dev, lpq, reinterpret_cast<long long*>(naccept_dev),
-                       reinterpret_cast<long long*>(ctx->n_nan), BatchCount{});
+                       reinterpret_cast<long long*>(ctx->n_nan.get()), BatchCount{});
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -611,7 +611,7 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     if (!pl.plain && (rc = ensure_lr_blocks(ctx, E))) return rc;
     // proposal workspace: two sets of q[nh][d], factor[nh], lpq[nh] (the fused accept + proposal kernel reads one set and
     // writes the other) and a second log-probability vector [nwalkers]
-    if ((rc = pool_grow(ctx, &ctx->mc_ws, &ctx->mc_cap, 2 * nh * (d + 3)))) return rc;
+    if ((rc = ctx_grow(ctx, ctx->mc_ws, 2 * nh * (d + 3)))) return rc;
     pl.fused = pl.plain && loglike_fuses_finalize(ctx, chunk);
     // the gather kernel counts the flags in front of each of its workgroups itself: fine for a rank's rows of an
     // ensemble, quadratic for very large batches, which keep the marking kernel with its per-workgroup counts
@@ -629,7 +629,7 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     // the contiguous shares rarely differ by a tile.  0 = never (default), 1 = from 8 ranks on, 2 = always.
     pl.balanced = pl.pre == 2 && R > 1 && nh <= 16384 &&
                   (ctx->balance_shards == 2 || (ctx->balance_shards == 1 && R >= 8));
-    if (pl.balanced && (rc = pool_grow(ctx, &ctx->bal_ws, &ctx->bal_cap, 4 * nh + 2 * (4 + chunk) + 16))) return rc;
+    if (pl.balanced && (rc = ctx_grow(ctx, ctx->bal_ws, 4 * nh + 2 * (4 + chunk) + 16))) return rc;
     if (pl.pre && (rc = ensure_cmp_rows(ctx, d))) return rc;
     return 0;
 }
@@ -730,13 +730,13 @@ extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev,
         if (fuse_ap && g + 1 < nhalfsteps) {
             const int64_t g1 = g + 1;
             hipLaunchKernelGGL(k_accept_propose, g32, dim3(256), 0, ctx->stream, pos_dev, lp_cur, lp_alt, en, half, step, q, factor,
-                               lp_src, reinterpret_cast<long long*>(naccept_dev), reinterpret_cast<long long*>(ctx->n_nan), done,
+                               lp_src, reinterpret_cast<long long*>(naccept_dev), reinterpret_cast<long long*>(ctx->n_nan.get()), done,
                                (int)(g1 & 1), (uint32_t)(step0 + (uint64_t)(g1 >> 1)), a, qs[1 - b], factors[1 - b],
                                propose_box(1 - b));
             double* sw = lp_cur; lp_cur = lp_alt; lp_alt = sw;
         } else {
             hipLaunchKernelGGL(k_accept, g32, dim3(256), 0, ctx->stream, pos_dev, lp_cur, en, half, step, q, factor, lp_src,
-                               reinterpret_cast<long long*>(naccept_dev), reinterpret_cast<long long*>(ctx->n_nan), done);
+                               reinterpret_cast<long long*>(naccept_dev), reinterpret_cast<long long*>(ctx->n_nan.get()), done);
         }
         if (half == 1 && (chain_dev || lpchain_dev))
             hipLaunchKernelGGL(k_store_step, dim3((unsigned)((nwalkers * d + 255) / 256)), dim3(256), 0, ctx->stream, pos_dev,

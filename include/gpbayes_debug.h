@@ -60,6 +60,9 @@ GPB_API int gpb_debug_loopback_release(gpb_ctx* ctx);
  * GP, row block, walker tile, start, end (100 MHz ticks), blockIdx} to the host and re-arms. */
 GPB_API int gpb_debug_tile_trace(gpb_ctx* ctx, int64_t capacity);
 GPB_API int gpb_debug_tile_trace_read(gpb_ctx* ctx, uint32_t* records_host, int64_t max_records, int64_t* n_out);
+/* debug hook: the device buffers this library's buffer cache has handed out and not yet got back (every context of the
+ * process together), their number and their bytes — what a test compares before and after a context's life */
+GPB_API int gpb_debug_pool_live(int64_t* buffers, int64_t* bytes);
 /* issue-rate probe: returns measured TFLOP/s of back-to-back v_mfma_f64_16x16x4_f64
  * (mode 0), v_fma_f64 (mode 1) or both co-issued (mode 2); mode 3: shader cycles per MFMA (one wave
  * per SIMD); mode 4: shader clock in GHz held during the dense MFMA loop. */
