@@ -412,15 +412,13 @@ __global__ void k_grad_finish(const double* __restrict__ X, int64_t W, int nd, c
 
 namespace {
 
-int64_t map_din(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }
-
 // the pieces of one gradient evaluation of W rows, carved out of ctx->gbuf
 struct GradWs {
     double *bt, *dm, *dv, *wmu, *wv, *xg, *jm, *lw, *xin, *out;
 };
 
 int grad_ws(gpb_ctx* ctx, int64_t W, bool need_beta, bool need_like, int64_t n_out, GradWs& g) {
-    const int64_t Wld = round_up(W, WPAD), P = ctx->P, d = ctx->d, din = map_din(ctx);
+    const int64_t Wld = round_up(W, WPAD), P = ctx->P, d = ctx->d, din = sampler_ndim(ctx);
     const bool lw_global = need_like && like_w_doubles(ctx) > LIKE_W_LDS;
     const int64_t sz[10] = {need_beta ? P * Wld * ctx->Np : 0, W * P * d, need_beta ? W * P * d : 0, W * P, W * P, W * d,
                             ctx->pmap_d_in > 0 ? W * d * din : 0, lw_global ? W * like_w_doubles(ctx) : 0, W * (din > d ? din : d), n_out};
@@ -517,7 +515,7 @@ extern "C" int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, in
     if (W == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
     if ((rc = ensure_wcap(ctx, W))) return rc;
-    const int64_t din = map_din(ctx), n = W * ctx->M * din;
+    const int64_t din = sampler_ndim(ctx), n = W * ctx->M * din;
     GradWs g;
     if ((rc = grad_ws(ctx, W, false, false, on_device ? 0 : n, g))) return rc;
     const double* X = Xs;
@@ -546,59 +544,27 @@ extern "C" int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, in
 extern "C" int gpb_chain_logpost_grad(gpb_ctx* const* ctxs, int E, const double* Xs_dev, int64_t W, double* ll_dev,
                                       double* grad_dev, const double* lo_dev, const double* hi_dev, double outside_value,
                                       double inside_const) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     gpb_ctx* c0 = ctxs[0];
     gpb_ctx* ctx = c0;                          // (the error macros report on it)
     if (!Xs_dev || !ll_dev || !grad_dev || !lo_dev || !hi_dev || W < 0)
         GPB_FAIL(GPB_E_ARG, "gpb_chain_logpost_grad: null pointer or negative size");
-    const int64_t nd = map_din(c0);
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        if (!c) GPB_FAIL(GPB_E_ARG, "gpb_chain_logpost_grad: null context");
-        int rc = grad_state_check(c, "gpb_chain_logpost_grad");
-        if (rc) { c0->err = c->err; return rc; }
-        if (!c->have_like) GPB_FAIL(GPB_E_STATE, "gpb_chain_logpost_grad before gpb_like_set");
-        if (c->device != c0->device || c->stream != c0->stream)
-            GPB_FAIL(GPB_E_STATE, "gpb_chain_logpost_grad: the emulators' contexts must share one device and stream");
-        if (map_din(c) != nd) GPB_FAIL(GPB_E_ARG, "gpb_chain_logpost_grad: the emulators disagree on the number of parameters");
-        if (c->pmap_d_in > 0 && c->pmap_d_out != c->d)
-            GPB_FAIL(GPB_E_STATE, "gpb_chain_logpost_grad: a parameter map's output must be the GPs' input");
-    }
+    int rc;
+    for (int e = 0; e < E; ++e)                 // (first: a fit-only context has no likelihood either, and says which it is)
+        if (ctxs[e] && (rc = grad_state_check(ctxs[e], "gpb_chain_logpost_grad"))) { c0->err = ctxs[e]->err; return rc; }
+    if ((rc = chain_ctx_check(ctxs, E, "gpb_chain_logpost_grad"))) return rc;
     if (W == 0) return 0;
     GPB_HIP(hipSetDevice(c0->device));
-    int rc;
-    GradWs ws[64];
+    const int64_t nd = sampler_ndim(c0);
+    GradWs ws[MAX_CHAIN_CTX];
     for (int e = 0; e < E; ++e) {
         if ((rc = ensure_wcap(ctxs[e], W)) || (rc = grad_ws(ctxs[e], W, true, true, 0, ws[e]))) {
             c0->err = ctxs[e]->err;
             return rc;
         }
     }
-    // the log-posterior: what gpb_chain_logpost writes, or — where the chain call does not apply — the sequence of
-    // per-emulator calls Chain.log_prob_device makes
-    if (gpb_chain_supported(ctxs, E) == 1) {
-        if ((rc = gpb_chain_logpost(ctxs, E, Xs_dev, W, ll_dev, lo_dev, hi_dev, outside_value, inside_const))) return rc;
-    } else {
-        for (int e = 0; e < E; ++e) {
-            gpb_ctx* c = ctxs[e];
-            const bool mapped = c->pmap_d_in > 0, last = e == E - 1;
-            const double* Xg = Xs_dev;
-            if (mapped) {
-                if ((rc = gpb_param_map(c, Xs_dev, W, ws[e].xg))) { c0->err = c->err; return rc; }
-                Xg = ws[e].xg;
-            }
-            if (!last || mapped) {
-                if ((rc = gpb_loglike(c, Xg, W, 1, ll_dev, e > 0, nullptr))) { c0->err = c->err; return rc; }
-                if (last && (rc = gpb_box_finish(c, Xs_dev, W, nd, lo_dev, hi_dev, outside_value, inside_const, ll_dev))) {
-                    c0->err = c->err;
-                    return rc;
-                }
-            } else if ((rc = gpb_logpost(c, Xs_dev, W, ll_dev, e > 0, lo_dev, hi_dev, outside_value, inside_const))) {
-                c0->err = c->err;
-                return rc;
-            }
-        }
-    }
+    // the log-posterior, as every sampler evaluates it
+    if ((rc = chain_eval(ctxs, E, Xs_dev, W, ll_dev, lo_dev, hi_dev, outside_value, inside_const))) return rc;
     // the gradient, emulator after emulator (fp64 throughout), added up in emuList order
     for (int e = 0; e < E; ++e) {
         gpb_ctx* c = ctxs[e];

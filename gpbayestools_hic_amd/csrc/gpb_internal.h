@@ -358,35 +358,25 @@ int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double*
                                  bool* taken);
 int ensure_lr_blocks(gpb_ctx* ctx, int E);          // its per-emulator blocks [E][Wcap] in the chain's first context
 bool compaction_applies(const gpb_ctx* ctx);
+// ---- a chain of emulators (gpb_chain.hip) ----------------------------------------------------------------
+constexpr int MAX_CHAIN_CTX = 64;         // emulators of one chain: the context lists of the gpb_chain_* entry points
+inline bool chain_args_ok(gpb_ctx* const* ctxs, int E) { return ctxs && E >= 1 && E <= MAX_CHAIN_CTX && ctxs[0]; }
 // the chain's number of (original) parameters as context c sees it
 inline int64_t sampler_ndim(const gpb_ctx* c) { return c->pmap_d_in > 0 ? c->pmap_d_in : c->d; }
-// The evaluation of the resident samplers (gpb_ptlmc.hip, gpb_smc.hip): lp of the rows X [W, nd], what Chain.log_prob_device
-// writes.  chain_call (gpb_chain_supported(ctxs, E) == 1): gpb_chain_logpost; else the per-emulator sequence for the
-// contexts it rejects (xg: room for the mapped parameters of every parameterTrafoPCA emulator, W * d doubles each).
-inline int chain_eval(gpb_ctx* const* ctxs, int E, bool chain_call, const double* X, int64_t W, int64_t nd, double* lp,
-                      const double* lo, const double* hi, double outside, double inside_const, double* xg) {
-    gpb_ctx* c0 = ctxs[0];
-    if (chain_call) return gpb_chain_logpost(ctxs, E, X, W, lp, lo, hi, outside, inside_const);
-    int rc;
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        const bool mapped = c->pmap_d_in > 0, last = e == E - 1;
-        const double* Xg = X;
-        if (mapped) {
-            if ((rc = gpb_param_map(c, X, W, xg))) { c0->err = c->err; return rc; }
-            Xg = xg;
-            xg += W * c->d;
-        }
-        if (!last || mapped) {
-            if ((rc = gpb_loglike(c, Xg, W, 1, lp, e > 0, nullptr))) { c0->err = c->err; return rc; }
-            if (last && (rc = gpb_box_finish(c, X, W, nd, lo, hi, outside, inside_const, lp))) { c0->err = c->err; return rc; }
-        } else if ((rc = gpb_logpost(c, X, W, lp, e > 0, lo, hi, outside, inside_const))) {
-            c0->err = c->err;
-            return rc;
-        }
-    }
-    return 0;
-}
+// What every entry point that takes a chain asks of its contexts (after chain_args_ok): none null, one device and stream,
+// one number of parameters, likelihood installed (need_like), a parameter map's output the GPs' input.  Sets ctxs[0]'s
+// message to `who` + the reason.  chain_check: and the compacted chain call admits them (gpb_chain_supported answers 1).
+int chain_ctx_check(gpb_ctx* const* ctxs, int E, const char* who, bool need_like = true);
+int chain_check(gpb_ctx* const* ctxs, int E, const char* who);
+// the compacted chain call of checked contexts.  premarked / cmpv: the caller's proposal kernel has taken the prior-box test
+// (1) and gathered the rows inside (2) into ctxs[0]->cmp_X, their count and indices at cmpv (gpb_chain_emcee_run)
+int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
+               const double* hi_dev, double outside, double inside_const, int premarked = 0, const int* cmpv = nullptr);
+// The evaluation of the resident samplers and the gradient: lp of the rows X [W, ndim] of checked contexts on the selected
+// device, what Chain.log_prob_device writes: gpb_chain_logpost where gpb_chain_supported answers 1, else the per-emulator
+// sequence of gpb_param_map / gpb_loglike / gpb_box_finish / gpb_logpost
+int chain_eval(gpb_ctx* const* ctxs, int E, const double* X, int64_t W, double* lp, const double* lo, const double* hi,
+               double outside, double inside_const);
 // test hooks
 int launch_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B,
                      double* C, int b_trans);

@@ -254,7 +254,7 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
                                    const double* temps13_dev, const double* hc_dev, const double* covmat0_dev,
                                    const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
                                    double* save_dev, int64_t nsave, int64_t* naccept_dev, int64_t* nswap_dev) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     gpb_ctx* ctx = ctxs[0];
     if (!theta_dev || !fval_dev || !tune_dev || !temps_dev || !temps13_dev || !hc_dev || !covmat0_dev || !lo_dev ||
         !hi_dev || nsteps < 0 || samptunning < 0 || (save_dev && nsave < 1))
@@ -263,35 +263,19 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
     if (numtemps < 0 || numchain < 1 || T < 2 || T > PTL_MAX_T)
         GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: numtemps + numchain must be 2 .. 4096 with numchain >= 1");
     if (step0 + (uint64_t)nsteps > 0xFFFFFFFFull) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: steps are numbered below 2^32");
+    int rc;
+    if ((rc = chain_ctx_check(ctxs, E, "gpb_chain_ptlmc_run"))) return rc;
     const int64_t nd = sampler_ndim(ctx);
-    int64_t nxg = 0;
-    for (int e = 0; e < E; ++e) {
-        if (!ctxs[e]) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: null context");
-        if (sampler_ndim(ctxs[e]) != nd) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: the emulators disagree on the number of parameters");
-        if (ctxs[e]->device != ctx->device || ctxs[e]->stream != ctx->stream)
-            GPB_FAIL(GPB_E_STATE, "gpb_chain_ptlmc_run: the emulators' contexts must share one device and stream");
-        if (ctxs[e]->pmap_d_in > 0) nxg += T * ctxs[e]->d;
-    }
     if (nd < 1 || nd > PTL_MAX_D) GPB_FAIL(GPB_E_ARG, "gpb_chain_ptlmc_run: 1 .. 256 parameters");
     const bool grad = dfval_dev != nullptr;
-    const bool chain_call = gpb_chain_supported(ctxs, E) == 1;
-    int rc;
-    // the state checks of the evaluation the loop will make, before anything is enqueued (no rows: nothing runs)
+    // the gradient's own state checks before anything is enqueued (no rows: nothing runs); chain_eval has none beyond the above
     double probe = 0.0;
-    if (grad) rc = gpb_chain_logpost_grad(ctxs, E, &probe, 0, &probe, &probe, lo_dev, hi_dev, outside_value, inside_const);
-    else if (chain_call) rc = gpb_chain_logpost(ctxs, E, &probe, 0, &probe, lo_dev, hi_dev, outside_value, inside_const);
-    else {
-        rc = 0;
-        for (int e = 0; e < E && !rc; ++e)
-            if (!ctxs[e]->have_like) { ctx->err = "gpb_chain_ptlmc_run before gpb_like_set"; rc = GPB_E_STATE; }
-    }
-    if (rc) return rc;
+    if (grad && (rc = gpb_chain_logpost_grad(ctxs, E, &probe, 0, &probe, &probe, lo_dev, hi_dev, outside_value, inside_const)))
+        return rc;
     if (nsteps == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    // workspace: rvalo, thetap, grad, the other theta / dfval buffers [T, nd] each; lp, the other fval, the accept flags [T]
-    // each; the mapped parameters of the per-emulator sequence
-    const int64_t need = 5 * T * nd + 3 * T + nxg;
-    if (int rc = ctx_grow(ctx, ctx->ptl_ws, need)) return rc;
+    // workspace: rvalo, thetap, grad, the other theta / dfval buffers [T, nd] each; lp, the other fval, the accept flags [T] each
+    if ((rc = ctx_grow(ctx, ctx->ptl_ws, 5 * T * nd + 3 * T))) return rc;
     double* rvalo = ctx->ptl_ws;
     double* thetap = rvalo + T * nd;
     double* gbuf = thetap + T * nd;
@@ -300,7 +284,6 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
     double* lp = dfvalB + T * nd;
     double* fvalB = lp + T;
     int* acc = reinterpret_cast<int*>(fvalB + T);
-    double* xg = fvalB + 2 * T;
     double *th = theta_dev, *fv = fval_dev, *df = dfval_dev;          // the state alternates between the two buffers
     double *th2 = thetaB, *fv2 = fvalB, *df2 = grad ? dfvalB : nullptr;
     const dim3 gT((unsigned)T);
@@ -312,7 +295,7 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
         if (grad) {
             if ((rc = gpb_chain_logpost_grad(ctxs, E, thetap, T, lp, gbuf, lo_dev, hi_dev, outside_value, inside_const)))
                 return rc;
-        } else if ((rc = chain_eval(ctxs, E, chain_call, thetap, T, nd, lp, lo_dev, hi_dev, outside_value, inside_const, xg))) {
+        } else if ((rc = chain_eval(ctxs, E, thetap, T, lp, lo_dev, hi_dev, outside_value, inside_const))) {
             return rc;
         }
         hipLaunchKernelGGL(k_ptl_accept, gT, dim3(64), 0, ctx->stream, th, fv, df, thetap, lp, grad ? gbuf : nullptr,

@@ -368,29 +368,19 @@ __global__ void k_smc_draws(int64_t N, int d, uint64_t seed, uint32_t stage, uin
 }
 #endif
 
-// the argument checks both entry points share; nxg: doubles the per-emulator sequence needs for its mapped parameters
-int smc_check(gpb_ctx* const* ctxs, int E, int64_t N, const char* who, int64_t& nd, int64_t& nxg) {
+// the argument checks both entry points share (need_like: the move evaluates the chain, the reweighting only its contexts' sizes)
+int smc_check(gpb_ctx* const* ctxs, int E, int64_t N, const char* who, bool need_like, int64_t& nd) {
     gpb_ctx* ctx = ctxs[0];
     if (N < 2 || N > SMC_MAX_N) GPB_FAIL(GPB_E_ARG, std::string(who) + ": 2 .. 1048576 particles");
+    if (int rc = chain_ctx_check(ctxs, E, who, need_like)) return rc;
     nd = sampler_ndim(ctx);
-    nxg = 0;
-    for (int e = 0; e < E; ++e) {
-        if (!ctxs[e]) GPB_FAIL(GPB_E_ARG, std::string(who) + ": null context");
-        if (sampler_ndim(ctxs[e]) != nd) GPB_FAIL(GPB_E_ARG, std::string(who) + ": the emulators disagree on the number of parameters");
-        if (ctxs[e]->device != ctx->device || ctxs[e]->stream != ctx->stream)
-            GPB_FAIL(GPB_E_STATE, std::string(who) + ": the emulators' contexts must share one device and stream");
-        if (ctxs[e]->pmap_d_in > 0) nxg += N * ctxs[e]->d;
-    }
     if (nd < 1 || nd > SMC_MAX_D) GPB_FAIL(GPB_E_ARG, std::string(who) + ": 1 .. 128 parameters");
     return 0;
 }
 
 // workspace of the chain's first context: wgt, cum, lp [N] each; one particle buffer [N, nd] (the gathered rows of a
-// reweighting, the proposals of a move step); cov [nd, nd]; mean [nd]; the mapped parameters of the per-emulator sequence
-int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd, int64_t nxg) {
-    const int64_t need = 3 * N + N * nd + nd * nd + nd + nxg;
-    return ctx_grow(ctx, ctx->smc_ws, need);
-}
+// reweighting, the proposals of a move step); cov [nd, nd]; mean [nd]
+int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd) { return ctx_grow(ctx, ctx->smc_ws, 3 * N + N * nd + nd * nd + nd); }
 }  // namespace
 }  // namespace gpb
 
@@ -399,16 +389,16 @@ using namespace gpb;
 extern "C" int gpb_chain_smc_reweight(gpb_ctx* const* ctxs, int E, int64_t N, uint64_t stage, uint64_t seed,
                                       double ess_fraction, double* x_dev, double* logl_dev, double* state_dev, double* Lc_dev,
                                       int64_t* ancestors_dev, double* mean_dev) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     gpb_ctx* ctx = ctxs[0];
     if (!x_dev || !logl_dev || !state_dev || !Lc_dev) GPB_FAIL(GPB_E_ARG, "gpb_chain_smc_reweight: null pointer");
     if (!(ess_fraction > 0.0 && ess_fraction < 1.0)) GPB_FAIL(GPB_E_ARG, "gpb_chain_smc_reweight: 0 < ess_fraction < 1");
     if (stage > 0xFFFFFFFFull) GPB_FAIL(GPB_E_ARG, "gpb_chain_smc_reweight: stages are numbered below 2^32");
-    int64_t nd, nxg;
+    int64_t nd;
     int rc;
-    if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_reweight", nd, nxg))) return rc;
+    if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_reweight", false, nd))) return rc;
     GPB_HIP(hipSetDevice(ctx->device));
-    if ((rc = smc_workspace(ctx, N, nd, nxg))) return rc;
+    if ((rc = smc_workspace(ctx, N, nd))) return rc;
     double* wgt = ctx->smc_ws;
     double* cum = wgt + N;
     double* lg = cum + N;
@@ -435,29 +425,20 @@ extern "C" int gpb_chain_smc_reweight(gpb_ctx* const* ctxs, int E, int64_t N, ui
 extern "C" int gpb_chain_smc_move(gpb_ctx* const* ctxs, int E, int64_t N, int64_t nsteps, uint64_t step0, uint64_t stage_step0,
                                   uint64_t seed, double* x_dev, double* logl_dev, double* state_dev, const double* Lc_dev,
                                   const double* lo_dev, const double* hi_dev, double outside_value, double inside_const) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     gpb_ctx* ctx = ctxs[0];
     if (!x_dev || !logl_dev || !state_dev || !Lc_dev || !lo_dev || !hi_dev || nsteps < 0)
         GPB_FAIL(GPB_E_ARG, "gpb_chain_smc_move: null pointer or negative size");
     if (step0 + (uint64_t)nsteps > 0xFFFFFFFFull || stage_step0 + (uint64_t)nsteps > 0xFFFFFFFFull)
         GPB_FAIL(GPB_E_ARG, "gpb_chain_smc_move: steps are numbered below 2^32");
-    int64_t nd, nxg;
+    int64_t nd;
     int rc;
-    if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_move", nd, nxg))) return rc;
-    const bool chain_call = gpb_chain_supported(ctxs, E) == 1;
-    // the state checks of the evaluation the loop will make, before anything is enqueued (no rows: nothing runs)
-    double probe = 0.0;
-    if (chain_call) rc = gpb_chain_logpost(ctxs, E, &probe, 0, &probe, lo_dev, hi_dev, outside_value, inside_const);
-    else
-        for (int e = 0; e < E && !rc; ++e)
-            if (!ctxs[e]->have_like) { ctx->err = "gpb_chain_smc_move before gpb_like_set"; rc = GPB_E_STATE; }
-    if (rc) return rc;
+    if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_move", true, nd))) return rc;      // (all the state checks chain_eval has)
     if (nsteps == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    if ((rc = smc_workspace(ctx, N, nd, nxg))) return rc;
+    if ((rc = smc_workspace(ctx, N, nd))) return rc;
     double* lp = ctx->smc_ws + 2 * N;
     double* xp = lp + N;
-    double* xg = ctx->smc_ws + 3 * N + N * nd + nd * nd + nd;
     const int d = (int)nd;
     const size_t lds = sizeof(double) * (size_t)(nd * nd + 4 * nd);
     if (lds > 65536)
@@ -467,7 +448,7 @@ extern "C" int gpb_chain_smc_move(gpb_ctx* const* ctxs, int E, int64_t N, int64_
     for (int64_t n = 0; n < nsteps; ++n) {
         const uint32_t k = (uint32_t)(step0 + (uint64_t)n);
         hipLaunchKernelGGL(k_smc_propose, dim3(gp), dim3(256), lds, ctx->stream, x_dev, Lc_dev, state_dev, N, d, seed, k, xp);
-        if ((rc = chain_eval(ctxs, E, chain_call, xp, N, nd, lp, lo_dev, hi_dev, outside_value, inside_const, xg))) return rc;
+        if ((rc = chain_eval(ctxs, E, xp, N, lp, lo_dev, hi_dev, outside_value, inside_const))) return rc;
         hipLaunchKernelGGL(k_smc_accept, dim3(ga), dim3(256), 0, ctx->stream, x_dev, logl_dev, xp, lp, state_dev, N, d, seed, k,
                            outside_value, (double)(stage_step0 + (uint64_t)n + 1));
     }

@@ -1,7 +1,7 @@
 // gpb_stretch.hip — the emcee-equivalent stretch move and its device-resident loop over a chain of emulators.
 //   k_propose / k_accept   emcee StretchMove (a=2) as driven by     src/mcmc.py:68-92,372-412
-//   gpb_chain_logpost / gpb_chain_emcee_run: the log-posterior batches go through gpb_internal.h (launch_compact,
-//   launch_kcross_group, launch_vsq, launch_loglike*) like those of the other samplers (gpb_ptlmc.hip, gpb_smc.hip)
+//   gpb_chain_emcee_run: the log-posterior batches are those of gpb_chain.hip (chain_rows, whose compaction the proposal
+//   kernels here take over; chain_eval for one uncompacted emulator), as for the other samplers (gpb_ptlmc.hip, gpb_smc.hip)
 #include "gpb_internal.h"
 #include "philox.h"
 #include <math.h>
@@ -445,130 +445,6 @@ __global__ void k_fill(double* __restrict__ x, int64_t n, double v) {
     if (i < n) x[i] = v;
 }
 
-// ---- chains of several emulators ---------------------------------------------------------------------
-// Chain._predict concatenates the emulators' observables and the covariance is block-diagonal over them
-// (src/mcmc.py:153-166), so the log-likelihood is the sum of the emulators' blocks; all emulators see the same rows of
-// the same parameter space (those with a parameter map, src/emulator.py:492-551, through gpb_param_map).
-namespace {
-// parameters of the CHAIN (a parameter map's d_in; the GPs' own d is bounded by 64 in gpb_gp_set).  The proposal kernels
-// take any number; k_compact_mark stages 256 rows of it in LDS in tiles, so the bound is only a sanity limit.
-constexpr int64_t MAX_CHAIN_NDIM = 512;
-
-// Why the compacted chain path does not admit these contexts (why == nullptr: it does): same device, stream and parameter
-// space; likelihood installed; a block likelihood kernel applies.  `why` continues the caller's name.
-struct ChainRefusal {
-    int code;
-    const char* why;
-};
-ChainRefusal chain_refusal(gpb_ctx* const* ctxs, int E) {
-    const gpb_ctx* c0 = ctxs[0];
-    for (int e = 0; e < E; ++e) {
-        const gpb_ctx* c = ctxs[e];
-        if (!c) return {GPB_E_ARG, ": null context"};
-        if (!c->have_like) return {GPB_E_STATE, " before gpb_like_set"};
-        if (c->device != c0->device || c->stream != c0->stream)
-            return {GPB_E_STATE, ": the emulators' contexts must share one device and stream"};
-        if (sampler_ndim(c) != sampler_ndim(c0)) return {GPB_E_ARG, ": the emulators disagree on the number of parameters"};
-        if (!compaction_applies(c))
-            return {GPB_E_STATE, ": needs the block likelihood kernels (PCA mode, M <= 64 or npc <= 16) for every emulator"};
-        if (c->pmap_d_in > 0 && c->pmap_d_out != c->d) return {GPB_E_STATE, ": a parameter map's output must be the GPs' input"};
-    }
-    if (sampler_ndim(c0) > MAX_CHAIN_NDIM) return {GPB_E_ARG, ": more than 512 chain parameters"};
-    return {0, nullptr};
-}
-int chain_check(gpb_ctx* const* ctxs, int E, const char* who) {
-    gpb_ctx* ctx = ctxs[0];
-    const ChainRefusal r = chain_refusal(ctxs, E);
-    if (r.why) GPB_FAIL(r.code, std::string(who) + r.why);
-    return 0;
-}
-
-// log-posterior of rows X[W][ndim] over all emulators, rows inside the box only (ctxs[0] owns the compaction)
-int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
-               const double* hi_dev, double outside, double inside_const, int premarked = 0, const int* cmpv = nullptr) {
-    gpb_ctx* c0 = ctxs[0];
-    int rc;
-    for (int e = 0; e < E; ++e)
-        if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
-    if ((rc = ensure_lr_blocks(c0, E))) return rc;
-    if ((rc = launch_compact(c0, X_dev, W, sampler_ndim(c0), lo_dev, hi_dev, outside, ll_dev, premarked))) return rc;
-    if (!cmpv) cmpv = c0->cmp_idx;                     // (count, -, -, -, indices ...) of the rows inside the box
-    // Three passes over the emulators (each kernel sees what it would see in its own emulator's sequence: same bits):
-    // (1) parameter maps, then K*^T and the mean partials — ONE launch per run of emulators of equal padded size
-    //     (k_kcross_multi);
-    // (2) V = L^-1 K*^T with the fused sum of squares: ONE launch for each run of emulators whose designs pad to the same
-    //     Np (the reference's analyses: nine emulators on one design) instead of one partly filled launch per emulator;
-    // (3) the block log-likelihoods, added up in emuList order: one launch that walks the emulators (k_loglike_lowrank_multi)
-    //     when every block takes the low-rank kernel, else one launch per emulator.
-    const double* Xg[64];
-    gpb_ctx* mapped[64];
-    int nmapped = 0;
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        Xg[e] = c0->cmp_X;
-        c->hint_from = c0;
-        if (c->pmap_d_in > 0) {                        // this emulator's GPs see the PCA-reduced parameters
-            mapped[nmapped++] = c;
-            Xg[e] = c->Xs;
-        }
-    }
-    if (nmapped > 1 && c0->chain_batch) {              // the maps of all mapped emulators over the gathered rows: one launch
-        if ((rc = launch_param_maps(mapped, nmapped, c0->cmp_X, W))) { c0->err = mapped[0]->err; return rc; }
-    } else {
-        for (int i = 0; i < nmapped; ++i)
-            if ((rc = gpb_param_map(mapped[i], c0->cmp_X, W, mapped[i]->Xs))) { c0->err = mapped[i]->err; return rc; }
-    }
-    for (int e = 0; e < E;) {              // K*^T: one launch per run of emulators of equal padded size and PADDED input
-        int n = 1;                                     // count (parameterTrafoPCA emulators keep 17-19 of 20 inputs each: one launch)
-        while (c0->chain_batch && e + n < E && ctxs[e + n]->Np == ctxs[e]->Np && ctxs[e + n]->dpad == ctxs[e]->dpad && n < 32) ++n;
-        if ((rc = launch_kcross_group(ctxs + e, Xg + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
-        e += n;
-    }
-    for (int e = 0; e < E;) {
-        int n = 1, gps = (int)ctxs[e]->P;
-        while (c0->chain_batch && e + n < E && ctxs[e + n]->Np == ctxs[e]->Np && gps + (int)ctxs[e + n]->P <= GPB_MAX_MULTI_GP) {
-            gps += (int)ctxs[e + n]->P;
-            ++n;
-        }
-        if ((rc = launch_vsq(ctxs + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
-        e += n;
-    }
-    bool taken;
-    if ((rc = launch_loglike_lowrank_chain(ctxs, E, W, ll_dev, cmpv, inside_const, &taken)) || taken) return rc;
-    for (int e = 0; e < E; ++e) {
-        gpb_ctx* c = ctxs[e];
-        const bool fused = loglike_fuses_finalize(c, W);
-        if ((!fused && (rc = launch_finalize(c, W, true))) ||
-            (rc = launch_loglike(c, W, ll_dev, e > 0, fused, nullptr, nullptr, nullptr, outside,
-                                 e == E - 1 ? inside_const : 0.0, cmpv))) {
-            c0->err = c->err;
-            return rc;
-        }
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" int gpb_chain_supported(gpb_ctx* const* ctxs, int E) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    int n = 1;
-    while (n < E && ctxs[n]) ++n;                      // the contexts before the first null one are judged first, in order
-    if (chain_refusal(ctxs, n).why) return 0;
-    return n < E ? GPB_E_ARG : 1;                      // a null context is the caller's error, all else an answer
-}
-
-extern "C" int gpb_chain_logpost(gpb_ctx* const* ctxs, int E, const double* Xs_dev, int64_t W, double* ll_dev,
-                                 const double* lo_dev, const double* hi_dev, double outside_value, double inside_const) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
-    gpb_ctx* ctx = ctxs[0];
-    if (!Xs_dev || !ll_dev || !lo_dev || !hi_dev || W < 0) GPB_FAIL(GPB_E_ARG, "gpb_chain_logpost: null pointer or negative size");
-    int rc = chain_check(ctxs, E, "gpb_chain_logpost");
-    if (rc) return rc;
-    if (W == 0) return 0;
-    GPB_HIP(hipSetDevice(ctx->device));
-    return chain_rows(ctxs, E, Xs_dev, W, ll_dev, lo_dev, hi_dev, outside_value, inside_const);
-}
-
 namespace {
 // What gpb_chain_emcee_run decides before it enqueues anything: argument checks, the share of every batch this rank
 // evaluates, which of the step's kernels are fused, and every workspace it needs — all of which can fail on ONE rank only
@@ -577,14 +453,14 @@ namespace {
 struct EmceePlan {
     int64_t nh = 0, d = 0, chunk = 0, r0 = 0;
     int R = 1;
-    bool sim = false, plain = false, fused = false, premark = false, fuse_ap = false, balanced = false;
+    bool sim = false, plain = false, premark = false, fuse_ap = false, balanced = false;
     int pre = 0;
 };
 
 int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     gpb_ctx* ctx = ctxs[0];
     if (nwalkers < 2 || (nwalkers & 1) || nwalkers > (1ll << 30)) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: nwalkers must be even, 2 .. 2^30");
-    // one emulator without a parameter map may also run uncompacted (tune key 27 = 0, non-PCA modes): gpb_logpost's sequence
+    // one emulator without a parameter map may also run uncompacted (tune key 27 = 0, non-PCA modes): chain_eval's gpb_logpost
     pl.plain = E == 1 && ctx->pmap_d_in == 0 && !compaction_applies(ctx);
     int rc;
     if (pl.plain) {
@@ -612,7 +488,6 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     // proposal workspace: two sets of q[nh][d], factor[nh], lpq[nh] (the fused accept + proposal kernel reads one set and
     // writes the other) and a second log-probability vector [nwalkers]
     if ((rc = ctx_grow(ctx, ctx->mc_ws, 2 * nh * (d + 3)))) return rc;
-    pl.fused = pl.plain && loglike_fuses_finalize(ctx, chunk);
     // the gather kernel counts the flags in front of each of its workgroups itself: fine for a rank's rows of an
     // ensemble, quadratic for very large batches, which keep the marking kernel with its per-workgroup counts
     pl.premark = !pl.plain && ctx->premark && chunk <= 16384;
@@ -636,7 +511,7 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
 }  // namespace
 
 extern "C" int gpb_chain_emcee_prepare(gpb_ctx* const* ctxs, int E, int64_t nwalkers) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     EmceePlan pl;
     return emcee_plan(ctxs, E, nwalkers, pl);
 }
@@ -645,7 +520,7 @@ extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev,
                                    int64_t nsteps, uint64_t seed, uint64_t step0, double a, int randomize_split,
                                    const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
                                    double* chain_dev, double* lpchain_dev, int64_t* naccept_dev) {
-    if (!ctxs || E < 1 || E > 64 || !ctxs[0]) return GPB_E_ARG;
+    if (!chain_args_ok(ctxs, E)) return GPB_E_ARG;
     gpb_ctx* ctx = ctxs[0];
     if (!pos_dev || !lp_dev || !lo_dev || !hi_dev || nsteps < 0) GPB_FAIL(GPB_E_ARG, "gpb_chain_emcee_run: null pointer or negative size");
     EmceePlan pl;
@@ -653,8 +528,7 @@ extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev,
     if (rc) return rc;
     const int64_t nh = pl.nh, d = pl.d, chunk = pl.chunk, r0 = pl.r0;
     const int R = pl.R, pre = pl.pre;
-    const bool sim = pl.sim, plain = pl.plain, fused = pl.fused, premark = pl.premark, fuse_ap = pl.fuse_ap,
-               balanced = pl.balanced;
+    const bool sim = pl.sim, plain = pl.plain, premark = pl.premark, fuse_ap = pl.fuse_ap, balanced = pl.balanced;
     double* qs[2] = {ctx->mc_ws, ctx->mc_ws + nh * (d + 2)};
     double* factors[2] = {qs[0] + nh * d, qs[1] + nh * d};
     double* lpqs[2] = {factors[0] + nh, factors[1] + nh};
@@ -717,10 +591,7 @@ extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev,
         // this rank's rows of the batch: [compaction to the rows inside the box,] per emulator K*^T + mean partials,
         // V = L^-1 K*^T with the fused sum of squares, block log-likelihood (+ prior box + constant)
         if (plain) {
-            if ((rc = launch_predict(ctx, q + r0 * d, chunk, true, !fused))) return rc;
-            if ((rc = launch_loglike(ctx, chunk, lpq + r0, false, fused, q + r0 * d, lo_dev, hi_dev, outside_value,
-                                     inside_const)))
-                return rc;
+            if ((rc = chain_eval(ctxs, E, q + r0 * d, chunk, lpq + r0, lo_dev, hi_dev, outside_value, inside_const))) return rc;
         } else if ((rc = chain_rows(ctxs, E, q + r0 * d, chunk, lpq + r0, lo_dev, hi_dev, outside_value, inside_const, pre,
                                     cmpv))) {
             return rc;

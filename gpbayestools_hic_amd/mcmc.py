@@ -250,25 +250,32 @@ class Chain:
 
     use_chain_call = True                        # False: sequence the emulators from Python (A/B tests)
 
-    def _chain_contexts(self):
-        """(engines, ctypes array of their contexts) when the C ABI can evaluate the whole chain in one call
-        (gpb_chain_logpost / gpb_chain_emcee_run: rows outside the prior box skipped, one emulator after the other on
-        one stream), else None.  Call after _prepare_blocks()."""
+    def _contexts(self):
+        """(engines, ctypes array of their contexts, count) of emuList, ready for a C call that takes the chain: every
+        emulator has its block of the experimental data, a fitted engine, and enqueues on torch's current stream."""
         from . import _native as nat
-        if not (self.use_chain_call and self._native()):
-            return None
+        self._prepare_blocks()
         engs = [e._engine_ready() for e in self.emuList]
         for g in engs:
             g._need_data()
             g._track_stream()
-        arr = (nat.C.c_void_p * len(engs))(*[g.h for g in engs])
-        if engs[0].lib.gpb_chain_supported(arr, len(engs)) != 1:
+        return engs, (nat.C.c_void_p * len(engs))(*[g.h for g in engs]), len(engs)
+
+    def _chain_contexts(self):
+        """(engines, ctypes array of their contexts) when the C ABI can evaluate the whole chain in one call
+        (gpb_chain_logpost / gpb_chain_emcee_run: rows outside the prior box skipped, one emulator after the other on
+        one stream), else None."""
+        if not (self.use_chain_call and self._native()):
             return None
-        return engs, arr
+        engs, arr, n = self._contexts()
+        return (engs, arr) if engs[0].lib.gpb_chain_supported(arr, n) == 1 else None
 
     def log_prob_device(self, X_dev, out=None, outside=-np.inf, lo_dev=None, hi_dev=None):
         """Device-resident log-posterior: X_dev torch.float64 cuda [W,ndim] -> lp [W] (no host
-        sync).  Used by the resident sampler; `log_posterior`/`log_likelihood` wrap it."""
+        sync).  Used by the resident sampler; `log_posterior`/`log_likelihood` wrap it.
+        The per-emulator sequence below is the Python counterpart of chain_eval (csrc/gpb_chain.hip), which the C-driven
+        samplers and the gradient run; it goes through the public per-emulator calls (use_chain_call = False: the A/B path the
+        tests compare the C paths against).  A change of the rule goes into both."""
         import torch
         from . import _native as nat
         self._prepare_blocks()
@@ -426,12 +433,7 @@ class Chain:
         if X.shape[1] != self.ndim:
             raise ValueError("X has %d columns, the chain has %d parameters" % (X.shape[1], self.ndim))
         dev = torch.device("cuda", self.device)
-        self._prepare_blocks()
-        engs = [e._engine_ready() for e in self.emuList]
-        for g in engs:
-            g._need_data()
-            g._track_stream()
-        arr = (nat.C.c_void_p * len(engs))(*[g.h for g in engs])
+        engs, arr, nemu = self._contexts()
         e0 = engs[0]
         lo_dev, hi_dev = self._box(dev)
         # slabs: the gradient keeps beta = K^-1 k* ([P, rows, N] doubles) per emulator besides the predict workspaces
@@ -444,7 +446,7 @@ class Chain:
             n = Xd.shape[0]
             ll = torch.empty(n, dtype=torch.float64, device=dev)
             gd = torch.empty((n, self.ndim), dtype=torch.float64, device=dev)
-            e0._ck(e0.lib.gpb_chain_logpost_grad(arr, len(engs), nat.ptr(Xd), n, nat.ptr(ll), nat.ptr(gd), nat.ptr(lo_dev),
+            e0._ck(e0.lib.gpb_chain_logpost_grad(arr, nemu, nat.ptr(Xd), n, nat.ptr(ll), nat.ptr(gd), nat.ptr(lo_dev),
                                                  nat.ptr(hi_dev), float(outside), EXTRA_STD_CONST))
             if not self.use_chain_call:              # (the A/B switch: the value from the per-emulator sequence)
                 ll = self.log_prob_device(Xd, outside=outside)

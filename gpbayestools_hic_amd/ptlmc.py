@@ -129,21 +129,13 @@ class PTLMCSampler:
                     dfval=None if self.dfval is None else self.dfval.cpu().numpy(), tau=float(tune[0]),
                     numtimes=float(tune[1]), k=self.k)
 
-    def _contexts(self):
-        ch = self.chain
-        ch._prepare_blocks()
-        engs = [e._engine_ready() for e in ch.emuList]
-        for g in engs:
-            g._need_data()
-            g._track_stream()
-        return engs[0], (nat.C.c_void_p * len(engs))(*[g.h for g in engs]), len(engs)
-
     def run(self, nsteps):
         """enqueue `nsteps` steps from step self.k (asynchronous: nothing waits for the device)"""
         nsteps = int(nsteps)
         if nsteps <= 0:
             return
-        e0, arr, E = self._contexts()
+        engs, arr, E = self.chain._contexts()
+        e0 = engs[0]
         lo, hi = self.chain._box(self.dev)
         e0._ck(e0.lib.gpb_chain_ptlmc_run(
             arr, E, self.numtemps, self.numchain, nsteps, self.k, self.seed, self.samptunning, self.taracc,

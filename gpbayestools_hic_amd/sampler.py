@@ -107,8 +107,7 @@ class StretchSampler:
             # one emulator without a parameter map also runs uncompacted (non-PCA modes, tune("compact", 0))
             if len(emus) != 1 or getattr(emus[0], "parameterTrafoPCA_", False) or eng.d != self.ndim:
                 return None
-            eng._track_stream()
-            cc = [eng], (nat.C.c_void_p * 1)(eng.h)
+            cc = ch._contexts()
         return eng, cc[1], len(cc[0])
 
     def _nan_count(self, eng):

@@ -101,18 +101,10 @@ class SMCSampler:
                    s=self.s)
         return out
 
-    def _contexts(self):
-        ch = self.chain
-        ch._prepare_blocks()
-        engs = [e._engine_ready() for e in ch.emuList]
-        for g in engs:
-            g._need_data()
-            g._track_stream()
-        return engs[0], (nat.C.c_void_p * len(engs))(*[g.h for g in engs]), len(engs)
-
     def reweight(self):
         """enqueue one stage's reweighting, resampling and preconditioning (asynchronous)"""
-        e0, arr, E = self._contexts()
+        engs, arr, E = self.chain._contexts()
+        e0 = engs[0]
         e0._ck(e0.lib.gpb_chain_smc_reweight(arr, E, self.N, self.stage, self.seed, self.ess_fraction, nat.ptr(self.x),
                                              nat.ptr(self.logl), nat.ptr(self.block), nat.ptr(self.Lc),
                                              nat.ptr(self.ancestors), nat.ptr(self.mean)))
@@ -124,7 +116,8 @@ class SMCSampler:
         nsteps = int(nsteps)
         if nsteps <= 0:
             return
-        e0, arr, E = self._contexts()
+        engs, arr, E = self.chain._contexts()
+        e0 = engs[0]
         lo, hi = self.chain._box(self.dev)
         e0._ck(e0.lib.gpb_chain_smc_move(arr, E, self.N, nsteps, self.k, self.s, self.seed, nat.ptr(self.x), nat.ptr(self.logl),
                                          nat.ptr(self.block), nat.ptr(self.Lc), nat.ptr(lo), nat.ptr(hi), OUTSIDE,

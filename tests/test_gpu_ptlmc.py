@@ -128,12 +128,20 @@ def test_single_steps_match_restatement(tmp_path, gradient):
     assert s.naccept.sum().item() > 0 and s.nswap.sum().item() > 0
 
 
+@pytest.mark.parametrize("rejected", [False, True])
 @pytest.mark.parametrize("gradient", [False, True])
-def test_single_steps_two_emulators_one_mapped(tmp_path, gradient):
-    """a chain of two emulators, the second with parameterTrafoPCA (the per-emulator sequence of the evaluation)"""
+def test_single_steps_two_emulators_one_mapped(tmp_path, gradient, rejected):
+    """a chain of two emulators, the second with parameterTrafoPCA.  rejected: with the box compaction switched off
+    gpb_chain_supported turns the chain down and the per-emulator sequence (parameter map, gpb_loglike, gpb_box_finish)
+    evaluates the proposals; otherwise the chain call does"""
     from gpbayestools_hic_amd.workload import build_multi_chain
     chain, emus, info = build_multi_chain([(128, 12, 3, "RBF"), (112, 10, 3, "Matern25")], 20, workdir=str(tmp_path),
                                           mapped=[False, True])
+    if rejected:
+        for e in emus:
+            e._engine_ready().tune("compact", 0)
+    chain._prepare_blocks()
+    assert (chain._chain_contexts() is None) == rejected
     s, temps, hc, cov0 = _sampler(chain, info["xstar"], 4, 4, gradient, samptunning=12, nsave=8)
     near = _step_by_step(chain, s, temps, hc, cov0, 16)
     assert near <= 2

@@ -258,7 +258,8 @@ def test_limits_and_refusals(tmp_path):
     from gpbayestools_hic_amd.smc import SMCSampler
     chain, emu, xstar = _emulator(str(tmp_path), 160, 4, 6, 3)
     s = _sampler(chain, 64)
-    e0, arr, E = s._contexts()
+    engs, arr, E = chain._contexts()
+    e0 = engs[0]
     lo, hi = chain._box(s.dev)
     big = torch.zeros(8, dtype=torch.float64, device="cuda:0")
     for N in (1, 0, (1 << 20) + 1):           # checked before anything is touched
@@ -331,7 +332,8 @@ def test_more_parameters_than_the_limit_is_an_argument_error(tmp_path):
     chain = _wide_chain(str(tmp_path), 129)
     s = _sampler(chain, 64)                   # (the start particles are evaluated by the chain call, which has no such limit)
     assert np.all(np.isfinite(s.logl.cpu().numpy()))
-    e0, arr, E = s._contexts()
+    engs, arr, E = chain._contexts()
+    e0 = engs[0]
     lo, hi = chain._box(s.dev)
     assert e0.lib.gpb_chain_smc_reweight(arr, E, 64, 0, 1, 0.5, nat.ptr(s.x), nat.ptr(s.logl), nat.ptr(s.block), nat.ptr(s.Lc),
                                          None, None) == -1
