@@ -751,6 +751,32 @@ extern "C" int gpb_emu_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on
     return 0;
 }
 
+// gpb_emu_predict without the [W, M, M] array: the same launch_predict, then the same ObsModel calls for the mean and the
+// covariance diagonal alone, written observable-major (k_obs_diag, gpb_like.hip)
+extern "C" int gpb_emu_predict_diag(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device, const double* extra_std,
+                                    double* mean_T, double* var_T, int64_t ld) {
+    if (!ctx || !Xs || !mean_T || W < 0) return GPB_E_ARG;
+    if (!ctx->have_transform) GPB_FAIL(GPB_E_STATE, "gpb_emu_predict_diag before gpb_emu_set_transform");
+    if (ld < W) GPB_FAIL(GPB_E_ARG, "gpb_emu_predict_diag: ld < W");
+    if (W == 0) return 0;
+    GPB_HIP(hipSetDevice(ctx->device));
+    const double *Xs_dev, *estd_dev;
+    int rc = stage_inputs(ctx, Xs, W, on_device, extra_std, &Xs_dev, &estd_dev);
+    if (rc) return rc;
+    if ((rc = launch_predict(ctx, Xs_dev, W, var_T != nullptr))) return rc;
+    if (on_device) return launch_obs_diag(ctx, W, estd_dev, mean_T, var_T, ld);
+    const int64_t M = ctx->M;
+    if ((rc = ensure_out(ctx, (var_T ? 2 : 1) * M * W))) return rc;
+    double* dm = ctx->out_stage;
+    double* dv = var_T ? ctx->out_stage + M * W : nullptr;
+    if ((rc = launch_obs_diag(ctx, W, estd_dev, dm, dv, W))) return rc;
+    const size_t row = sizeof(double) * W, pitch = sizeof(double) * ld;
+    GPB_HIP(hipMemcpy2DAsync(mean_T, pitch, dm, row, row, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+    if (var_T) GPB_HIP(hipMemcpy2DAsync(var_T, pitch, dv, row, row, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- closed-form cross-validation (gpb_cv.hip)
 extern "C" int gpb_gp_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, const int32_t* fold_ptr_host, int64_t nf,
                          int on_device, double* mean, double* var, double* cov) {

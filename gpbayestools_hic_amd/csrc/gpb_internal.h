@@ -339,6 +339,18 @@ int launch_sobol_obs(gpb_ctx* ctx, const double* e_dev, const double* H_dev, dou
 int launch_sobol_main_effect(gpb_ctx* ctx, int64_t j, const double* t_dev, int64_t G, double* zbuf_dev, double* curve_dev);
 // likelihood (gpb_like.hip)
 int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev, double* cov_dev);
+// the same batch's mean and covariance DIAGONAL, observable-major: mean_T / var_T [M][ld] (var_T may be nullptr), columns < W
+int launch_obs_diag(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_T, double* var_T, int64_t ld);
+// posterior-predictive summaries over the sample axis of [M][ld] arrays (gpb_ppd.hip): one workgroup per row and kernel.
+// k [2 nq]: the ranks of the order statistics, (k_i, min(k_i + 1, S - 1)) per level.  Outputs that are nullptr are skipped.
+constexpr int PPD_MAX_Q = 16;
+struct PpdLevels {
+    double q[PPD_MAX_Q];
+    long long k[2 * PPD_MAX_Q];
+    int nq;
+};
+int launch_ppd(gpb_ctx* ctx, const double* mu_T, const double* var_T, int64_t M, int64_t S, int64_t ld, const PpdLevels& lv,
+               const double* vadd, const double* yobs, double* moments, double* order, double* mixq, double* pit);
 // true when launch_loglike will take the block log-likelihood kernels that sum the partials themselves
 bool loglike_fuses_finalize(const gpb_ctx* ctx, int64_t W);
 // cmp_dev (optional): the batch was compacted by launch_compact: row w of the workspace is row cmp_dev[4 + w] of ll_dev

@@ -19,7 +19,9 @@ struct ObsModel {
                                         const double* C0_)
         : P(P_), M(M_), no_pca(mode == GPB_MODE_NO_PCA || mode == GPB_MODE_NO_PCA_EXPDIAG),
           expdiag(mode == GPB_MODE_EXPDIAG || mode == GPB_MODE_NO_PCA_EXPDIAG), A(A_), mu(mu_), scale(scale_), C0(C0_) {}
-    __device__ __forceinline__ double mean(const double* zm, int m) const {
+    // (zm, zv, mo: anything indexable — an array in LDS, or a view of one walker's column of the predict workspace)
+    template <class ZM>
+    __device__ __forceinline__ double mean(const ZM& zm, int m) const {
         double v;
         if (!no_pca) {
             v = 0.0;
@@ -31,7 +33,8 @@ struct ObsModel {
         if (expdiag) v = exp(v);                                             // :567-568
         return v;
     }
-    __device__ __forceinline__ double cov(const double* zv, const double* mo, int i, int j) const {
+    template <class ZV, class MO>
+    __device__ __forceinline__ double cov(const ZV& zv, const MO& mo, int i, int j) const {
         double v;
         if (!no_pca) {
             if (expdiag && i != j) v = 0.0;
@@ -86,6 +89,53 @@ int launch_obs(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_dev
     hipLaunchKernelGGL(k_obs, dim3((unsigned)W), dim3(256), sh, ctx->stream, ctx->mean_pc,
                        cov_dev ? ctx->var_pc : nullptr, estd_dev, ctx->Wld, (int)ctx->P, (int)ctx->M, ctx->mode,
                        ctx->A, ctx->mu, ctx->scale, ctx->C0, mean_dev, cov_dev);
+    GPB_HIP(hipGetLastError());
+    return 0;
+}
+
+// One walker's column of the predict workspace [P][Wld] as ObsModel sees k_obs's LDS copies: zm[p], zv[p] (+ extra_std^2)
+struct PcMeanCol {
+    const double* col;
+    int64_t Wld;
+    __device__ __forceinline__ double operator[](int p) const { return col[(int64_t)p * Wld]; }
+};
+struct PcVarCol {
+    const double* col;
+    int64_t Wld;
+    double e2;        // fl(extra_std^2), rounded on its own as k_obs forms it (__dmul_rn: never contracted into the sum)
+    __device__ __forceinline__ double operator[](int p) const { return col[(int64_t)p * Wld] + e2; }        // src/emulator.py:578-579
+};
+struct OneValue {
+    double v;
+    __device__ __forceinline__ double operator[](int) const { return v; }
+};
+
+// diagonal only, observable-major (gpb_emu_predict_diag): thread (lane = walker, y = observable) forms mean_T[m][w] = k_obs's
+// mean[w][m] and var_T[m][w] = its cov[w][m][m] by the same ObsModel calls.  Walkers on the lanes: the reads of mean_pc / var_pc
+// [P][Wld] and the writes of the [M][ld] outputs are contiguous per wave; nothing of size M x M is formed.
+constexpr int DIAG_ROWS = 4;
+__global__ __launch_bounds__(64 * DIAG_ROWS) void k_obs_diag(const double* __restrict__ mean_pc, const double* __restrict__ var_pc,
+                                                             const double* __restrict__ estd, int64_t W, int64_t Wld, int P, int M,
+                                                             int mode, const double* __restrict__ A, const double* __restrict__ mu,
+                                                             const double* __restrict__ scale, const double* __restrict__ C0,
+                                                             double* __restrict__ mean_T, double* __restrict__ var_T, int64_t ld) {
+    const int64_t w = blockIdx.x * (int64_t)64 + threadIdx.x;
+    const int m = blockIdx.y * DIAG_ROWS + threadIdx.y;
+    if (w >= W || m >= M) return;
+    const ObsModel obs(P, M, mode, A, mu, scale, C0);
+    const double v = obs.mean(PcMeanCol{mean_pc + w, Wld}, m);
+    mean_T[(int64_t)m * ld + w] = v;
+    if (!var_T) return;
+    const double e = estd ? estd[w] : 0.0;
+    var_T[(int64_t)m * ld + w] = obs.cov(PcVarCol{var_pc + w, Wld, __dmul_rn(e, e)}, OneValue{v}, m, m);
+}
+
+int launch_obs_diag(gpb_ctx* ctx, int64_t W, const double* estd_dev, double* mean_T, double* var_T, int64_t ld) {
+    const int64_t gy = (ctx->M + DIAG_ROWS - 1) / DIAG_ROWS;
+    if (gy > 65535) GPB_FAIL(GPB_E_ARG, "gpb_emu_predict_diag: more than 262140 observables");
+    hipLaunchKernelGGL(k_obs_diag, dim3((unsigned)((W + 63) / 64), (unsigned)gy), dim3(64, DIAG_ROWS), 0, ctx->stream, ctx->mean_pc,
+                       var_T ? ctx->var_pc : nullptr, estd_dev, W, ctx->Wld, (int)ctx->P, (int)ctx->M, ctx->mode, ctx->A, ctx->mu,
+                       ctx->scale, ctx->C0, mean_T, var_T, ld);
     GPB_HIP(hipGetLastError());
     return 0;
 }

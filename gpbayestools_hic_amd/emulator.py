@@ -59,6 +59,34 @@ class SobolIndices:
         return "SobolIndices(nobs=%d, ndim=%d)" % self.first_order.shape
 
 
+class PosteriorPredictive:
+    """What the posterior predicts for every observable, over all S samples of a chain (Chain.posterior_predictive): quantiles
+    [nq] the levels asked for; mean [nobs] = E_s mu; std_emulator = sqrt(E_s sigma^2), the emulator's own uncertainty;
+    std_parameter = sqrt(E_s (mu - E mu)^2), the spread of the means over the posterior; std = sqrt of the sum of the two
+    variances (law of total variance); band [nq, nobs] = np.percentile of the means at the levels (the band without the
+    emulator's uncertainty); predictive [nq, nobs] = the quantiles of the mixture 1/S sum_s N(mu_s, sigma_s^2) (the band with
+    it); pit [nobs] = that mixture's CDF, widened by the experimental variance, at the measurement: the per-observable
+    posterior-predictive p-value; n_samples = S."""
+
+    def __init__(self, quantiles, mean, std_emulator, std_parameter, std, band, predictive, pit, n_samples):
+        self.quantiles, self.mean, self.std_emulator, self.std_parameter, self.std = quantiles, mean, std_emulator, std_parameter, std
+        self.band, self.predictive, self.pit, self.n_samples = band, predictive, pit, int(n_samples)
+
+    def __repr__(self):
+        return "PosteriorPredictive(nobs=%d, n_samples=%d, quantiles=%s)" % (self.mean.shape[0], self.n_samples, tuple(self.quantiles))
+
+
+def percentile_from_order(order, q, S):
+    """np.percentile(x, 100 q) (the default "linear" method) from the two order statistics order [..., nq, 2] = x_(k), x_(k + 1) at
+    k = floor(q (S - 1)), by numpy's own interpolation rule: lo + (hi - lo) g for g < 1/2, else hi - (hi - lo) (1 - g)."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1)
+    virt = q * (S - 1)
+    g = virt - np.floor(virt)
+    lo, hi = order[..., 0], order[..., 1]
+    diff = hi - lo
+    return np.where(g >= 0.5, hi - diff * (1.0 - g), lo + diff * g)
+
+
 class DesignProposal:
     """Where the next model runs go (Emulator.propose_design, Chain.propose_design): points [n_new, ndim] = the picked candidates
     in pick order, indices [n_new] into the candidates, gain [n_new] = the drop of the weighted reference-averaged posterior
@@ -762,6 +790,24 @@ class Emulator:
             else:
                 mean[sl] = part
         return (mean, cov) if return_cov else mean
+
+    def predict_diag(self, X, extra_std=0):
+        """(mean [W, nobs], var [W, nobs]) at X [W, ndim]: predict(X)'s mean and np.diagonal(cov, axis1=1, axis2=2), bit for bit,
+        without the [W, nobs, nobs] array (gpb_emu_predict_diag) — what a band or a per-observable error bar needs.  The
+        parameterTrafoPCA map and the slabs are predict's (without the covariance a slab is sized by the K*^T workspace alone)."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        Xg = np.ascontiguousarray(self._map_parameters(X))
+        eng = self._engine_ready()
+        W = Xg.shape[0]
+        es = np.ascontiguousarray(np.broadcast_to(np.asarray(extra_std, dtype=np.float64).reshape(-1), (W,)))
+        per_row = 8 * self._ngp * self._X_train.shape[0]
+        slab = int(min(max((8 << 30) // per_row, 1024), 1 << 17)) // 128 * 128
+        mean, var = np.empty((W, self.nobs)), np.empty((W, self.nobs))
+        for i0 in range(0, W, slab):
+            sl = slice(i0, min(i0 + slab, W))
+            m_T, v_T = eng.emu_predict_diag(np.ascontiguousarray(Xg[sl]), extra_std=np.ascontiguousarray(es[sl]))
+            mean[sl], var[sl] = m_T.T, v_T.T
+        return mean, var
 
     def predict_jacobian(self, X):
         """d mean / d X [W, nobs, ndim] at X[W, ndim], in the original parameters: the derivative of predict(X,

@@ -514,6 +514,97 @@ class GPEngine:
         self._ck(self.lib.gpb_emu_predict(self.h, nat.ptr(Xs), W, 0, nat.ptr(es), nat.ptr(mean), nat.ptr(cov)))
         return (mean, cov) if return_cov else mean
 
+    def emu_predict_diag(self, Xs, extra_std=None, out=None):
+        """emu_predict without the [W, M, M] array, observable-major (gpb_emu_predict_diag): (mean_T [M, W], var_T [M, W]) with
+        mean_T[m, w] = emu_predict's mean[w, m] and var_T[m, w] = its cov[w, m, m], bit for bit.  numpy in -> numpy out, torch(cuda)
+        in -> torch out.  out (torch path): a pair of device views [M, >= W] with unit stride along the samples — the slab's
+        columns of a larger [M, S] pair, e.g. (mu[:, i0:i1], var[:, i0:i1]) — written in place; their other columns stay."""
+        self._need_data()
+        if _is_torch(Xs):
+            import torch
+            Xs = self._check_cols(Xs, "Xs")
+            W = Xs.shape[0]
+            es = self._extra_std_dev(extra_std, W)
+            if out is None:
+                out = (torch.empty((self.M, W), dtype=torch.float64, device=Xs.device),
+                       torch.empty((self.M, W), dtype=torch.float64, device=Xs.device))
+            mean_T, var_T = out
+            for name, t in (("out[0]", mean_T), ("out[1]", var_T)):
+                if not _is_torch(t) or not t.is_cuda or t.device.index != self.device or str(t.dtype) != "torch.float64":
+                    raise ValueError("%s: expected a torch.float64 tensor on cuda:%d" % (name, self.device))
+                if t.dim() != 2 or t.shape[0] != self.M or t.shape[1] < W or (t.shape[1] > 1 and t.stride(1) != 1) \
+                        or (self.M > 1 and t.stride(0) < W):
+                    raise ValueError("%s: expected a [%d, >= %d] view with unit stride along the samples" % (name, self.M, W))
+            ld = int(mean_T.stride(0)) if self.M > 1 else max(int(mean_T.shape[1]), W)
+            if self.M > 1 and int(var_T.stride(0)) != ld:
+                raise ValueError("out: the two views need the same row stride")
+            if W:
+                self._ck(self.lib.gpb_emu_predict_diag(self.h, nat.ptr(Xs), W, 1, nat.ptr(es), nat.ptr(mean_T), nat.ptr(var_T), ld))
+            return mean_T, var_T
+        if out is not None:
+            raise ValueError("emu_predict_diag: out= takes device views, together with torch input")
+        Xs = nat.f64(Xs).reshape(-1, self.d)
+        W = Xs.shape[0]
+        es = None if extra_std is None else nat.f64(np.broadcast_to(np.asarray(extra_std, float).reshape(-1), (W,)))
+        mean_T, var_T = nat.host_empty((self.M, W)), nat.host_empty((self.M, W))
+        if W:
+            self._ck(self.lib.gpb_emu_predict_diag(self.h, nat.ptr(Xs), W, 0, nat.ptr(es), nat.ptr(mean_T), nat.ptr(var_T), W))
+        return mean_T, var_T
+
+    PPD_MAX_LEVELS = 16
+
+    def ppd_summary(self, mu_T, var_T, q, vadd=None, yobs=None, S=None, on_device=False, outputs=None):
+        """Reductions over the sample axis of observable-major device arrays (gpb_ppd_summary): mu_T, var_T (None = 0) torch cuda
+        views [M, >= S] with unit stride along the samples (S: the samples to reduce, default all columns), q the levels in
+        [0, 1] (at most 16).  Returns a dict with only the outputs whose inputs were given: "moments" [M, 3] (E mu, E sigma^2,
+        E (mu - E mu)^2) and "order" [M, nq, 2] (the two order statistics numpy's percentile interpolates between) always;
+        "mixq" [M, nq], the quantiles of the predictive mixture with tau^2 = sigma^2 + vadd, when var_T or vadd is given; "pit"
+        [M], the mixture's CDF at yobs, when yobs is.  vadd, yobs: [M], numpy or torch cuda.  numpy out, or with on_device
+        torch tensors (asynchronous).  outputs: the names to compute instead of that rule (the library refuses a name whose inputs
+        are missing).  The engine lends its device and stream only: M is the caller's."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        if not _is_torch(mu_T) or mu_T.dim() != 2:
+            raise ValueError("mu_T: expected a two-dimensional torch tensor")
+        M = int(mu_T.shape[0])
+        S = int(mu_T.shape[1]) if S is None else int(S)
+        ld = None
+        for name, t in (("mu_T", mu_T), ("var_T", var_T)):
+            if t is None:
+                continue
+            if not _is_torch(t) or not t.is_cuda or t.device.index != self.device or str(t.dtype) != "torch.float64":
+                raise ValueError("%s: expected a torch.float64 tensor on cuda:%d" % (name, self.device))
+            if t.dim() != 2 or t.shape[0] != M or t.shape[1] < S or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError("%s: expected a [%d, >= %d] view with unit stride along the samples" % (name, M, S))
+            t_ld = int(t.stride(0)) if M > 1 else max(int(t.shape[1]), S)
+            if ld is not None and t_ld != ld:
+                raise ValueError("mu_T and var_T need the same row stride")
+            ld = t_ld
+        q = nat.f64(np.atleast_1d(np.asarray(q, dtype=np.float64))).reshape(-1)
+        nq = int(q.shape[0])
+
+        def vec(a, name):
+            if a is None:
+                return None
+            if not _is_torch(a):
+                a = torch.as_tensor(nat.f64(a).reshape(-1), device=dev)
+            return self._dev(a, (M,), name, contiguous=False)
+        vadd, yobs = vec(vadd, "vadd"), vec(yobs, "yobs")
+        shapes = {"moments": (M, 3), "order": (M, nq, 2), "mixq": (M, nq), "pit": (M,)}
+        if outputs is None:
+            outputs = ["moments", "order"] + (["mixq"] if var_T is not None or vadd is not None else []) \
+                + (["pit"] if yobs is not None else [])
+        shapes = {k: shapes[k] for k in outputs}
+        if on_device:
+            out = {k: torch.empty(s, dtype=torch.float64, device=dev) for k, s in shapes.items()}
+        else:
+            out = {k: np.empty(s) for k, s in shapes.items()}
+        self._ck(self.lib.gpb_ppd_summary(self.h, nat.ptr(mu_T), nat.ptr(var_T), M, S, ld, nat.ptr(q), nq, nat.ptr(vadd),
+                                          nat.ptr(yobs), 1 if on_device else 0, nat.ptr(out.get("moments")),
+                                          nat.ptr(out.get("order")), nat.ptr(out.get("mixq")), nat.ptr(out.get("pit"))))
+        return out
+
     def emu_predict_jac(self, Xs):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
         the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""

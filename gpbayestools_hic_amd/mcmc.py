@@ -367,6 +367,85 @@ class Chain:
         return SobolIndices(*[np.concatenate([getattr(r, k) for r in parts], axis=0)
                               for k in ("mean", "variance", "first_order", "total")], names=list(self.pardict))
 
+    ppd_slab_rows = None                         # most rows of one posterior_predictive slab (None: _log_prob's rule); same bits
+
+    def _ppd_arrays(self, X, extra_std=0.0):
+        """(engines, mu_T, var_T): the emulators' means and covariance diagonals at the rows X [S, ndim], observable-major
+        device arrays [nobs, S] in emuList order — what _predict(X, extra_std) returns as mean and np.diagonal(cov), bit for
+        bit, without the [S, nobs, nobs] array.  Slab by slab and emulator by emulator: upload (for parameterTrafoPCA emulators
+        the rows mapped on the host, as predict maps them), gpb_emu_predict_diag into the emulator's rows."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        engs = [e._engine_ready() for e in self.emuList]
+        for g in engs:
+            g._need_data()
+            g._track_stream()
+        S = X.shape[0]
+        if sum(e.nobs for e in self.emuList) != self.nobs:
+            raise ValueError("emulators provide %d observables, experiment has %d" % (sum(e.nobs for e in self.emuList), self.nobs))
+        per_row = max(8 * e._ngp * e._X_train.shape[0] for e in self.emuList)
+        slab = int(min(max((8 << 30) // per_row, 1024), 1 << 17)) // 128 * 128
+        if self.ppd_slab_rows is not None:
+            slab = max(int(self.ppd_slab_rows), 1)
+        mu_T = torch.empty((self.nobs, S), dtype=torch.float64, device=dev)
+        var_T = torch.empty((self.nobs, S), dtype=torch.float64, device=dev)
+        es = np.ascontiguousarray(extra_std * X[:, -1])               # as _predict forms it (src/mcmc.py:153-166)
+        for i0 in range(0, S, slab):
+            i1 = min(i0 + slab, S)
+            Xd = torch.as_tensor(np.ascontiguousarray(X[i0:i1]), device=dev)
+            esd = torch.as_tensor(es[i0:i1], device=dev)
+            r0 = 0
+            for emu, eng in zip(self.emuList, engs):
+                # parameterTrafoPCA emulators: the HOST map, as Emulator.predict applies it — the device pre-pass agrees with it
+                # to ~1e-12, not to the bit, and these arrays are _predict's bits
+                Xg = Xd
+                if getattr(emu, "parameterTrafoPCA_", False):
+                    Xg = torch.as_tensor(np.ascontiguousarray(emu._map_parameters(X[i0:i1])), device=dev)
+                eng.emu_predict_diag(Xg, extra_std=esd, out=(mu_T[r0:r0 + emu.nobs, i0:i1], var_T[r0:r0 + emu.nobs, i0:i1]))
+                r0 += emu.nobs
+        return engs, mu_T, var_T
+
+    def posterior_predictive(self, samples, quantiles=(0.05, 0.16, 0.5, 0.84, 0.95), extra_std=0.0):
+        """What does the posterior predict for every observable, with the emulator's own uncertainty, and where does the data
+        sit in it — over ALL samples of a chain, on the device.  The posterior-predictive check of examples/ClosureTest.ipynb
+        and the bands of PlotMCMC.ipynb, which take fifteen samples because `_predict` returns the [S, nobs, nobs] covariance.
+
+        samples: [S, ndim], or a stored [nwalkers, nsteps, ndim] chain (flattened).  Rows outside the prior box are predicted
+        like any other, as `_predict` does.  Per slab and emulator one predict pass writes the means and the covariance
+        diagonals observable-major into one [nobs, S] device pair (gpb_emu_predict_diag); two reductions over the sample axis
+        follow (gpb_ppd_summary): moments, the order statistics for np.percentile's band and the quantiles of the predictive
+        mixture 1/S sum_s N(mu_s, sigma_s^2); then the mixture's CDF at the measurement with the experimental variance added.
+        Closed form, nothing sampled, equal inputs give equal bits.  Returns a PosteriorPredictive.
+        NotImplementedError for foreign emulators and for a chain sharded over several ranks."""
+        from .emulator import PosteriorPredictive, percentile_from_order
+        if not self._native():
+            raise NotImplementedError("posterior_predictive needs every emulator of the chain to be this package's Emulator (foreign "
+                                      "emulators expose no GP state to predict from on the device)")
+        if self.sharding is not None and getattr(self.sharding, "world", 1) > 1:
+            raise NotImplementedError("posterior_predictive: a chain sharded over several ranks is not supported; call it on one "
+                                      "rank (shard_over(None))")
+        X = np.asarray(samples, dtype=np.float64)
+        if X.ndim == 3:
+            X = X.reshape(-1, X.shape[-1])
+        X = np.ascontiguousarray(np.atleast_2d(X))
+        if X.ndim != 2 or X.shape[1] != self.ndim or X.shape[0] < 1:
+            raise ValueError("posterior_predictive: samples must be [S, %d] or [nwalkers, nsteps, %d], got %s"
+                             % (self.ndim, self.ndim, np.shape(samples)))
+        if not np.all(np.isfinite(X)):
+            raise ValueError("posterior_predictive: samples hold non-finite values")
+        q = np.ascontiguousarray(np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+        if q.shape[0] < 1 or q.shape[0] > GPEngine.PPD_MAX_LEVELS or not np.all((q >= 0.0) & (q <= 1.0)):
+            raise ValueError("posterior_predictive: 1 to %d quantile levels in [0, 1]" % GPEngine.PPD_MAX_LEVELS)
+        S = X.shape[0]
+        engs, mu_T, var_T = self._ppd_arrays(X, extra_std)
+        e0 = engs[0]
+        out = e0.ppd_summary(mu_T, var_T, q)
+        pit = e0.ppd_summary(mu_T, var_T, q, vadd=np.diag(self.expdata_cov), yobs=self.expdata[0], outputs=("pit",))["pit"]
+        mom = out["moments"]
+        return PosteriorPredictive(q, mom[:, 0], np.sqrt(mom[:, 1]), np.sqrt(mom[:, 2]), np.sqrt(mom[:, 1] + mom[:, 2]),
+                                   np.ascontiguousarray(percentile_from_order(out["order"], q, S).T),
+                                   np.ascontiguousarray(out["mixq"].T), pit, S)
+
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a

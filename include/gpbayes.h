@@ -277,6 +277,48 @@ GPB_API int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint8_t
                          int32_t* picks_dev /*[T]*/, double* gain_dev /*[T]*/, double* scores_dev /*[T,C] or NULL*/);
 GPB_API int gpb_design_end(gpb_ctx* ctx);
 
+/* ---- posterior-predictive summaries of a whole chain ----------------------------------------------------------------------- *
+ * gpb_emu_predict_diag <- Chain._predict's per-emulator call, mean and np.diagonal(cov) only  src/mcmc.py:153-166, src/emulator.py:553-605
+ * gpb_ppd_summary      <- what examples/ClosureTest.ipynb and PlotMCMC.ipynb take from `_predict(posteriorSamples)` — the reference
+ *                         for fifteen samples, because the [S, nobs, nobs] covariance is all `_predict` returns — for every sample
+ *                         of a chain: bands of the means, the predictive distribution with the emulator's own uncertainty, and where
+ *                         the measurement sits in it.  Closed form, nothing sampled.
+ * gpb_emu_predict_diag: gpb_emu_predict without the [W, M, M] array, written observable-major: element (m, w) at m * ld + w, ld >= W;
+ *   mean_T[m][w] is bit for bit gpb_emu_predict's mean[w][m] and var_T[m][w] its cov[w][m][m] — the same predict launch and the same
+ *   transform arithmetic — in all four GPB_MODE_*, with and without extra_std, under whichever predict arithmetic key 51 selects.
+ *   Columns w >= W of the rows are not touched: a long chain goes through slab by slab into one [M, S] array by advancing the
+ *   pointers.  Xs are GP-input-space rows (a caller with a parameter map applies gpb_param_map first); Xs, extra_std and the outputs
+ *   live where on_device says (0: host, the call synchronises; 1: device, asynchronous).  var_T may be NULL.
+ *   Errors: those of gpb_emu_predict, and GPB_E_ARG for ld < W.
+ * gpb_ppd_summary: every observable row m of mu_T / var_T [M, ld] (device arrays as gpb_emu_predict_diag writes them; var_T may be
+ *   NULL = 0) reduced over its samples s < S <= ld.  The context gives the device and the stream only: no GP state is needed, and M
+ *   is the caller's (the rows of several emulators in one array).  q_host [nq]: levels in [0, 1], 1 <= nq <= 16.  vadd_dev [M] or
+ *   NULL: a variance added to every sigma_s^2 of row m (the experimental variance for the PIT); yobs_dev [M]: the measurement.
+ *   Outputs (NULL: skipped, its work too), in host memory when on_device = 0 (the call synchronises) or device memory (asynchronous):
+ *     moments [M, 3]    E_s mu | E_s sigma^2 (the emulator part; 0 without var_T) | E_s (mu - E mu)^2 (the parameter part, two
+ *                       passes, divided by S): by the law of total variance the last two sum to the predictive variance
+ *     order [M, nq, 2]  the order statistics mu_(k) and mu_(min(k + 1, S - 1)) of the row, k = floor(q (S - 1)): the two neighbours
+ *                       numpy's default ("linear") percentile interpolates between, exact (a radix select, nothing is sorted)
+ *     mixq [M, nq]      the q-quantile of the predictive mixture F_m(y) = 1/S sum_s Phi((y - mu_s) / tau_s), tau_s^2 =
+ *                       max(sigma_s^2 + vadd_m, 0): exactly 64 halvings of [min_s(mu_s - 9 tau_s), max_s(mu_s + 9 tau_s)] (mid =
+ *                       (a + b) / 2; F(mid) < q moves a, otherwise b; stops early only when mid is no longer strictly inside), the
+ *                       result is b; a sample with tau_s = 0 contributes the step y >= mu_s; q = 0 gives -inf, q = 1 +inf
+ *     pit [M]           F_m(yobs_m): the per-observable posterior-predictive p-value
+ *   F is a sum of erfc / 2 in a fixed tree whose shape depends on S alone; no floating-point atomics: a row's bits do not depend on
+ *   M, on the other rows, on ld or on which outputs share the call, and on_device 0 and 1 give the same bits.  Inputs must be
+ *   finite (the caller checks).
+ *   Errors (GPB_E_ARG): S < 1 or M < 1 (or either above 2^31 - 1), ld < S, nq outside 1 .. 16, a level outside [0, 1], with mixq a
+ *   level strictly between 0 and 1e-15 or strictly between 1 - 1e-15 and 1 (beyond the bracket's reach), mixq with neither var_T
+ *   nor vadd, pit without yobs. */
+GPB_API int gpb_emu_predict_diag(gpb_ctx* ctx, const double* Xs /*[W,d]*/, int64_t W, int on_device,
+                         const double* extra_std /*[W] or NULL*/, double* mean_T /*[M,ld]*/, double* var_T /*[M,ld] or NULL*/,
+                         int64_t ld);
+GPB_API int gpb_ppd_summary(gpb_ctx* ctx, const double* mu_T /*[M,ld] dev*/, const double* var_T /*[M,ld] dev or NULL*/,
+                    int64_t M, int64_t S, int64_t ld, const double* q_host /*[nq]*/, int nq,
+                    const double* vadd_dev /*[M] or NULL*/, const double* yobs_dev /*[M] or NULL*/, int on_device,
+                    double* moments /*[M,3] or NULL*/, double* order /*[M,nq,2] or NULL*/, double* mixq /*[M,nq] or NULL*/,
+                    double* pit /*[M] or NULL*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
