@@ -149,6 +149,7 @@ struct gpb_ctx {
     gpb::DevBuf<double> gbuf;        // gradient path (gpb_grad.hip): beta^T = (K^-1 K*^T)^T [P][Wld][Np], then per-row pieces
     gpb::DevBuf<double> covbuf;      // [P][Wc][Wc]
     gpb::DevBuf<double> out_stage;   // staging for host outputs
+    gpb::DevBuf<double> diag_ws;     // chain diagnostics (gpb_diag.hip): Y [G][nsteps to 64][nwalkers to 16] | lag partials | walker statistics
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

@@ -15,40 +15,16 @@
 // fixed tree (wave butterfly, then the waves in order): its shape depends on S alone, so a row's bits depend on nothing but the
 // row — not on M, the other rows, ld, or the outputs that share the call.  No floating-point atomics.
 #include "gpb_internal.h"
+#include "block_reduce.h"
 #include <math.h>
 
 namespace gpb {
 
 namespace {
 
-constexpr int PPD_THREADS = 256;
-constexpr int PPD_WAVES = PPD_THREADS / 64;
+constexpr int PPD_THREADS = REDUCE_THREADS;      // Kahan, wave_sum, block_sum: block_reduce.h
+constexpr int PPD_WAVES = REDUCE_WAVES;
 constexpr int PPD_RANKS = 2 * PPD_MAX_Q;
-
-// compensated (Kahan) accumulation: the error of a thread's partial sum does not grow with the number of its terms
-struct Kahan {
-    double s = 0.0, c = 0.0;
-    __device__ __forceinline__ void add(double x) {
-        const double y = x - c, t = s + y;
-        c = isinf(t) ? 0.0 : (t - s) - y;         // (a sum that overflows stays +-inf instead of turning into NaN)
-        s = t;
-    }
-};
-
-__device__ __forceinline__ double wave_sum(double v) {            // butterfly: every lane ends with the same bits
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum of v over the workgroup, the same bits in every thread; sw: PPD_WAVES doubles of LDS (free again after the call)
-__device__ __forceinline__ double block_sum(double v, double* sw) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-    __syncthreads();
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- moments
 __global__ __launch_bounds__(PPD_THREADS) void k_ppd_moments(const double* __restrict__ mu_T, const double* __restrict__ var_T,

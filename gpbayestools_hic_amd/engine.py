@@ -605,6 +605,54 @@ class GPEngine:
                                           nat.ptr(out.get("order")), nat.ptr(out.get("mixq")), nat.ptr(out.get("pit"))))
         return out
 
+    DIAG_NO_WINDOW = 1 << 30                      # GPB_DIAG_NO_WINDOW
+
+    def mcmc_diag(self, x_dev, layout="steps", max_lag=None, c=5.0, on_device=False, outputs=None):
+        """Convergence diagnostics of a chain that lies on the device (gpb_mcmc_diag): x_dev a torch cuda float64 tensor, layout
+        "steps" = [nsteps, nwalkers, ndim] (the sampler's store) or "walkers" = [nwalkers, nsteps, ndim] (the pickles), or any
+        view of either with unit stride along the parameters (chain[discard::thin]): the strides are passed, nothing is copied.
+        max_lag: the largest lag of the autocorrelation function (default nsteps - 1); c: the factor of emcee's automatic window.
+        Returns a dict of numpy arrays (torch tensors, asynchronously, with on_device): "rho" [ndim, max_lag + 1], "tau" [ndim],
+        "window" [ndim] int32 (bit 30, DIAG_NO_WINDOW: no window inside max_lag; -1: no walker moved), "moments" [ndim, 3]
+        (mean, W, B), "rhat" [ndim], "nconst" [ndim] int32.  outputs: the names to compute (default all).  The engine lends its
+        device and stream only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        if layout not in ("steps", "walkers"):
+            raise ValueError("layout: 'steps' ([nsteps, nwalkers, ndim]) or 'walkers' ([nwalkers, nsteps, ndim])")
+        if not _is_torch(x_dev) or x_dev.dim() != 3:
+            raise ValueError("x_dev: expected a three-dimensional torch tensor")
+        if not x_dev.is_cuda or x_dev.device.index != self.device or str(x_dev.dtype) != "torch.float64":
+            raise ValueError("x_dev: expected a torch.float64 tensor on cuda:%d" % self.device)
+        ts, tw = (0, 1) if layout == "steps" else (1, 0)
+        n, nw, d = int(x_dev.shape[ts]), int(x_dev.shape[tw]), int(x_dev.shape[2])
+        if d > 1 and x_dev.stride(2) != 1:
+            raise ValueError("x_dev: expected unit stride along the parameters")
+        ss, ws = int(x_dev.stride(ts)), int(x_dev.stride(tw))
+        # an axis of extent 1 has no meaningful stride: give it the one of a contiguous array
+        if nw == 1 and layout == "steps":
+            ws = d
+        if n == 1 and layout == "walkers":
+            ss = d
+        if nw == 1 and layout == "walkers":
+            ws = max(ws, ss * n)
+        max_lag = n - 1 if max_lag is None else int(max_lag)
+        names = ("rho", "tau", "window", "moments", "rhat", "nconst")
+        outputs = names if outputs is None else tuple(outputs)
+        if any(k not in names for k in outputs):
+            raise ValueError("outputs: names among %s" % (names,))
+        shapes = {"rho": (d, max(max_lag, 0) + 1), "tau": (d,), "window": (d,), "moments": (d, 3), "rhat": (d,), "nconst": (d,)}
+        ints = ("window", "nconst")
+        if on_device:
+            out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ints else torch.float64, device=dev) for k in outputs}
+        else:
+            out = {k: np.empty(shapes[k], dtype=np.int32 if k in ints else np.float64) for k in outputs}
+        self._ck(self.lib.gpb_mcmc_diag(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, max_lag, float(c), 1 if on_device else 0,
+                                        nat.ptr(out.get("rho")), nat.ptr(out.get("tau")), nat.ptr(out.get("window")),
+                                        nat.ptr(out.get("moments")), nat.ptr(out.get("rhat")), nat.ptr(out.get("nconst"))))
+        return out
+
     def emu_predict_jac(self, Xs):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
         the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""

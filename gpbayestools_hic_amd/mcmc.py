@@ -446,6 +446,28 @@ class Chain:
                                    np.ascontiguousarray(percentile_from_order(out["order"], q, S).T),
                                    np.ascontiguousarray(out["mixq"].T), pit, S)
 
+    def convergence(self, chain=None, discard=0, c=5, tol=50):
+        """Is the chain long enough?  ChainDiagnostics (diagnostics.py) of a stored [nwalkers, nsteps, ndim] array — self.chain
+        (default; read from mcmc_path when it is not in memory), a loaded pickle's, or run_MCMC_PTLMC's output — without its
+        first `discard` steps: integrated autocorrelation time with emcee's automatic window, effective sample size,
+        split-R-hat, mean, std and Monte-Carlo standard error per parameter, computed on the device (gpb_mcmc_diag; the
+        array is uploaded in its own layout, not permuted, and read through its strides).  Never raises for a short chain:
+        converged=False."""
+        from .diagnostics import diagnose
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        x = np.asarray(chain, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError("convergence: chain must be [nwalkers, nsteps, ndim], got %s" % (np.shape(chain),))
+        discard = int(discard)
+        if discard < 0 or x.shape[1] - discard < 4:
+            raise ValueError("convergence: at least 4 steps must remain after discard")
+        names = list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[2] else None
+        return diagnose(x[:, discard:], c=c, tol=tol, layout="walkers", names=names, device=self.device or 0)
+
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a

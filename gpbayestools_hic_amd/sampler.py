@@ -250,6 +250,31 @@ class StretchSampler:
     def flatlnprobability(self):
         return self._lp_dev.reshape(-1).cpu().numpy()
 
+    # ------------------------------------------------------------------ convergence
+    def _stored_view(self, discard, thin):
+        if self._chain_dev is None:
+            raise AttributeError("no stored chain: run the sampler (store=True) first")
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError("discard >= 0 and thin >= 1")
+        return self._chain_dev[discard::thin], thin
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """emcee's EnsembleSampler.get_autocorr_time: the integrated autocorrelation time [ndim] of chain[discard::thin],
+        multiplied by thin; kwargs (c, tol, quiet) as diagnostics.integrated_time takes them.  Computed on the stored chain
+        where it lies on the device, through its strides (gpb_mcmc_diag)."""
+        from .diagnostics import integrated_time
+        x, thin = self._stored_view(discard, thin)
+        return thin * integrated_time(x, **kwargs)
+
+    def diagnostics(self, discard=0, thin=1, c=5, tol=50):
+        """ChainDiagnostics of chain[discard::thin] (diagnostics.py): tau, window, effective sample size, split-R-hat, mean, std
+        and Monte-Carlo standard error per parameter; never raises for a short chain (converged=False instead)."""
+        from .diagnostics import diagnose
+        x, thin = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        return diagnose(x, c=c, tol=tol, thin=thin, names=list(names) if names else None)
+
 
 class _HostLogProb:
     """minimal chain-like object around a host callable f(X[w, ndim]) -> lp[w]"""

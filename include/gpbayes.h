@@ -319,6 +319,52 @@ GPB_API int gpb_ppd_summary(gpb_ctx* ctx, const double* mu_T /*[M,ld] dev*/, con
                     double* moments /*[M,3] or NULL*/, double* order /*[M,nq,2] or NULL*/, double* mixq /*[M,nq] or NULL*/,
                     double* pit /*[M] or NULL*/);
 
+/* ---- convergence diagnostics of a resident chain ---------------------------------------------------------------------------- *
+ * gpb_mcmc_diag <- emcee's autocorr.integrated_time (function_1d, auto_window) behind EnsembleSampler.get_autocorr_time — the
+ *                  reference's sampler class is emcee's (src/mcmc.py:68-92), and neither it nor emcee has an R-hat — for a chain
+ *                  that already lies in device memory: the walker-averaged autocorrelation function, the integrated autocorrelation
+ *                  time with emcee's automatic window, and split-R-hat (Gelman et al., BDA3 section 11.4), per parameter j < d.
+ *   The context gives the device and the stream only: no GP state is needed, the factorisation, the predict workspace and everything
+ *   else in the context are untouched.  x_dev: element (step t, walker w, parameter j) at t * step_stride + w * walker_stride + j —
+ *   the sampler's [nsteps, nwalkers, d] store and the pickles' [nwalkers, nsteps, d], or a thinned / cut view of either, without a
+ *   copy.  Outputs (NULL: skipped) in host memory when on_device = 0 (the call synchronises) or device memory (asynchronous).
+ *   Per (parameter j, walker w): the mean over t, two passes in a fixed order; y_w(t) the centred series; c0_w = sum_t y_w(t)^2.
+ *   A walker all of whose values of parameter j are equal never moved (decided by comparing the values, not from a rounded mean: its
+ *   mean is its value and c0_w == 0 exactly; so is one whose differences are so small that their squares underflow): it is left
+ *   out of parameter j's average and counted in nconst[j] (DEVIATION: emcee divides by its c0 and returns NaN for the whole
+ *   parameter).  If all walkers of j are constant: rho[j, :], tau[j], rhat[j] = NaN and window[j] = -1.
+ *     rho [d, max_lag + 1]  rho[j, k] = mean over the walkers that moved of  sum_t y_w(t) y_w(t + k) / c0_w: raw lag sums, no
+ *                           1 / (n - k) factor — what emcee's zero-padded FFT yields.  Computed as the diagonal sums of Y Y^T, Y[t, w] =
+ *                           y_w(t) / sqrt(c0_w), 64 x 64 blocks within max_lag of the diagonal only.
+ *     tau [d], window [d]   taus[m] = 2 sum_{k <= m} rho[j, k] - 1, accumulated sequentially in k; window[j] = the first m in [0,
+ *                           max_lag] with m >= c taus[m] (emcee's auto_window); tau[j] = taus[window[j]].  No such m within max_lag:
+ *                           window[j] = max_lag with bit 30 set (GPB_DIAG_NO_WINDOW) and tau[j] = taus[max_lag].  (DEVIATION: when
+ *                           every m is "still inside", emcee's np.argmin over an all-True mask returns window 0; that quirk is not
+ *                           reproduced.)
+ *     moments [d, 3]        the mean over all draws | W | B of split-R-hat: halves of h = nsteps / 2 draws, the first t < h, the second
+ *                           t >= nsteps - h (the middle draw of an odd nsteps is dropped); W = the mean over the 2 nwalkers
+ *                           half-walkers of their sample variances (divisor h - 1); B = h times the sample variance (divisor
+ *                           2 nwalkers - 1) of their means.  Constant walkers are included.
+ *     rhat [d]              sqrt(((h - 1) / h W + B / h) / W)
+ *     nconst [d]            walkers of parameter j that never moved
+ *   No floating-point atomics; every sum runs in an order fixed by the padded shapes (nsteps to 64, nwalkers to 16) alone.  A
+ *   parameter's bits do not depend on d or on the other parameters, on which of the layouts the data arrived in, on on_device, or on
+ *   which outputs share the call.  A lag's block partials are added in an order that depends on nsteps only: rho[j, k], k <= L, is
+ *   bit for bit the same for every max_lag >= L, hence tau and window do not depend on max_lag whenever the window lies inside it.
+ *   Workspace: Y and the per-block lag partials, from the context's buffer cache; the parameters are processed in groups that keep
+ *   it under GPB_DIAG_WS_MB megabytes (one parameter at a time where a single one needs more: nsteps = 5000, nwalkers = 4096 is
+ *   166 MB per parameter).  The grouping changes no bit.
+ *   Inputs must be finite (the caller checks).
+ *   Errors (GPB_E_ARG): nsteps < 4; nwalkers < 1 or d < 1; nsteps, nwalkers or d above 2^31 - 1; max_lag outside [0, nsteps - 1];
+ *   c <= 0 or not finite; strides that let two elements alias: walker_stride < d, step_stride < d, or neither step_stride >=
+ *   walker_stride * nwalkers nor walker_stride >= step_stride * nsteps. */
+#define GPB_DIAG_NO_WINDOW (1 << 30)
+#define GPB_DIAG_WS_MB 512
+GPB_API int gpb_mcmc_diag(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                  int64_t step_stride, int64_t walker_stride, int64_t max_lag, double c, int on_device,
+                  double* rho /*[d,max_lag+1] or NULL*/, double* tau /*[d] or NULL*/, int32_t* window /*[d] or NULL*/,
+                  double* moments /*[d,3] or NULL*/, double* rhat /*[d] or NULL*/, int32_t* nconst /*[d] or NULL*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
