@@ -8,7 +8,7 @@ src/mcmc.py log-posterior loop): hand-written HIP kernels for gfx950 behind a C 
 __version__ = "0.1.0"
 
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
-           "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal"]
+           "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -27,6 +27,10 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("StretchSampler", "LoggingEnsembleSampler"):
         from . import sampler
         return getattr(sampler, name)
+    if name in ("PosteriorMarginals", "marginals"):       # (`marginals` is the submodule; the function is marginals.marginals)
+        import importlib
+        mod = importlib.import_module(".marginals", __name__)
+        return mod if name == "marginals" else mod.PosteriorMarginals
     if name == "WalkerSharding":
         from .dist import WalkerSharding
         return WalkerSharding

@@ -1205,7 +1205,7 @@ extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
 #ifndef GPB_DEBUG_VARIANTS
     // the measurement hooks (26, 32: one rank's share of a sharded step on a single GPU) exist in the debug build
     // (libgpbayes_debug.so, -DGPB_DEBUG_VARIANTS) and are refused here
-    if ((key == 26 && value != 0) || (key == 32 && value != 0))
+    if ((key == 26 && value != 0) || (key == 32 && value != 0) || (key == 52 && value != 0))
         GPB_FAIL(GPB_E_ARG, "gpb_ctx_option: this value selects a hook of the debug build only");
 #endif
     switch (key) {
@@ -1258,6 +1258,10 @@ extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
         case 33: if (value < 0) return GPB_E_ARG; ctx->tile_switch_c = value; break;
         case 34: if (value < 0) return GPB_E_ARG; ctx->mid_switch_c = value; break;
         case 35: if (value < 0) return GPB_E_ARG; ctx->narrow_switch_c = value; break;
+        case 52:        // gpb_chain_marginals: bytes of codes and integer weights per sample group (0: GPB_MARG_WS_MB megabytes); same counts
+            if (value < 0) return GPB_E_ARG;
+            ctx->marg_ws_bytes = value > 0 ? (int64_t)value : (int64_t)GPB_MARG_WS_MB << 20;
+            break;
         default: return GPB_E_ARG;
     }
     return 0;

@@ -150,6 +150,10 @@ struct gpb_ctx {
     gpb::DevBuf<double> covbuf;      // [P][Wc][Wc]
     gpb::DevBuf<double> out_stage;   // staging for host outputs
     gpb::DevBuf<double> diag_ws;     // chain diagnostics (gpb_diag.hip): Y [G][nsteps to 64][nwalkers to 16] | lag partials | walker statistics
+    // chain marginals (gpb_marg.hip): edges | h1 | outside | h2 | pairs | integer weights | one code byte per (sample, parameter)
+    // of a sample group; marg_ws_bytes caps the last two (option key 52 lowers it, in the debug build only: the grouping's test)
+    gpb::DevBuf<int64_t> marg_ws;
+    int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

@@ -653,6 +653,73 @@ class GPEngine:
                                         nat.ptr(out.get("moments")), nat.ptr(out.get("rhat")), nat.ptr(out.get("nconst"))))
         return out
 
+    MARG_MAX_BINS = 64
+
+    def chain_marginals(self, x_dev, layout="steps", edges=None, pairs=None, weights=None, on_device=False, outputs=None):
+        """Histograms of every parameter and parameter pair of a chain that lies on the device (gpb_chain_marginals): x_dev and
+        layout as mcmc_diag takes them (a flat [S, ndim] particle set: x_dev[:, None, :]); edges [ndim, B + 1] the bin edges
+        per parameter, B <= 64, taken as given: a value is in bin b iff e[b] <= x < e[b + 1], the last bin closed, NaN and the
+        rest outside — np.histogram's and np.histogram2d's counts.  pairs [npairs, 2] (default all i < j, lexicographic);
+        weights [nsteps] (numpy or torch cuda; one walker only): sample t adds rint(w_t 2^32 / max w) instead of 1.
+        Returns a dict of int64 numpy arrays (torch tensors, asynchronously, with on_device): "h1" [ndim, B], "h2" [npairs, B,
+        B] (h2[p, bi, bj]: pairs[p, 0] in bin bi, pairs[p, 1] in bin bj), "outside" [ndim].  outputs: the names to compute
+        (default all).  Integer accumulation only: equal inputs give equal counts whatever the layout.  The engine lends its
+        device and stream only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        if layout not in ("steps", "walkers"):
+            raise ValueError("layout: 'steps' ([nsteps, nwalkers, ndim]) or 'walkers' ([nwalkers, nsteps, ndim])")
+        if not _is_torch(x_dev) or x_dev.dim() != 3:
+            raise ValueError("x_dev: expected a three-dimensional torch tensor")
+        if not x_dev.is_cuda or x_dev.device.index != self.device or str(x_dev.dtype) != "torch.float64":
+            raise ValueError("x_dev: expected a torch.float64 tensor on cuda:%d" % self.device)
+        ts, tw = (0, 1) if layout == "steps" else (1, 0)
+        n, nw, d = int(x_dev.shape[ts]), int(x_dev.shape[tw]), int(x_dev.shape[2])
+        if d > 1 and x_dev.stride(2) != 1:
+            raise ValueError("x_dev: expected unit stride along the parameters")
+        ss, ws = int(x_dev.stride(ts)), int(x_dev.stride(tw))
+        # an axis of extent 1 has no meaningful stride: give it the one of a contiguous array
+        if nw == 1 and layout == "steps":
+            ws = d
+        if n == 1 and layout == "walkers":
+            ss = d
+        if nw == 1 and layout == "walkers":
+            ws = max(ws, ss * n)
+        if n == 1 and layout == "steps":
+            ss = max(ss, ws * nw)
+        edges = nat.f64(edges)
+        if edges.ndim != 2 or edges.shape[0] != d or edges.shape[1] < 2:
+            raise ValueError("edges: expected [%d, B + 1]" % d)
+        B = int(edges.shape[1]) - 1
+        if pairs is None:
+            npairs = d * (d - 1) // 2
+        else:
+            pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+            npairs = int(pairs.shape[0])
+        wscale = 1.0
+        if weights is not None:
+            if not _is_torch(weights):
+                weights = torch.as_tensor(nat.f64(weights).reshape(-1), device=dev)
+            weights = self._dev(weights, (n,), "weights", contiguous=False)
+            wmax = float(weights.max()) if n else 0.0
+            if not (wmax > 0.0) or not np.isfinite(wmax):
+                raise ValueError("weights: the largest weight must be positive and finite")
+            wscale = 4294967296.0 / wmax
+        names = ("h1", "h2", "outside")
+        outputs = names if outputs is None else tuple(outputs)
+        if any(k not in names for k in outputs):
+            raise ValueError("outputs: names among %s" % (names,))
+        shapes = {"h1": (d, B), "h2": (npairs, B, B), "outside": (d,)}
+        if on_device:
+            out = {k: torch.empty(shapes[k], dtype=torch.int64, device=dev) for k in outputs}
+        else:
+            out = {k: np.empty(shapes[k], dtype=np.int64) for k in outputs}
+        self._ck(self.lib.gpb_chain_marginals(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, nat.ptr(edges), B, nat.ptr(pairs), npairs,
+                                              nat.ptr(weights), wscale, 1 if on_device else 0, nat.ptr(out.get("h1")),
+                                              nat.ptr(out.get("h2")), nat.ptr(out.get("outside"))))
+        return out
+
     def emu_predict_jac(self, Xs):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
         the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""
@@ -851,7 +918,7 @@ class GPEngine:
              "kcross_chunks": 19, "kcross_wpl": 20, "mid_switch": 22, "lowrank": 23, "chol_lookahead": 25, "sim_ranks": 26,
              "compact": 27, "tile_by_live": 28, "premark": 29, "fuse_accept_propose": 30, "sim_rank": 32, "tile_switch_c": 33,
              "mid_switch_c": 34, "narrow_switch_c": 35, "balance_shards": 36, "chain_batch": 40, "force_tile": 42, "generic_mvn": 43,
-             "tile_switch": 44, "chol_pair": 47, "lr_split": 49, "kinv_tile": 50, "predict_sliced": 51}[key]
+             "tile_switch": 44, "chol_pair": 47, "lr_split": 49, "kinv_tile": 50, "predict_sliced": 51, "marg_ws_bytes": 52}[key]
         self._ck(self.lib.gpb_ctx_option(self.h, k, int(value)))
         if k == 51:
             self.predict_sliced = int(value)         # (what Emulator.state_digest folds in)

@@ -468,6 +468,41 @@ class Chain:
         names = list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[2] else None
         return diagnose(x[:, discard:], c=c, tol=tol, layout="walkers", names=names, device=self.device or 0)
 
+    def posterior_marginals(self, chain=None, discard=0, thin=1, bins=20, range=None, weights=None,
+                            quantiles=(0.05, 0.16, 0.5, 0.84, 0.95), pairs=None):
+        """The posterior in parameter space: PosteriorMarginals (marginals.py) of a stored [nwalkers, nsteps, ndim] array —
+        self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first `discard`
+        steps and thinned by `thin`, or of a flat [S, ndim] particle set with its importance `weights` (the `chain` and
+        `weights` of a pocoMC / run_SMC pickle; discard and thin do not apply).  Histograms of every parameter and pair over
+        `range` (default: the prior box min / max; "data": every parameter's own extent, as the notebook's hist2d(bins=20)),
+        np.percentile's percentiles and the median -lower +upper intervals of PlotMCMC.ipynb, computed on the device
+        (gpb_chain_marginals, gpb_ppd_summary; the array is uploaded in its own layout and read through its strides)."""
+        from .marginals import marginals
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        x = np.asarray(chain, dtype=np.float64)
+        if x.ndim not in (2, 3):
+            raise ValueError("posterior_marginals: chain must be [nwalkers, nsteps, ndim] or [S, ndim], got %s" % (np.shape(chain),))
+        names = list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[-1] else None
+        if range is None and np.ndim(bins) == 0:
+            if len(self.min) != x.shape[-1]:
+                raise ValueError("posterior_marginals: the chain has %d parameters, the prior box %d" % (x.shape[-1], len(self.min)))
+            range = np.stack([self.min, self.max], axis=1)
+        kw = dict(bins=bins, range=range, pairs=pairs, quantiles=quantiles, names=names, device=self.device or 0)
+        if x.ndim == 2:
+            return marginals(x, weights=weights, **kw)
+        if weights is not None:
+            raise ValueError("posterior_marginals: weights go with a flat [S, ndim] particle set")
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+            raise ValueError("posterior_marginals: discard >= 0, thin >= 1 and at least one step must remain")
+        import torch
+        xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
+        return marginals(xd[:, discard::thin], layout="walkers", **kw)
+
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a

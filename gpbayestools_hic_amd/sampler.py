@@ -275,6 +275,16 @@ class StretchSampler:
         names = getattr(self.chain_obj, "pardict", None)
         return diagnose(x, c=c, tol=tol, thin=thin, names=list(names) if names else None)
 
+    def marginals(self, discard=0, thin=1, **kw):
+        """PosteriorMarginals of chain[discard::thin] (marginals.py): histograms of every parameter and pair, percentiles and
+        credible intervals, computed on the stored chain where it lies on the device, through its strides
+        (gpb_chain_marginals); kw (bins, range, pairs, quantiles) as marginals.marginals takes them."""
+        from .marginals import marginals
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return marginals(x, layout="steps", **kw)
+
 
 class _HostLogProb:
     """minimal chain-like object around a host callable f(X[w, ndim]) -> lp[w]"""

@@ -365,6 +365,45 @@ GPB_API int gpb_mcmc_diag(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int
                   double* rho /*[d,max_lag+1] or NULL*/, double* tau /*[d] or NULL*/, int32_t* window /*[d] or NULL*/,
                   double* moments /*[d,3] or NULL*/, double* rhat /*[d] or NULL*/, int32_t* nconst /*[d] or NULL*/);
 
+/* ---- corner-plot marginals of a resident chain ------------------------------------------------------------------------------ *
+ * gpb_chain_marginals <- examples/PlotMCMC.ipynb (plot_corner_1dataset): `ax.hist(samples[:, i], bins=20)` per parameter and
+ *                        `ax.hist2d(samples[:, j], samples[:, i], bins=20)` per pair — np.histogram and np.histogram2d of every column
+ *                        and column pair, for a chain that already lies in device memory, all pairs in one call.
+ *   The context gives the device, the stream and the buffer cache only: no GP state is needed, the factorisation, the predict
+ *   workspace and everything else in the context are untouched.  x_dev: element (step t, walker w, parameter j) at t * step_stride +
+ *   w * walker_stride + j, exactly as gpb_mcmc_diag reads it — the sampler's [nsteps, nwalkers, d] store, the pickles' [nwalkers,
+ *   nsteps, d], a chain[discard::thin] view of either, without a copy; a flat [S, d] particle set is nsteps = S, nwalkers = 1.
+ *   edges_host [d, B + 1]: the bin edges of every parameter, taken as given (they need not be uniform).
+ *   BIN RULE: a value x of parameter j is in bin b iff e[j][b] <= x < e[j][b + 1]; the last bin also takes x == e[j][B]; anything
+ *   else, NaN included, is outside for j.  That is bit for bit what np.histogram(x, bins=e) and np.histogram2d(..., bins=[ei, ej])
+ *   count, and their bins=B, range=(lo, hi) forms when e = np.linspace(lo, hi, B + 1).  A value is searched in the edges; no bin
+ *   index is computed from (x - lo) / (hi - lo) * B.
+ *   pairs_host [npairs, 2] (int32) or NULL = all i < j in lexicographic order, npairs = d (d - 1) / 2.
+ *   Outputs (NULL: skipped, its work too) in host memory when on_device = 0 (the call synchronises) or device memory (asynchronous):
+ *     h1 [d, B]            h1[j][b]: the samples of parameter j in bin b
+ *     h2 [npairs, B, B]    h2[p][bi][bj]: the samples with parameter pairs[p][0] in bin bi and parameter pairs[p][1] in bin bj; a
+ *                          sample outside for either parameter is not counted, as in histogram2d
+ *     outside [d]          the samples outside for j
+ *   WEIGHT RULE: with w_dev [nsteps] (nwalkers == 1 only: a particle set) sample t adds the integer q_t = llrint(w_t * wscale)
+ *   (round half to even), clamped to [0, 2^32], NaN giving 0, instead of 1 — to h1, h2 and outside alike.  The caller passes wscale
+ *   = 2^32 / max w: the resolution is 2^-32 of the largest weight and the sums are exact in int64 ((2^31 - 1) 2^32 < 2^63); numpy
+ *   reproduces them with np.rint(w * wscale).astype(np.int64) and np.add.at.
+ *   All accumulation is integer (LDS and global integer atomics); no floating-point sum appears anywhere.  The counts therefore do
+ *   not depend on arrival order, on which of the layouts the data arrived in, on on_device, on the pairs that share the call or on
+ *   which outputs are requested.  Workspace, from the context's buffer cache: one byte per (sample, parameter) — its bin, or 255 —
+ *   written by the pass that reads the chain once and read by the pair pass; the samples go through in groups that keep it under
+ *   GPB_MARG_WS_MB megabytes, and the grouping changes no count.
+ *   Errors (GPB_E_ARG): nsteps, nwalkers or d below 1 or above 2^31 - 1; B outside 1 .. 64; edges that are not finite and strictly
+ *   increasing; a pair index outside [0, d) or a pair (i, i); npairs < 0; pairs_host == NULL with npairs != d (d - 1) / 2 (checked
+ *   when h2 is requested); npairs B^2 above 2^31 - 1; strides that let two elements alias (gpb_mcmc_diag's rule); weights with
+ *   nwalkers != 1; with weights a wscale that is not finite and positive. */
+#define GPB_MARG_WS_MB 512
+GPB_API int gpb_chain_marginals(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                        int64_t step_stride, int64_t walker_stride, const double* edges_host /*[d,B+1]*/, int B,
+                        const int32_t* pairs_host /*[npairs,2] or NULL = all i<j, lexicographic*/, int64_t npairs,
+                        const double* w_dev /*[nsteps] or NULL*/, double wscale, int on_device,
+                        int64_t* h1 /*[d,B] or NULL*/, int64_t* h2 /*[npairs,B,B] or NULL*/, int64_t* outside /*[d] or NULL*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
@@ -583,7 +622,8 @@ GPB_API int gpb_dist_finalize(gpb_ctx* ctx);
  *   cancel; 2: D = 6 with the rule off (accuracy probes).  At cfg 4 D = 7 runs the predict launch in ~0.7 of the fp64 kernel's
  *   time, D = 6 in ~0.5.
  *   Keys 26 / 32 (one rank's share of a sharded step on a single GPU: a measurement hook) take non-zero values in the debug build
- *   only (libgpbayes_debug.so: include/gpbayes_debug.h) and return GPB_E_ARG here.
+ *   only (libgpbayes_debug.so: include/gpbayes_debug.h) and return GPB_E_ARG here.  So does key 52, the bytes of gpb_chain_marginals'
+ *   per-group workspace (0: GPB_MARG_WS_MB megabytes): a test hook for the sample groups, which change no count.
  * gpb_debug_has_variants: 1 when the loaded library is that debug build (-DGPB_DEBUG_VARIANTS), 0 for the product library.
  * gpb_profile_enable / _read: HIP-event timing of the dominant kernel (k_predict: V = L^-1 K*^T + sum of squares) on the
  *   context's stream — number of timed launches, their summed duration, the (GP, walker) pairs they processed; read resets.
