@@ -20,8 +20,6 @@ int pick_dpad(int64_t d) {
     return -1;
 }
 
-int ensure_out(gpb_ctx* ctx, int64_t count) { return ctx_grow(ctx, ctx->out_stage, count); }
-
 // [P][Wld] -> [W][P]
 __global__ void k_transpose_pw(const double* __restrict__ src, double* __restrict__ dst, int64_t W, int64_t Wld,
                                int P) {
@@ -563,21 +561,15 @@ extern "C" int gpb_gp_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on_
     if ((rc = launch_predict(ctx, Xs_dev, W, var != nullptr))) return rc;
     const int64_t P = ctx->P;
     dim3 grid((unsigned)((W + 255) / 256));
-    if (on_device) {
-        hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->mean_pc, mean, W, ctx->Wld, (int)P);
-        if (var) hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->var_pc, var, W, ctx->Wld, (int)P);
-        GPB_HIP(hipGetLastError());
-        return 0;
-    }
-    if ((rc = ensure_out(ctx, 2 * W * P))) return rc;
-    hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->mean_pc, ctx->out_stage, W, ctx->Wld, (int)P);
-    GPB_HIP(hipMemcpyAsync(mean, ctx->out_stage, sizeof(double) * W * P, hipMemcpyDeviceToHost, ctx->stream));
-    if (var) {
-        hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->var_pc, ctx->out_stage + W * P, W, ctx->Wld, (int)P);
-        GPB_HIP(hipMemcpyAsync(var, ctx->out_stage + W * P, sizeof(double) * W * P, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dv;
+    so.out(dm, mean, W * P);
+    so.out(dv, var, W * P);
+    if ((rc = so.reserve())) return rc;
+    hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->mean_pc, dm, W, ctx->Wld, (int)P);
+    if (var) hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->var_pc, dv, W, ctx->Wld, (int)P);
+    GPB_HIP(hipGetLastError());
+    return so.finish();
 }
 
 extern "C" int gpb_gp_predict_cov(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device, double* mean,
@@ -591,21 +583,15 @@ extern "C" int gpb_gp_predict_cov(gpb_ctx* ctx, const double* Xs, int64_t W, int
     if (rc) return rc;
     const int64_t P = ctx->P;
     dim3 grid((unsigned)((W + 255) / 256));
-    if (on_device) {
-        if ((rc = launch_predict_cov(ctx, Xs_dev, W, cov))) return rc;
-        hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->mean_pc, mean, W, ctx->Wld, (int)P);
-        GPB_HIP(hipGetLastError());
-        return 0;
-    }
-    if ((rc = ensure_out(ctx, W * P + P * W * W))) return rc;
-    double* dm = ctx->out_stage;
-    double* dc = dm + W * P;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dc;
+    so.out(dm, mean, W * P);
+    so.out(dc, cov, P * W * W);
+    if ((rc = so.reserve())) return rc;
     if ((rc = launch_predict_cov(ctx, Xs_dev, W, dc))) return rc;
     hipLaunchKernelGGL(k_transpose_pw, grid, dim3(256), 0, ctx->stream, ctx->mean_pc, dm, W, ctx->Wld, (int)P);
-    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * P, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * P * W * W, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    GPB_HIP(hipGetLastError());
+    return so.finish();
 }
 
 // ---------------------------------------------------------------------------- emulator transform
@@ -739,16 +725,13 @@ extern "C" int gpb_emu_predict(gpb_ctx* ctx, const double* Xs, int64_t W, int on
     if (rc) return rc;
     if ((rc = launch_predict(ctx, Xs_dev, W, cov != nullptr))) return rc;
     const int64_t M = ctx->M;
-    if (on_device) return launch_obs(ctx, W, estd_dev, mean, cov);
-    const int64_t need = W * M + (cov ? W * M * M : 0);
-    if ((rc = ensure_out(ctx, need))) return rc;
-    double* dm = ctx->out_stage;
-    double* dc = cov ? ctx->out_stage + W * M : nullptr;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dc;
+    so.out(dm, mean, W * M);
+    so.out(dc, cov, W * M * M);
+    if ((rc = so.reserve())) return rc;
     if ((rc = launch_obs(ctx, W, estd_dev, dm, dc))) return rc;
-    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * M, hipMemcpyDeviceToHost, ctx->stream));
-    if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * W * M * M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 // gpb_emu_predict without the [W, M, M] array: the same launch_predict, then the same ObsModel calls for the mean and the
@@ -764,17 +747,14 @@ extern "C" int gpb_emu_predict_diag(gpb_ctx* ctx, const double* Xs, int64_t W, i
     int rc = stage_inputs(ctx, Xs, W, on_device, extra_std, &Xs_dev, &estd_dev);
     if (rc) return rc;
     if ((rc = launch_predict(ctx, Xs_dev, W, var_T != nullptr))) return rc;
-    if (on_device) return launch_obs_diag(ctx, W, estd_dev, mean_T, var_T, ld);
     const int64_t M = ctx->M;
-    if ((rc = ensure_out(ctx, (var_T ? 2 : 1) * M * W))) return rc;
-    double* dm = ctx->out_stage;
-    double* dv = var_T ? ctx->out_stage + M * W : nullptr;
-    if ((rc = launch_obs_diag(ctx, W, estd_dev, dm, dv, W))) return rc;
-    const size_t row = sizeof(double) * W, pitch = sizeof(double) * ld;
-    GPB_HIP(hipMemcpy2DAsync(mean_T, pitch, dm, row, row, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-    if (var_T) GPB_HIP(hipMemcpy2DAsync(var_T, pitch, dv, row, row, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dv;
+    const int64_t ldd = so.out2d(dm, mean_T, M, W, ld);       // (the stage's rows are W apart, the caller's ld)
+    so.out2d(dv, var_T, M, W, ld);
+    if ((rc = so.reserve())) return rc;
+    if ((rc = launch_obs_diag(ctx, W, estd_dev, dm, dv, ldd))) return rc;
+    return so.finish();
 }
 
 // ---------------------------------------------------------------------------- closed-form cross-validation (gpb_cv.hip)
@@ -785,17 +765,15 @@ extern "C" int gpb_gp_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, c
     int rc = cv_plan(ctx, "gpb_gp_cv", idx_host, n_idx, fold_ptr_host, nf, &kmax);
     if (rc) return rc;
     const int64_t P = ctx->P, ncov = P * nf * kmax * kmax;
-    if (on_device) return launch_cv(ctx, mean, var, 1, P, cov);
-    if ((rc = ensure_out(ctx, 2 * n_idx * P + (cov ? ncov : 0)))) return rc;
-    double* dm = ctx->out_stage;
-    double* dv = var ? dm + n_idx * P : nullptr;
-    double* dc = cov ? dm + 2 * n_idx * P : nullptr;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dv, *dc;
+    so.out(dm, mean, n_idx * P);
+    so.out(dv, var, n_idx * P);
+    if (!var) so.gap(n_idx * P);                       // (the covariance blocks start behind the room of both)
+    so.out(dc, cov, ncov);
+    if ((rc = so.reserve())) return rc;
     if ((rc = launch_cv(ctx, dm, dv, 1, P, dc))) return rc;
-    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * n_idx * P, hipMemcpyDeviceToHost, ctx->stream));
-    if (var) GPB_HIP(hipMemcpyAsync(var, dv, sizeof(double) * n_idx * P, hipMemcpyDeviceToHost, ctx->stream));
-    if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * ncov, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 extern "C" int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, const int32_t* fold_ptr_host, int64_t nf,
@@ -811,77 +789,77 @@ extern "C" int gpb_emu_cv(gpb_ctx* ctx, const int32_t* idx_host, int64_t n_idx, 
     ctx->last_W = 0;                                   // the K*^T of the last predict batch is no longer described by Wld
     if ((rc = launch_cv(ctx, ctx->mean_pc, ctx->var_pc, ctx->Wld, 1, nullptr))) return rc;
     const int64_t W = n_idx, M = ctx->M;
-    if (on_device) return launch_obs(ctx, W, nullptr, mean, cov);
-    if ((rc = ensure_out(ctx, W * M + (cov ? W * M * M : 0)))) return rc;
-    double* dm = ctx->out_stage;
-    double* dc = cov ? ctx->out_stage + W * M : nullptr;
+    HostOut so(ctx, on_device != 0);
+    double *dm, *dc;
+    so.out(dm, mean, W * M);
+    so.out(dc, cov, W * M * M);
+    if ((rc = so.reserve())) return rc;
     if ((rc = launch_obs(ctx, W, nullptr, dm, dc))) return rc;
-    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * W * M, hipMemcpyDeviceToHost, ctx->stream));
-    if (cov) GPB_HIP(hipMemcpyAsync(cov, dc, sizeof(double) * W * M * M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 // ---------------------------------------------------------------------------- closed-form Sobol indices (gpb_sobol.hip)
 // results are formed in the Sobol workspace behind the tables and tile partials; host callers get them copied from there
 extern "C" int gpb_gp_sobol(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int on_device, double* e, double* H) {
     if (!ctx || !e || !H) return GPB_E_ARG;
-    int rc = sobol_plan(ctx, "gpb_gp_sobol", lo_host, hi_host, false, -1);     // (checks first: the sizes below are the context's)
+    int rc = sobol_plan(ctx, "gpb_gp_sobol", lo_host, hi_host, false);     // (checks first: the sizes below are the context's)
     if (rc) return rc;
-    const int64_t P = ctx->P, nH = P * P * (2 * ctx->d + 1), np = sobol_part_doubles(ctx);
-    if ((rc = sobol_plan(ctx, "gpb_gp_sobol", lo_host, hi_host, false, np + P + nH))) return rc;
-    if (on_device) return launch_sobol(ctx, e, H);
-    double* de = ctx->sobol_ws + sobol_tab_doubles(ctx) + np;
-    double* dH = de + P;
+    const int64_t P = ctx->P, nH = P * P * (2 * ctx->d + 1);
+    HostOut so(ctx, on_device != 0);
+    double *de, *dH;
+    so.out(de, e, P);
+    so.out(dH, H, nH);
+    SobolWs ws;
+    if ((rc = so.reserve(ctx->sobol_ws, [&](Carver<double>& c) { sobol_lay(ctx, c, ws, true); }))) return rc;
     if ((rc = launch_sobol(ctx, de, dH))) return rc;
-    GPB_HIP(hipMemcpyAsync(e, de, sizeof(double) * P, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipMemcpyAsync(H, dH, sizeof(double) * nH, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 extern "C" int gpb_emu_sobol(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int on_device, double* mean, double* var,
                              double* first, double* total) {
     if (!ctx || !mean || !var || !first || !total) return GPB_E_ARG;
-    int rc = sobol_plan(ctx, "gpb_emu_sobol", lo_host, hi_host, true, -1);
+    int rc = sobol_plan(ctx, "gpb_emu_sobol", lo_host, hi_host, true);
     if (rc) return rc;
-    const int64_t P = ctx->P, M = ctx->M, d = ctx->d, nH = P * P * (2 * d + 1), np = sobol_part_doubles(ctx);
-    if ((rc = sobol_plan(ctx, "gpb_emu_sobol", lo_host, hi_host, true, np + P + nH + 2 * M + 2 * M * d))) return rc;
-    double* de = ctx->sobol_ws + sobol_tab_doubles(ctx) + np;
-    double* dH = de + P;
+    const int64_t P = ctx->P, M = ctx->M, d = ctx->d, nH = P * P * (2 * d + 1);
+    HostOut so(ctx, on_device != 0);
+    double *de, *dH, *dm, *dv, *df, *dt;
+    so.out(dm, mean, M);
+    so.out(dv, var, M);
+    so.out(df, first, M * d);
+    so.out(dt, total, M * d);
+    SobolWs ws;
+    if ((rc = so.reserve(ctx->sobol_ws, [&](Carver<double>& c) {      // (e and H of the GPs stay in the workspace on either route)
+            sobol_lay(ctx, c, ws, true);
+            de = c.take<double>(P);
+            dH = c.take<double>(nH);
+        })))
+        return rc;
     if ((rc = launch_sobol(ctx, de, dH))) return rc;
-    if (on_device) return launch_sobol_obs(ctx, de, dH, mean, var, first, total);
-    double* dm = dH + nH;
-    double* dv = dm + M;
-    double* df = dv + M;
-    double* dt = df + M * d;
     if ((rc = launch_sobol_obs(ctx, de, dH, dm, dv, df, dt))) return rc;
-    GPB_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipMemcpyAsync(var, dv, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipMemcpyAsync(first, df, sizeof(double) * M * d, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipMemcpyAsync(total, dt, sizeof(double) * M * d, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 extern "C" int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int64_t j, const double* t, int64_t G,
                                    int on_device, double* curve) {
     if (!ctx || !t || !curve) return GPB_E_ARG;
-    int rc = sobol_plan(ctx, "gpb_emu_main_effect", lo_host, hi_host, true, -1);
+    int rc = sobol_plan(ctx, "gpb_emu_main_effect", lo_host, hi_host, true);
     if (rc) return rc;
     if (j < 0 || j >= ctx->d) GPB_FAIL(GPB_E_ARG, "gpb_emu_main_effect: parameter index outside [0, d)");
     if (G < 1 || G > (int64_t)1 << 24) GPB_FAIL(GPB_E_ARG, "gpb_emu_main_effect: need 1 <= G <= 2^24 grid points");
     const int64_t P = ctx->P, M = ctx->M;
-    if ((rc = sobol_plan(ctx, "gpb_emu_main_effect", lo_host, hi_host, true, G * P + G + G * M))) return rc;
-    double* zbuf = ctx->sobol_ws + sobol_tab_doubles(ctx);
-    if (on_device) return launch_sobol_main_effect(ctx, j, t, G, zbuf, curve);
-    double* dt = zbuf + G * P;
-    double* dc = dt + G;
-    GPB_HIP(hipMemcpyAsync(dt, t, sizeof(double) * G, hipMemcpyHostToDevice, ctx->stream));
+    HostOut so(ctx, on_device != 0);
+    const double* dt;
+    double *zbuf, *dc;
+    so.in(dt, t, G);
+    so.out(dc, curve, G * M);
+    SobolWs ws;
+    if ((rc = so.reserve(ctx->sobol_ws, [&](Carver<double>& c) {
+            sobol_lay(ctx, c, ws, false);
+            zbuf = c.take<double>(G * P);
+        })))
+        return rc;
     if ((rc = launch_sobol_main_effect(ctx, j, dt, G, zbuf, dc))) return rc;
-    GPB_HIP(hipMemcpyAsync(curve, dc, sizeof(double) * G * M, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 // ---------------------------------------------------------------------------- likelihood block
@@ -915,20 +893,15 @@ extern "C" int gpb_loglike(gpb_ctx* ctx, const double* Xs, int64_t W, int on_dev
     if (n_notpd_host) GPB_HIP(hipMemsetAsync(ctx->notpd, 0, sizeof(int), ctx->stream));
     const bool fused = loglike_fuses_finalize(ctx, W);
     if ((rc = launch_predict(ctx, Xs_dev, W, true, !fused))) return rc;
-    if (on_device) {
-        if ((rc = launch_loglike(ctx, W, ll, accumulate != 0, fused))) return rc;
-    } else {
-        if ((rc = ensure_out(ctx, W))) return rc;
-        if (accumulate) GPB_HIP(hipMemcpyAsync(ctx->out_stage, ll, sizeof(double) * W, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_loglike(ctx, W, ctx->out_stage, accumulate != 0, fused))) return rc;
-        GPB_HIP(hipMemcpyAsync(ll, ctx->out_stage, sizeof(double) * W, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (n_notpd_host) {
-        GPB_HIP(hipMemcpyAsync(n_notpd_host, ctx->notpd, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-    } else if (!on_device) {
-        GPB_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    HostOut so(ctx, on_device != 0);
+    double* dl;
+    so.out(dl, ll, W, accumulate != 0);
+    if ((rc = so.reserve())) return rc;
+    if ((rc = launch_loglike(ctx, W, dl, accumulate != 0, fused))) return rc;
+    if (!n_notpd_host) return so.finish();
+    if ((rc = so.copy_back())) return rc;
+    GPB_HIP(hipMemcpyAsync(n_notpd_host, ctx->notpd, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -959,19 +932,18 @@ extern "C" int gpb_mvn_loglike(gpb_ctx* ctx, const double* dY, const double* cov
     GPB_HIP(hipSetDevice(ctx->device));
     GPB_HIP(hipMemsetAsync(ctx->notpd, 0, sizeof(int), ctx->stream));
     int rc;
-    if (on_device) {
-        if ((rc = launch_mvn(ctx, dY, cov, W, M, ll))) return rc;
-    } else {
-        const int64_t need = W * M + W * M * M + W;
-        if ((rc = ensure_out(ctx, need))) return rc;
-        double* dy = ctx->out_stage; double* dc = dy + W * M; double* dl = dc + W * M * M;
-        GPB_HIP(hipMemcpyAsync(dy, dY, sizeof(double) * W * M, hipMemcpyHostToDevice, ctx->stream));
-        GPB_HIP(hipMemcpyAsync(dc, cov, sizeof(double) * W * M * M, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_mvn(ctx, dy, dc, W, M, dl))) return rc;
-        GPB_HIP(hipMemcpyAsync(ll, dl, sizeof(double) * W, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (n_notpd_host) GPB_HIP(hipMemcpyAsync(n_notpd_host, ctx->notpd, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (n_notpd_host || !on_device) GPB_HIP(hipStreamSynchronize(ctx->stream));
+    HostOut so(ctx, on_device != 0);
+    const double *dy, *dc;
+    double* dl;
+    so.in(dy, dY, W * M);
+    so.in(dc, cov, W * M * M);
+    so.out(dl, ll, W);
+    if ((rc = so.reserve())) return rc;
+    if ((rc = launch_mvn(ctx, dy, dc, W, M, dl))) return rc;
+    if (!n_notpd_host) return so.finish();
+    if ((rc = so.copy_back())) return rc;
+    GPB_HIP(hipMemcpyAsync(n_notpd_host, ctx->notpd, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GPB_HIP(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

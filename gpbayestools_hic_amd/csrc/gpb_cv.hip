@@ -170,6 +170,11 @@ __global__ __launch_bounds__(256) void k_cv_loo(const double* __restrict__ part,
     if (bad) atomicAdd(notpd, 1);
 }
 
+// the pieces of cv_ws for the planned call (CvWs, ws_layout.h): its folds, if it has a list of them, and the leave-one-out partials
+void cv_lay(const gpb_ctx* ctx, Carver<int>& c, CvWs& ws) {
+    ws.lay(c, ctx->cv_has_idx ? ctx->cv_n + ctx->cv_nf + 1 : 0, ctx->cv_loo ? ctx->P * (ctx->Np / 64) * ctx->Np : 0);
+}
+
 }  // namespace
 
 // Checks the folds of a cross-validation call and stores them in the context (device copy included); *kmax = the largest fold.
@@ -205,18 +210,17 @@ int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, co
         }
         ctx->cv_loo = *kmax == 1;
     }
-    const int64_t Np = ctx->Np, nI = Np / 64;
-    const int64_t ints = round_up((idx ? n_idx + nf + 1 : 0), 2);      // (even: the doubles behind them stay aligned)
+    ctx->cv_n = n_idx; ctx->cv_nf = nf; ctx->cv_kmax = *kmax;
     GPB_HIP(hipSetDevice(ctx->device));
-    if (const int rc = ctx_grow(ctx, ctx->cv_ws, ints + (ctx->cv_loo ? 2 * ctx->P * nI * Np : 0))) return rc;
+    CvWs ws;
+    if (const int rc = ctx_carve(ctx, ctx->cv_ws, [&](Carver<int>& c) { cv_lay(ctx, c, ws); })) return rc;
     if (idx) {
         // the host copy lives in the context: the previous call's upload must have left it before it is overwritten
         GPB_HIP(hipStreamSynchronize(ctx->stream));
         ctx->h_cv.assign(idx, idx + n_idx);
         for (int64_t f = 0; f <= nf; ++f) ctx->h_cv.push_back(fold_ptr ? fold_ptr[f] : (int)f);
-        GPB_HIP(hipMemcpyAsync(ctx->cv_ws, ctx->h_cv.data(), sizeof(int) * ctx->h_cv.size(), hipMemcpyHostToDevice, ctx->stream));
+        GPB_HIP(hipMemcpyAsync(ws.folds, ctx->h_cv.data(), sizeof(int) * ctx->h_cv.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    ctx->cv_n = n_idx; ctx->cv_nf = nf; ctx->cv_kmax = *kmax; ctx->cv_ints = ints;
     return 0;
 }
 
@@ -224,11 +228,14 @@ int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, co
 int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64_t si, double* cov_dev) {
     const int64_t Np = ctx->Np, P = ctx->P, n_idx = ctx->cv_n, nf = ctx->cv_nf;
     const int nI = (int)(Np / 64), pad = (int)pad_front(Np, ctx->N);
-    const int* idx = ctx->cv_has_idx ? reinterpret_cast<const int*>(ctx->cv_ws.get()) : nullptr;
+    CvWs ws;
+    Carver<int> pieces(ctx->cv_ws.get());
+    cv_lay(ctx, pieces, ws);
+    const int* idx = ws.folds;
     const CvOut out{mean_dev, var_dev, sp, si, cov_dev, (int)ctx->cv_kmax};
     if (P > 65535 || nI > 65535) GPB_FAIL(GPB_E_ARG, "gpb: cross-validation of more than 65535 GPs or 4 million design points");
     if (ctx->cv_loo) {
-        double* part = reinterpret_cast<double*>(reinterpret_cast<int*>(ctx->cv_ws.get()) + ctx->cv_ints);
+        double* part = ws.part;
         hipLaunchKernelGGL(k_cv_colsq, dim3((unsigned)nI, (unsigned)nI, (unsigned)P), dim3(256), 0, ctx->stream, ctx->Linv, part, Np, nI);
         hipLaunchKernelGGL(k_cv_loo, dim3((unsigned)((n_idx + 255) / 256), (unsigned)P), dim3(256), 0, ctx->stream, part, ctx->alpha,
                            ctx->Z, idx, n_idx, Np, nI, pad, ctx->alpha_reg, ctx->pnoise, out, ctx->notpd);

@@ -237,25 +237,12 @@ __global__ __launch_bounds__(256) void k_design_row(const double* __restrict__ V
     Ut[c] = u;
 }
 
-// the begin block's layout (doubles; every part starts on an even offset: the GEMM's operands are read two at a time)
-struct DesignLayout {
-    int64_t Cp, Rp, xc, xr, w, g, dg, vc, vr, s, sc, total;
-};
-DesignLayout design_layout(const gpb_ctx* ctx, int64_t C, int64_t R) {
-    DesignLayout L;
-    L.Cp = round_up(C, WPAD);
-    L.Rp = round_up(R, WPAD);
-    const int64_t P = ctx->P, Np = ctx->Np;
-    L.xc = 0;
-    L.xr = L.xc + round_up(C * ctx->d, 2);
-    L.w = L.xr + round_up(R * ctx->d, 2);
-    L.g = L.w + L.Rp;
-    L.dg = L.g + round_up(P, 2);
-    L.vc = L.dg + P * L.Cp;
-    L.vr = L.vc + P * Np * L.Cp;
-    L.s = L.vr + P * Np * L.Rp;
-    L.sc = L.s + P * L.Rp * L.Cp;                     // the candidates' simulation noise [P][Cp] (gpb_design_set_noise)
-    L.total = L.sc + P * L.Cp;
+static_assert(WS_PAD == WPAD, "the design layouts pad to the walker-batch granule");
+// the pieces of the begin block (DesignWs, ws_layout.h) in a context's design_ws as it stands
+DesignWs design_layout(const gpb_ctx* ctx, int64_t C, int64_t R) {
+    DesignWs L;
+    Carver<double> c(ctx->design_ws.get());
+    L.lay(c, C, R, ctx->d, ctx->P, ctx->Np);
     return L;
 }
 
@@ -280,38 +267,37 @@ extern "C" int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev, int64_t C, c
         if (!(g_host[p] >= 0.0)) GPB_FAIL(GPB_E_ARG, "gpb_design_begin: a GP weight g is negative (or NaN)");
     if (P > 65535) GPB_FAIL(GPB_E_ARG, "gpb_design_begin: more than 65535 GPs");
     GPB_HIP(hipSetDevice(ctx->device));
-    const DesignLayout L = design_layout(ctx, C, R);
+    DesignWs L;
     int rc;
-    if ((rc = ctx_grow(ctx, ctx->design_ws, L.total))) return rc;
+    if ((rc = ctx_carve(ctx, ctx->design_ws, [&](Carver<double>& c) { L.lay(c, C, R, d, P, Np); }))) return rc;
     if ((rc = ensure_wcap(ctx, C > R ? C : R))) return rc;
-    double* ws = ctx->design_ws;
     hipStream_t st = ctx->stream;
-    GPB_HIP(hipMemcpyAsync(ws + L.xc, Xc_dev, sizeof(double) * (size_t)(C * d), hipMemcpyDeviceToDevice, st));
-    GPB_HIP(hipMemcpyAsync(ws + L.xr, Xr_dev, sizeof(double) * (size_t)(R * d), hipMemcpyDeviceToDevice, st));
-    GPB_HIP(hipMemsetAsync(ws + L.w, 0, sizeof(double) * (size_t)L.Rp, st));
-    GPB_HIP(hipMemcpyAsync(ws + L.w, w_dev, sizeof(double) * (size_t)R, hipMemcpyDeviceToDevice, st));
-    GPB_HIP(hipMemcpyAsync(ws + L.g, g_host, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+    GPB_HIP(hipMemcpyAsync(L.xc, Xc_dev, sizeof(double) * (size_t)(C * d), hipMemcpyDeviceToDevice, st));
+    GPB_HIP(hipMemcpyAsync(L.xr, Xr_dev, sizeof(double) * (size_t)(R * d), hipMemcpyDeviceToDevice, st));
+    GPB_HIP(hipMemsetAsync(L.w, 0, sizeof(double) * (size_t)L.Rp, st));
+    GPB_HIP(hipMemcpyAsync(L.w, w_dev, sizeof(double) * (size_t)R, hipMemcpyDeviceToDevice, st));
+    GPB_HIP(hipMemcpyAsync(L.g, g_host, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
     GPB_HIP(hipStreamSynchronize(st));                 // (g_host is the caller's)
     // V = L^-1 K*^T of the two point sets through the predict path's cross kernel (fp64 K*^T) and the joint covariance's k_vmat
     ctx->want_kst = true;
-    rc = launch_kcross(ctx, ws + L.xc, C, nullptr);
-    if (!rc) rc = launch_vmat(ctx, ws + L.vc);
-    if (!rc) rc = launch_kcross(ctx, ws + L.xr, R, nullptr);
-    if (!rc) rc = launch_vmat(ctx, ws + L.vr);
+    rc = launch_kcross(ctx, L.xc, C, nullptr);
+    if (!rc) rc = launch_vmat(ctx, L.vc);
+    if (!rc) rc = launch_kcross(ctx, L.xr, R, nullptr);
+    if (!rc) rc = launch_vmat(ctx, L.vr);
     ctx->want_kst = false;
     if (rc) return rc;
     const int64_t k0 = pad_front(Np, ctx->N);          // a multiple of the GEMM's K-step
     const dim3 gk((unsigned)(L.Cp / 16), (unsigned)(L.Rp / 16), (unsigned)P);
 #define GPB_DS_KERN(KIND)                                                                                                       \
-    hipLaunchKernelGGL(k_design_kern<KIND>, gk, dim3(256), 0, st, ws + L.xr, (int)R, ws + L.xc, (int)C, (int)d, ctx->ls, (int)ctx->dpad, \
-                       ctx->amp, ws + L.s, L.Rp, L.Cp)
+    hipLaunchKernelGGL(k_design_kern<KIND>, gk, dim3(256), 0, st, L.xr, (int)R, L.xc, (int)C, (int)d, ctx->ls, (int)ctx->dpad, \
+                       ctx->amp, L.s, L.Rp, L.Cp)
     if (ctx->kind == GPB_KERNEL_RBF) GPB_DS_KERN(GPB_KERNEL_RBF);
     else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_DS_KERN(GPB_KERNEL_MATERN15);
     else GPB_DS_KERN(GPB_KERNEL_MATERN25);
 #undef GPB_DS_KERN
-    hipLaunchKernelGGL(k_design_gemm, dim3((unsigned)(L.Cp / 128), (unsigned)(L.Rp / 128), (unsigned)P), dim3(256), 0, st, ws + L.vr,
-                       ws + L.vc, ws + L.s, Np, k0, L.Rp, L.Cp, (int)R, (int)C);
-    hipLaunchKernelGGL(k_design_diag, dim3((unsigned)(L.Cp / 64), (unsigned)P), dim3(256), 0, st, ws + L.vc, ctx->amp, ws + L.dg, Np, k0,
+    hipLaunchKernelGGL(k_design_gemm, dim3((unsigned)(L.Cp / 128), (unsigned)(L.Rp / 128), (unsigned)P), dim3(256), 0, st, L.vr,
+                       L.vc, L.s, Np, k0, L.Rp, L.Cp, (int)R, (int)C);
+    hipLaunchKernelGGL(k_design_diag, dim3((unsigned)(L.Cp / 64), (unsigned)P), dim3(256), 0, st, L.vc, ctx->amp, L.dg, Np, k0,
                        L.Cp, (int)C);
     GPB_HIP(hipGetLastError());
     ctx->design_C = C;
@@ -329,8 +315,8 @@ extern "C" int gpb_design_set_noise(gpb_ctx* ctx, const double* s_c_dev) {
     }
     GPB_HIP(hipSetDevice(ctx->device));
     const int64_t C = ctx->design_C, P = ctx->P;
-    const DesignLayout L = design_layout(ctx, C, ctx->design_R);
-    double* sc = ctx->design_ws + L.sc;
+    const DesignWs L = design_layout(ctx, C, ctx->design_R);
+    double* sc = L.sc;
     GPB_HIP(hipMemsetAsync(sc, 0, sizeof(double) * (size_t)(P * L.Cp), ctx->stream));
     GPB_HIP(hipMemcpy2DAsync(sc, sizeof(double) * (size_t)L.Cp, s_c_dev, sizeof(double) * (size_t)C, sizeof(double) * (size_t)C, (size_t)P,
                              hipMemcpyDeviceToDevice, ctx->stream));
@@ -362,62 +348,50 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
     hipStream_t st = ctx->stream;
     const int64_t Cp = round_up(C, WPAD), Rp = round_up(R, WPAD);
     const int nch = (int)(Rp / DS_RCH);
-    // per context: U [T][P][Cp] | u_r [P][Rp] | part [P][nch][Cp] | J [Cp] | den [P]; the first context also the pick and the flags
-    struct Run { double *U, *ur, *part, *J, *den; };
-    Run run[DS_MAX_CTX];
+    DesignRun run[DS_MAX_CTX];      // per context (ws_layout.h); the first context's also holds the pick and the flags
     DesignTab tab;
     tab.E = E;
-    int* pick = nullptr;
-    uint8_t* elig = eligible_dev;
     for (int e = 0; e < E; ++e) {
         gpb_ctx* c = ctxs[e];
-        const int64_t P = c->P;
-        const int64_t nU = T * P * Cp, nur = P * Rp, npart = P * nch * Cp, nden = round_up(P, 2);
-        const int64_t need = nU + nur + npart + Cp + nden + (e == 0 ? 2 + Cp / 8 : 0);
-        if (const int rc = ctx_grow(c, c->design_run, need)) { ctx->err = c->err; return rc; }
-        run[e].U = c->design_run;
-        run[e].ur = run[e].U + nU;
-        run[e].part = run[e].ur + nur;
-        run[e].J = run[e].part + npart;
-        run[e].den = run[e].J + Cp;
-        tab.J[e] = run[e].J;
-        if (e == 0) {
-            pick = reinterpret_cast<int*>(run[e].den + nden);
-            if (!elig) {
-                elig = reinterpret_cast<uint8_t*>(run[e].den + nden + 2);
-                GPB_HIP(hipMemsetAsync(elig, 1, (size_t)C, st));
-            }
+        if (const int rc = ctx_carve(c, c->design_run, [&](Carver<double>& cv) { run[e].lay(cv, T, c->P, Cp, Rp, nch, e == 0); })) {
+            ctx->err = c->err;
+            return rc;
         }
+        tab.J[e] = run[e].J;
+    }
+    int* pick = run[0].pick;
+    uint8_t* elig = eligible_dev;
+    if (!elig) {
+        elig = run[0].elig;
+        GPB_HIP(hipMemsetAsync(elig, 1, (size_t)C, st));
     }
     for (int64_t t = 0; t < T; ++t) {
         for (int e = 0; e < E; ++e) {
             gpb_ctx* c = ctxs[e];
-            const DesignLayout L = design_layout(c, C, R);
-            double* ws = c->design_ws;
+            const DesignWs L = design_layout(c, C, R);
             const int P = (int)c->P;
             const dim3 gs((unsigned)(Cp / 128), (unsigned)nch, (unsigned)P);
             if (t == 0)
-                hipLaunchKernelGGL(k_design_score<false>, gs, dim3(256), 0, st, ws + L.s, run[e].ur, run[e].U, ws + L.w, run[e].part, Rp, Cp);
+                hipLaunchKernelGGL(k_design_score<false>, gs, dim3(256), 0, st, L.s, run[e].ur, run[e].U, L.w, run[e].part, Rp, Cp);
             else
-                hipLaunchKernelGGL(k_design_score<true>, gs, dim3(256), 0, st, ws + L.s, run[e].ur, run[e].U + (t - 1) * P * Cp, ws + L.w,
+                hipLaunchKernelGGL(k_design_score<true>, gs, dim3(256), 0, st, L.s, run[e].ur, run[e].U + (t - 1) * P * Cp, L.w,
                                    run[e].part, Rp, Cp);
-            hipLaunchKernelGGL(k_design_combine, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, st, run[e].part, ws + L.dg, ws + L.g,
-                               c->noise, c->alpha_reg, c->design_noise ? ws + L.sc : nullptr, P, nch, Cp, (int)C, run[e].J);
+            hipLaunchKernelGGL(k_design_combine, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, st, run[e].part, L.dg, L.g,
+                               c->noise, c->alpha_reg, c->design_noise ? L.sc : nullptr, P, nch, Cp, (int)C, run[e].J);
         }
         hipLaunchKernelGGL(k_design_pick, dim3(1), dim3(1024), 0, st, tab, (int)C, elig, (int)t, pick, picks_dev, gain_dev, scores_dev);
         if (t + 1 == T) break;                         // (nothing reads the last pick's downdate)
         for (int e = 0; e < E; ++e) {
             gpb_ctx* c = ctxs[e];
-            const DesignLayout L = design_layout(c, C, R);
-            double* ws = c->design_ws;
+            const DesignWs L = design_layout(c, C, R);
             const int P = (int)c->P;
             const int64_t k0 = pad_front(c->Np, c->N);
-            hipLaunchKernelGGL(k_design_ur, dim3((unsigned)((Rp + 255) / 256), (unsigned)P), dim3(256), 0, st, ws + L.s, ws + L.dg, c->noise,
-                               c->alpha_reg, c->design_noise ? ws + L.sc : nullptr, pick, Rp, Cp, (int)R, run[e].ur, run[e].den);
+            hipLaunchKernelGGL(k_design_ur, dim3((unsigned)((Rp + 255) / 256), (unsigned)P), dim3(256), 0, st, L.s, L.dg, c->noise,
+                               c->alpha_reg, c->design_noise ? L.sc : nullptr, pick, Rp, Cp, (int)R, run[e].ur, run[e].den);
             const dim3 gr((unsigned)(Cp / 64), (unsigned)P);
 #define GPB_DS_ROW(KIND)                                                                                                          \
-    hipLaunchKernelGGL(k_design_row<KIND>, gr, dim3(256), 0, st, ws + L.vc, run[e].U, ws + L.xc, c->ls, c->amp, run[e].den, pick,  \
-                       ws + L.dg, c->Np, k0, Cp, (int)C, (int)c->d, (int)c->dpad, P, (int)t)
+    hipLaunchKernelGGL(k_design_row<KIND>, gr, dim3(256), 0, st, L.vc, run[e].U, L.xc, c->ls, c->amp, run[e].den, pick,  \
+                       L.dg, c->Np, k0, Cp, (int)C, (int)c->d, (int)c->dpad, P, (int)t)
             if (c->kind == GPB_KERNEL_RBF) GPB_DS_ROW(GPB_KERNEL_RBF);
             else if (c->kind == GPB_KERNEL_MATERN15) GPB_DS_ROW(GPB_KERNEL_MATERN15);
             else GPB_DS_ROW(GPB_KERNEL_MATERN25);

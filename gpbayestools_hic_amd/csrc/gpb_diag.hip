@@ -220,15 +220,17 @@ int launch_mcmc_diag(gpb_ctx* ctx, const double* x, int64_t n, int64_t nw, int64
     const int64_t nblk = nd * nb;
     if (nblk > 0x7fffffffLL) GPB_FAIL(GPB_E_ARG, "gpb_mcmc_diag: more than 2^31 - 1 blocks in the band");
     // one parameter: Y, the lag partials of its blocks (one diagonal more is addressed, never read, by the last lags), the statistics
-    const int64_t per = nsp * nwp + (nblk + nb) * 128 + nwp * DIAG_STATS;
+    DiagWs dw;
+    Carver<double> one;
+    dw.lay(one, 1, nsp, nwp, nblk + nb, DIAG_STATS);
+    const int64_t per = one.total();
     int64_t G = DIAG_WS_BYTES / (8 * per);
     G = G < 1 ? 1 : (G > d ? d : G);
     if (G > 65535) G = 65535;
     if ((nwp * G + DIAG_THREADS - 1) / DIAG_THREADS > 0x7fffffffLL) GPB_FAIL(GPB_E_ARG, "gpb_mcmc_diag: too many walkers");
-    if (const int rc = ctx_grow(ctx, ctx->diag_ws, per * G)) return rc;
-    double* Y = ctx->diag_ws;
-    double* part = Y + G * nsp * nwp;
-    double* stats = part + G * (nblk + nb) * 128;
+    if (const int rc = ctx_carve(ctx, ctx->diag_ws, [&](Carver<double>& cv) { dw.lay(cv, G, nsp, nwp, nblk + nb, DIAG_STATS); }))
+        return rc;
+    double *Y = dw.Y, *part = dw.part, *stats = dw.stats;
     for (int64_t j0 = 0; j0 < d; j0 += G) {
         const int64_t dg = imin64(G, d - j0);
         hipLaunchKernelGGL(k_diag_pack, dim3((unsigned)((nwp * dg + DIAG_THREADS - 1) / DIAG_THREADS)), dim3(DIAG_THREADS), 0,
@@ -272,23 +274,18 @@ extern "C" int gpb_mcmc_diag(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, 
     const bool need_acf = rho || tau || window;
     const int64_t L1 = max_lag + 1;
     const int64_t n_rho = need_acf ? d * L1 : 0;
-    if (const int rc = ctx_grow(ctx, ctx->out_stage, n_rho + 7 * d)) return rc;      // (7: tau, 3 moments, rhat, 2 d ints)
-    double* s_rho = ctx->out_stage;
-    double* s_tau = s_rho + n_rho;
-    double* s_mo = s_tau + d;
-    double* s_rh = s_mo + 3 * d;
-    int* s_win = reinterpret_cast<int*>(s_rh + d);
-    int* s_nc = s_win + d;
-    if (const int rc = launch_mcmc_diag(ctx, x_dev, nsteps, nwalkers, d, step_stride, walker_stride, max_lag, c, need_acf, s_rho, s_tau,
-                                        s_mo, s_rh, s_win, s_nc))
+    // the kernels write every statistic, wanted or not, into the stage; what the caller wants is copied from there
+    DiagStage s;
+    if (const int rc = ctx_carve(ctx, ctx->out_stage, [&](Carver<double>& cv) { s.lay(cv, n_rho, d); })) return rc;
+    if (const int rc = launch_mcmc_diag(ctx, x_dev, nsteps, nwalkers, d, step_stride, walker_stride, max_lag, c, need_acf, s.rho, s.tau,
+                                        s.moments, s.rhat, s.window, s.nconst))
         return rc;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (rho) GPB_HIP(hipMemcpyAsync(rho, s_rho, sizeof(double) * n_rho, kind, ctx->stream));
-    if (tau) GPB_HIP(hipMemcpyAsync(tau, s_tau, sizeof(double) * d, kind, ctx->stream));
-    if (window) GPB_HIP(hipMemcpyAsync(window, s_win, sizeof(int32_t) * d, kind, ctx->stream));
-    if (moments) GPB_HIP(hipMemcpyAsync(moments, s_mo, sizeof(double) * 3 * d, kind, ctx->stream));
-    if (rhat) GPB_HIP(hipMemcpyAsync(rhat, s_rh, sizeof(double) * d, kind, ctx->stream));
-    if (nconst) GPB_HIP(hipMemcpyAsync(nconst, s_nc, sizeof(int32_t) * d, kind, ctx->stream));
-    if (!on_device) GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostOut so(ctx, on_device != 0, true);
+    so.at(rho, s.rho, n_rho);
+    so.at(tau, s.tau, d);
+    so.at(window, s.window, d);
+    so.at(moments, s.moments, 3 * d);
+    so.at(rhat, s.rhat, d);
+    so.at(nconst, s.nconst, d);
+    return so.finish();
 }

@@ -412,26 +412,13 @@ __global__ void k_grad_finish(const double* __restrict__ X, int64_t W, int nd, c
 
 namespace {
 
-// the pieces of one gradient evaluation of W rows, carved out of ctx->gbuf
-struct GradWs {
-    double *bt, *dm, *dv, *wmu, *wv, *xg, *jm, *lw, *xin, *out;
-};
-
+// the pieces of one gradient evaluation of W rows, carved out of ctx->gbuf (GradWs, ws_layout.h)
 int grad_ws(gpb_ctx* ctx, int64_t W, bool need_beta, bool need_like, int64_t n_out, GradWs& g) {
-    const int64_t Wld = round_up(W, WPAD), P = ctx->P, d = ctx->d, din = sampler_ndim(ctx);
     const bool lw_global = need_like && like_w_doubles(ctx) > LIKE_W_LDS;
-    const int64_t sz[10] = {need_beta ? P * Wld * ctx->Np : 0, W * P * d, need_beta ? W * P * d : 0, W * P, W * P, W * d,
-                            ctx->pmap_d_in > 0 ? W * d * din : 0, lw_global ? W * like_w_doubles(ctx) : 0, W * (din > d ? din : d), n_out};
-    int64_t need = 0;
-    for (int i = 0; i < 10; ++i) need += round_up(sz[i], 32);
-    if (int rc = ctx_grow(ctx, ctx->gbuf, need)) return rc;
-    double* q = ctx->gbuf;
-    double** dst[10] = {&g.bt, &g.dm, &g.dv, &g.wmu, &g.wv, &g.xg, &g.jm, &g.lw, &g.xin, &g.out};
-    for (int i = 0; i < 10; ++i) {
-        *dst[i] = sz[i] ? q : nullptr;
-        q += round_up(sz[i], 32);
-    }
-    return 0;
+    return ctx_carve(ctx, ctx->gbuf, [&](Carver<double>& c) {
+        g.lay(c, need_beta, ctx->P, round_up(W, WPAD), ctx->Np, W, ctx->d, sampler_ndim(ctx), ctx->pmap_d_in > 0,
+              lw_global ? W * like_w_doubles(ctx) : 0, n_out);
+    });
 }
 
 // K*^T (fp64) of the rows Xg[W][d], optionally the per-GP means / variances, then beta^T (need_beta) and the contraction into
@@ -492,19 +479,13 @@ extern "C" int gpb_gp_predict_grad(gpb_ctx* ctx, const double* Xs, int64_t W, in
     const int64_t n = W * ctx->P * ctx->d;
     GradWs g;
     if ((rc = grad_ws(ctx, W, dvar != nullptr, false, on_device ? 0 : 2 * n, g))) return rc;
-    const double* X = Xs;
-    if (!on_device) {
-        GPB_HIP(hipMemcpyAsync(g.xin, Xs, sizeof(double) * W * ctx->d, hipMemcpyHostToDevice, ctx->stream));
-        X = g.xin;
-    }
-    double* om = on_device ? dmean : g.out;
-    double* ov = dvar ? (on_device ? dvar : g.out + n) : nullptr;
+    HostOut so(ctx, on_device != 0);
+    const double* X;
+    if ((rc = so.in_at(X, Xs, g.xin, W * ctx->d))) return rc;
+    double* om = so.at(dmean, g.out, n);
+    double* ov = so.at(dvar, g.out ? g.out + n : nullptr, n);
     if ((rc = gp_grad_rows(ctx, X, W, dvar != nullptr, false, g.bt, om, ov))) return rc;
-    if (on_device) return 0;
-    GPB_HIP(hipMemcpyAsync(dmean, om, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (dvar) GPB_HIP(hipMemcpyAsync(dvar, ov, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 extern "C" int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, int on_device, double* jac) {
@@ -518,11 +499,9 @@ extern "C" int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, in
     const int64_t din = sampler_ndim(ctx), n = W * ctx->M * din;
     GradWs g;
     if ((rc = grad_ws(ctx, W, false, false, on_device ? 0 : n, g))) return rc;
-    const double* X = Xs;
-    if (!on_device) {
-        GPB_HIP(hipMemcpyAsync(g.xin, Xs, sizeof(double) * W * din, hipMemcpyHostToDevice, ctx->stream));
-        X = g.xin;
-    }
+    HostOut so(ctx, on_device != 0);
+    const double* X;
+    if ((rc = so.in_at(X, Xs, g.xin, W * din))) return rc;
     const double* Xg = X;
     if (ctx->pmap_d_in > 0) {
         if ((rc = gpb_param_map(ctx, X, W, g.xg))) return rc;
@@ -530,15 +509,12 @@ extern "C" int gpb_emu_predict_jac(gpb_ctx* ctx, const double* Xs, int64_t W, in
         Xg = g.xg;
     }
     if ((rc = gp_grad_rows(ctx, Xg, W, false, true, nullptr, g.dm, nullptr))) return rc;
-    double* o = on_device ? jac : g.out;
+    double* o = so.at(jac, g.out, n);
     hipLaunchKernelGGL(k_emu_jac, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->mean_pc, ctx->Wld, g.dm,
                        (int)ctx->P, (int)ctx->d, (int)ctx->M, ctx->mode, ctx->A, ctx->mu, ctx->scale,
                        ctx->pmap_d_in > 0 ? g.jm : nullptr, (int)din, W, o);
     GPB_HIP(hipGetLastError());
-    if (on_device) return 0;
-    GPB_HIP(hipMemcpyAsync(jac, o, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return so.finish();
 }
 
 extern "C" int gpb_chain_logpost_grad(gpb_ctx* const* ctxs, int E, const double* Xs_dev, int64_t W, double* ll_dev,

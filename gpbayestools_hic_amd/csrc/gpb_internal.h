@@ -9,6 +9,7 @@
 #include "../../include/gpbayes.h"
 #include "../../include/gpbayes_debug.h"
 #include "dev_buf.h"
+#include "ws_layout.h"
 
 namespace gpb {
 
@@ -158,7 +159,7 @@ struct gpb_ctx {
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;
     std::vector<int> h_cv;
-    int64_t cv_n = 0, cv_nf = 0, cv_kmax = 0, cv_ints = 0;
+    int64_t cv_n = 0, cv_nf = 0, cv_kmax = 0;
     bool cv_loo = false, cv_has_idx = false;
     // Sobol indices (gpb_sobol.hip): I | E tables [P][N][dpad] each, e partials [P][Np/64], then what the call needs (tile
     // partials, staged results); the box of the planned call, lo [d] | hi [d]
@@ -289,11 +290,136 @@ inline int ctx_replace(gpb_ctx* ctx, DevBuf<T>& b, int64_t n) {
     GPB_HIP(b.alloc(n));
     return 0;
 }
-// ctx_grow: a workspace of at least `need` elements (never shrunk; the contents are not kept)
+// ctx_grow: a workspace of at least `need` elements (never shrunk; the contents are not kept) — for a buffer that is ONE array.
+// THE RULE for a buffer with more than one piece: it is sized by ctx_carve, and a result that goes to the caller's device
+// pointer or to host memory goes through HostOut (both below); no total is summed by hand next to the offsets it must cover.
 template <typename T>
 inline int ctx_grow(gpb_ctx* ctx, DevBuf<T>& b, int64_t need) {
     return b.cap >= need ? 0 : ctx_replace(ctx, b, need);
 }
+// ctx_carve: `layout(Carver<T>&)` — a list of take() calls that only assigns pointers (ws_layout.h) — runs once counting, the
+// buffer grows to that total, and it runs again over the buffer: the pointers it leaves cannot exceed what was allocated.
+template <typename T, typename F>
+inline int ctx_carve(gpb_ctx* ctx, DevBuf<T>& b, F&& layout) {
+    Carver<T> count;
+    layout(count);
+    if (const int rc = ctx_grow(ctx, b, count.total())) return rc;
+    Carver<T> pieces(b.get());
+    layout(pieces);
+    return 0;
+}
+
+// The results (and staged inputs) of an entry point whose caller passes device pointers (on_device) or host memory.  Device
+// mode: every piece is the caller's pointer and finish() does nothing.  Host mode: every piece is a piece of a staging buffer
+// (out_stage unless reserve() is given another), finish() copies the results back on the context's stream and synchronises
+// it once.  always_staged: the kernels write the stage in device mode too and finish() copies device-to-device.  A null
+// caller pointer yields a null piece.
+//     HostOut so(ctx, on_device);
+//     double *dm, *dv;
+//     so.out(dm, mean, n); so.out(dv, var, n);
+//     if ((rc = so.reserve())) return rc;
+//     ... launch into dm, dv ...
+//     return so.finish();
+struct HostOut {
+    static constexpr int MAX_PIECES = 8;
+    struct Piece {
+        double** slot;             // where reserve() leaves the piece's pointer (nullptr: a piece placed by the caller, at())
+        void* user;
+        void* stage;
+        int64_t n;                 // doubles to carve
+        size_t row_bytes, rows, user_pitch;     // rows > 0: a pitched result, copied back row by row
+        bool load, store;
+    };
+    gpb_ctx* ctx;
+    bool on_device, always_staged, overflow = false;
+    Piece pc[MAX_PIECES];
+    int np = 0;
+
+    HostOut(gpb_ctx* c, bool on_dev, bool always = false) : ctx(c), on_device(on_dev), always_staged(always) {}
+    bool staged() const { return !on_device || always_staged; }
+    // n doubles of result; load: the stage starts as a copy of the caller's values (an accumulating kernel)
+    void out(double*& dev, double* user, int64_t n, bool load = false) {
+        dev = user;
+        if (user && staged()) add(Piece{&dev, user, nullptr, n, sizeof(double) * (size_t)n, 0, 0, load, true});
+    }
+    // rows x W doubles of result with the caller's leading dimension ld; returns the leading dimension to write `dev` with
+    int64_t out2d(double*& dev, double* user, int64_t rows, int64_t W, int64_t ld) {
+        dev = user;
+        if (!user || !staged()) return ld;
+        add(Piece{&dev, user, nullptr, rows * W, sizeof(double) * (size_t)W, (size_t)rows, sizeof(double) * (size_t)ld, false, true});
+        return W;
+    }
+    // n doubles of input
+    void in(const double*& dev, const double* user, int64_t n) {
+        dev = user;
+        if (user && !on_device)
+            add(Piece{const_cast<double**>(&dev), const_cast<double*>(user), nullptr, n, sizeof(double) * (size_t)n, 0, 0, true, false});
+    }
+    // n doubles of the stage that no caller sees (keeps the pieces behind it where they are)
+    void gap(int64_t n) {
+        if (staged()) add(Piece{nullptr, nullptr, nullptr, n, 0, 0, 0, false, false});
+    }
+    // a result of n elements whose stage the caller has placed (a piece of a layout): the pointer to write
+    template <typename T>
+    T* at(T* user, T* stage, int64_t n) {
+        if (!user || !staged()) return user;
+        add(Piece{nullptr, user, stage, 0, sizeof(T) * (size_t)n, 0, 0, false, true});
+        return stage;
+    }
+    // the same for an input; enqueues its upload at once
+    int in_at(const double*& dev, const double* user, double* stage, int64_t n) {
+        dev = user;
+        if (!user || on_device) return 0;
+        GPB_HIP(hipMemcpyAsync(stage, user, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        dev = stage;
+        return 0;
+    }
+    // places the pieces of out() / out2d() / in() / gap() in `buf` behind what `front(Carver<double>&)` takes (a workspace whose
+    // tail is the stage), sizes the buffer for both, and uploads the inputs
+    template <typename F>
+    int reserve(DevBuf<double>& buf, F&& front) {
+        if (overflow) GPB_FAIL(GPB_E_ARG, "gpb: internal: HostOut has more pieces than it has room for");
+        if (const int rc = ctx_carve(ctx, buf, [&](Carver<double>& c) {
+                front(c);
+                for (int i = 0; i < np; ++i) {
+                    if (pc[i].n <= 0) continue;
+                    pc[i].stage = c.take<double>(pc[i].n);
+                    if (pc[i].slot) *pc[i].slot = static_cast<double*>(pc[i].stage);
+                }
+            }))
+            return rc;
+        for (int i = 0; i < np; ++i)
+            if (pc[i].load) GPB_HIP(hipMemcpyAsync(pc[i].stage, pc[i].user, pc[i].row_bytes, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    }
+    int reserve() {
+        return reserve(ctx->out_stage, [](Carver<double>&) {});
+    }
+    // the copies to the caller, no synchronisation (an entry point that has more to enqueue in front of it)
+    int copy_back() {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        for (int i = 0; i < np; ++i) {
+            const Piece& p = pc[i];
+            if (!p.store) continue;
+            if (p.rows)
+                GPB_HIP(hipMemcpy2DAsync(p.user, p.user_pitch, p.stage, p.row_bytes, p.row_bytes, p.rows, kind, ctx->stream));
+            else
+                GPB_HIP(hipMemcpyAsync(p.user, p.stage, p.row_bytes, kind, ctx->stream));
+        }
+        return 0;
+    }
+    int finish() {
+        if (const int rc = copy_back()) return rc;
+        if (!on_device) GPB_HIP(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+
+ private:
+    void add(const Piece& p) {
+        if (np == MAX_PIECES) overflow = true;
+        else pc[np++] = p;
+    }
+};
 // fit side (gpb_fit.hip)
 int launch_scale_design(gpb_ctx* ctx);
 int choose_forms(gpb_ctx* ctx, bool upload = true);    // gpb_api.hip: per-GP distance form from h_theta and the design's extents
@@ -333,12 +459,11 @@ int launch_vmat(gpb_ctx* ctx, double* dst = nullptr);     // gpb_cov.hip: vbuf (
 // the fold covariance blocks [P][nf][kmax][kmax]
 int cv_plan(gpb_ctx* ctx, const char* who, const int32_t* idx, int64_t n_idx, const int32_t* fold_ptr, int64_t nf, int64_t* kmax);
 int launch_cv(gpb_ctx* ctx, double* mean_dev, double* var_dev, int64_t sp, int64_t si, double* cov_dev);
-// closed-form Sobol indices (gpb_sobol.hip): sobol_plan checks state and box (GPB_E_STATE / GPB_E_ARG), keeps the box and sizes
-// ctx->sobol_ws for the tables plus `extra` doubles, which start at sobol_ws + sobol_tab_doubles; launch_sobol needs
-// sobol_part_doubles of them in front for its tile partials
-int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi, bool need_transform, int64_t extra);
-int64_t sobol_tab_doubles(const gpb_ctx* ctx);
-int64_t sobol_part_doubles(const gpb_ctx* ctx);
+// closed-form Sobol indices (gpb_sobol.hip): sobol_plan checks state and box (GPB_E_STATE / GPB_E_ARG), keeps the box and selects
+// the device.  sobol_lay: the front of ctx->sobol_ws (SobolWs: the tables every call needs and, with_part, launch_sobol's tile
+// partials); the entry points carve what else they need behind it and size the buffer (ctx_carve / HostOut::reserve)
+int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi, bool need_transform);
+void sobol_lay(const gpb_ctx* ctx, Carver<double>& c, SobolWs& ws, bool with_part);
 int launch_sobol(gpb_ctx* ctx, double* e_dev, double* H_dev);
 int launch_sobol_obs(gpb_ctx* ctx, const double* e_dev, const double* H_dev, double* mean, double* var, double* first, double* total);
 int launch_sobol_main_effect(gpb_ctx* ctx, int64_t j, const double* t_dev, int64_t G, double* zbuf_dev, double* curve_dev);

@@ -174,16 +174,15 @@ int launch_chain_marginals(gpb_ctx* ctx, const double* x, int64_t n, int64_t nw,
     int64_t Sg = per_sample ? ctx->marg_ws_bytes / per_sample : S;
     Sg = Sg < 1 ? 1 : (Sg > S ? S : Sg);
     if (Sg > 0x40000000LL) Sg = 0x40000000LL;                    // (the kernels' 32-bit sample offsets)
-    const int64_t n_qw = w ? Sg : 0, n_codes = need_h2 ? (Sg * d + 7) / 8 : 0;
-    if (const int rc = ctx_grow(ctx, ctx->marg_ws, n_edges + n_h1 + d + n_h2 + n_pairs + n_qw + n_codes)) return rc;
-    int64_t* base = ctx->marg_ws;
-    double* edges = reinterpret_cast<double*>(base);
-    u64* h1 = reinterpret_cast<u64*>(base + n_edges);
-    u64* out = h1 + n_h1;
-    u64* h2 = out + d;
-    int* pairs = reinterpret_cast<int*>(h2 + n_h2);
-    u64* qw = reinterpret_cast<u64*>(h2 + n_h2 + n_pairs);
-    unsigned char* codes = reinterpret_cast<unsigned char*>(qw + n_qw);
+    const int64_t n_qw = w ? Sg : 0, n_codes = need_h2 ? Sg * d : 0;            // (codes: bytes)
+    MargWs mw;
+    if (const int rc = ctx_carve(ctx, ctx->marg_ws, [&](Carver<int64_t>& c) { mw.lay(c, n_edges, n_h1, d, n_h2, n_pairs, n_qw, n_codes); }))
+        return rc;
+    double* edges = mw.edges;
+    u64 *h1 = reinterpret_cast<u64*>(mw.h1), *out = reinterpret_cast<u64*>(mw.out), *h2 = reinterpret_cast<u64*>(mw.h2),
+        *qw = reinterpret_cast<u64*>(mw.qw);
+    int* pairs = mw.pairs;
+    unsigned char* codes = mw.codes;
     GPB_HIP(hipMemcpyAsync(edges, edges_host, sizeof(double) * n_edges, hipMemcpyHostToDevice, ctx->stream));
     GPB_HIP(hipMemsetAsync(h1, 0, sizeof(u64) * (n_h1 + d + n_h2), ctx->stream));
     if (need_h2) {
@@ -281,10 +280,9 @@ extern "C" int gpb_chain_marginals(gpb_ctx* ctx, const double* x_dev, int64_t ns
     if (const int rc = launch_chain_marginals(ctx, x_dev, nsteps, nwalkers, d, step_stride, walker_stride, steps_outer, edges_host, B,
                                               pairs_host, npairs, w_dev, wscale, need_h1, need_h2, &s_h1, &s_out, &s_h2))
         return rc;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (h1) GPB_HIP(hipMemcpyAsync(h1, s_h1, sizeof(int64_t) * d * B, kind, ctx->stream));
-    if (outside) GPB_HIP(hipMemcpyAsync(outside, s_out, sizeof(int64_t) * d, kind, ctx->stream));
-    if (need_h2) GPB_HIP(hipMemcpyAsync(h2, s_h2, sizeof(int64_t) * npairs * B * B, kind, ctx->stream));
-    if (!on_device) GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostOut so(ctx, on_device != 0, true);
+    so.at(h1, s_h1, d * B);
+    so.at(outside, s_out, d);
+    if (need_h2) so.at(h2, s_h2, npairs * B * B);
+    return so.finish();
 }

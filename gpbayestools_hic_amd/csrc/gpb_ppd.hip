@@ -292,20 +292,13 @@ extern "C" int gpb_ppd_summary(gpb_ctx* ctx, const double* mu_T, const double* v
     if (pit && !yobs_dev) GPB_FAIL(GPB_E_ARG, "gpb_ppd_summary: pit needs yobs");
     if (!moments && !order && !mixq && !pit) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    if (on_device) return launch_ppd(ctx, mu_T, var_T, M, S, ld, lv, vadd_dev, yobs_dev, moments, order, mixq, pit);
-    const int64_t n_mo = moments ? 3 * M : 0, n_or = order ? 2 * nq * M : 0, n_mq = mixq ? nq * M : 0, n_pi = pit ? M : 0;
-    if (const int rc = ctx_grow(ctx, ctx->out_stage, n_mo + n_or + n_mq + n_pi)) return rc;
-    double* d_mo = ctx->out_stage;
-    double* d_or = d_mo + n_mo;
-    double* d_mq = d_or + n_or;
-    double* d_pi = d_mq + n_mq;
-    if (const int rc = launch_ppd(ctx, mu_T, var_T, M, S, ld, lv, vadd_dev, yobs_dev, moments ? d_mo : nullptr, order ? d_or : nullptr,
-                                  mixq ? d_mq : nullptr, pit ? d_pi : nullptr))
-        return rc;
-    if (moments) GPB_HIP(hipMemcpyAsync(moments, d_mo, sizeof(double) * n_mo, hipMemcpyDeviceToHost, ctx->stream));
-    if (order) GPB_HIP(hipMemcpyAsync(order, d_or, sizeof(double) * n_or, hipMemcpyDeviceToHost, ctx->stream));
-    if (mixq) GPB_HIP(hipMemcpyAsync(mixq, d_mq, sizeof(double) * n_mq, hipMemcpyDeviceToHost, ctx->stream));
-    if (pit) GPB_HIP(hipMemcpyAsync(pit, d_pi, sizeof(double) * n_pi, hipMemcpyDeviceToHost, ctx->stream));
-    GPB_HIP(hipStreamSynchronize(ctx->stream));
-    return 0;
+    HostOut so(ctx, on_device != 0);
+    double *d_mo, *d_or, *d_mq, *d_pi;
+    so.out(d_mo, moments, 3 * M);
+    so.out(d_or, order, 2 * nq * M);
+    so.out(d_mq, mixq, nq * M);
+    so.out(d_pi, pit, M);
+    if (const int rc = so.reserve()) return rc;
+    if (const int rc = launch_ppd(ctx, mu_T, var_T, M, S, ld, lv, vadd_dev, yobs_dev, d_mo, d_or, d_mq, d_pi)) return rc;
+    return so.finish();
 }

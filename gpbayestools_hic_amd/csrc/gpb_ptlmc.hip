@@ -274,16 +274,11 @@ extern "C" int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps
         return rc;
     if (nsteps == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    // workspace: rvalo, thetap, grad, the other theta / dfval buffers [T, nd] each; lp, the other fval, the accept flags [T] each
-    if ((rc = ctx_grow(ctx, ctx->ptl_ws, 5 * T * nd + 3 * T))) return rc;
-    double* rvalo = ctx->ptl_ws;
-    double* thetap = rvalo + T * nd;
-    double* gbuf = thetap + T * nd;
-    double* thetaB = gbuf + T * nd;
-    double* dfvalB = thetaB + T * nd;
-    double* lp = dfvalB + T * nd;
-    double* fvalB = lp + T;
-    int* acc = reinterpret_cast<int*>(fvalB + T);
+    PtlWs ws;
+    if ((rc = ctx_carve(ctx, ctx->ptl_ws, [&](Carver<double>& c) { ws.lay(c, T, nd); }))) return rc;
+    double *rvalo = ws.rvalo, *thetap = ws.thetap, *gbuf = ws.grad, *thetaB = ws.thetaB, *dfvalB = ws.dfvalB, *lp = ws.lp,
+           *fvalB = ws.fvalB;
+    int* acc = ws.acc;
     double *th = theta_dev, *fv = fval_dev, *df = dfval_dev;          // the state alternates between the two buffers
     double *th2 = thetaB, *fv2 = fvalB, *df2 = grad ? dfvalB : nullptr;
     const dim3 gT((unsigned)T);

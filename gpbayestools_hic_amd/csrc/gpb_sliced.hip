@@ -337,9 +337,15 @@ void sliced_free(gpb_ctx* ctx) {
     ctx->slA_depth = 0;
 }
 
-const double* sliced_colscale(const gpb_ctx* ctx) {
-    return reinterpret_cast<const double*>(ctx->sl_scale.get()) + ctx->P * round_up(ctx->Np, 128);
+// the pieces of a context's sl_scale as it stands (SlScale, ws_layout.h)
+static SlScale sliced_scales(const gpb_ctx* ctx) {
+    SlScale s;
+    Carver<double> c(ctx->sl_scale.get());
+    s.lay(c, ctx->P, round_up(ctx->Np, 128));
+    return s;
 }
+
+const double* sliced_colscale(const gpb_ctx* ctx) { return sliced_scales(ctx).colscale; }
 
 // Buffers of the sliced path (room for SL_DMAX planes, whichever depth runs); the planes of L^-1 follow a new factorisation or a
 // change of depth here, on first use.
@@ -353,13 +359,11 @@ int sliced_prepare(gpb_ctx* ctx, int depth) {
         if ((rc = ctx_replace(ctx, ctx->slA, a_bytes))) return rc;
         GPB_HIP(hipMemsetAsync(ctx->slA, 0, (size_t)a_bytes, ctx->stream));       // the upper triangle and the rows behind Np: zero for good
     }
-    if (!ctx->sl_scale) {  // doubles [P][Np128] + [P], then P * Np128 ints
-        ctx->slA_valid = false;
-        if ((rc = ctx_replace(ctx, ctx->sl_scale, P * Np128 + P + (P * Np128 + 1) / 2))) return rc;
-    }
-    double* rowscale = reinterpret_cast<double*>(ctx->sl_scale.get());
-    double* colscale = rowscale + P * Np128;
-    int* rowexp = reinterpret_cast<int*>(colscale + P);
+    if (!ctx->sl_scale) ctx->slA_valid = false;
+    SlScale sc;
+    if ((rc = ctx_carve(ctx, ctx->sl_scale, [&](Carver<double>& c) { sc.lay(c, P, Np128); }))) return rc;
+    double *rowscale = sc.rowscale, *colscale = sc.colscale;
+    int* rowexp = sc.rowexp;
     if (!ctx->slA_valid || ctx->slA_depth != depth) {
         hipLaunchKernelGGL(k_sl_rowscale, dim3((unsigned)((Np128 + 3) / 4), (unsigned)P), dim3(256), 0, ctx->stream, ctx->Linv,
                            ctx->amp, rowscale, rowexp, colscale, Np, Np128);
@@ -445,11 +449,10 @@ int launch_vsq_sliced(gpb_ctx* ctx, int64_t W, const int* nrows_dev, int kskip) 
     const int depth = ctx->batch_sliced;
     if (!ctx->slA || !ctx->slA_valid || !ctx->slB || ctx->slA_depth != depth)
         GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced before sliced_prepare");
-    const double* rowscale = reinterpret_cast<const double*>(ctx->sl_scale.get());
-    const double* colscale = rowscale + P * Np128;
+    const SlScale sc = sliced_scales(ctx);
     const int nI = (int)(Np128 / SL_BM);
     const int wtn = sliced_wtn(ctx, depth, P, nI, W, nrows_dev);
-    const SlGP gp{ctx->slA, ctx->slB, rowscale, colscale, ctx->spart, (int)P, 0};
+    const SlGP gp{ctx->slA, ctx->slB, sc.rowscale, sc.colscale, ctx->spart, (int)P, 0};
     return sliced_dispatch<false>(ctx, depth, wtn, gp, Np, Np128, Wld, (int)P, nI, kskip, nrows_dev);
 }
 
@@ -465,11 +468,10 @@ int launch_vsq_sliced_multi(gpb_ctx* const* ctxs, int E, int64_t W, const int* n
         gpb_ctx* c = ctxs[e];
         if (!c->slA || !c->slA_valid || !c->slB || c->Np != Np || c->Wld != Wld || c->batch_sliced != depth || c->slA_depth != depth)
             GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced_multi over a context that is not prepared");
-        const double* rowscale = reinterpret_cast<const double*>(c->sl_scale.get());
-        const double* colscale = rowscale + c->P * Np128;
+        const SlScale sc = sliced_scales(c);
         for (int p = 0; p < (int)c->P; ++p, ++G) {
             if (G >= SL_MAX_GP) GPB_FAIL(GPB_E_STATE, "gpb: internal: launch_vsq_sliced_multi: too many GPs for one table");
-            tab.gp[G] = SlGP{c->slA, c->slB, rowscale, colscale, c->spart, (int)c->P, p};
+            tab.gp[G] = SlGP{c->slA, c->slB, sc.rowscale, sc.colscale, c->spart, (int)c->P, p};
         }
     }
     const int nI = (int)(Np128 / SL_BM);

@@ -378,9 +378,10 @@ int smc_check(gpb_ctx* const* ctxs, int E, int64_t N, const char* who, bool need
     return 0;
 }
 
-// workspace of the chain's first context: wgt, cum, lp [N] each; one particle buffer [N, nd] (the gathered rows of a
-// reweighting, the proposals of a move step); cov [nd, nd]; mean [nd]
-int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd) { return ctx_grow(ctx, ctx->smc_ws, 3 * N + N * nd + nd * nd + nd); }
+// workspace of the chain's first context (SmcWs, ws_layout.h)
+int smc_workspace(gpb_ctx* ctx, int64_t N, int64_t nd, SmcWs& ws) {
+    return ctx_carve(ctx, ctx->smc_ws, [&](Carver<double>& c) { ws.lay(c, N, nd); });
+}
 }  // namespace
 }  // namespace gpb
 
@@ -398,13 +399,9 @@ extern "C" int gpb_chain_smc_reweight(gpb_ctx* const* ctxs, int E, int64_t N, ui
     int rc;
     if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_reweight", false, nd))) return rc;
     GPB_HIP(hipSetDevice(ctx->device));
-    if ((rc = smc_workspace(ctx, N, nd))) return rc;
-    double* wgt = ctx->smc_ws;
-    double* cum = wgt + N;
-    double* lg = cum + N;
-    double* xg = lg + N;
-    double* cov = xg + N * nd;
-    double* mean = cov + nd * nd;
+    SmcWs ws;
+    if ((rc = smc_workspace(ctx, N, nd, ws))) return rc;
+    double *wgt = ws.wgt, *cum = ws.cum, *lg = ws.lp, *xg = ws.xp, *cov = ws.cov, *mean = ws.mean;
     const int d = (int)nd;
     hipLaunchKernelGGL(k_smc_reweight, dim3(1), dim3(SMC_RW_T), 0, ctx->stream, logl_dev, N, ess_fraction, state_dev, wgt, cum);
     hipLaunchKernelGGL(k_smc_resample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, cum, x_dev, logl_dev, N, d,
@@ -436,9 +433,9 @@ extern "C" int gpb_chain_smc_move(gpb_ctx* const* ctxs, int E, int64_t N, int64_
     if ((rc = smc_check(ctxs, E, N, "gpb_chain_smc_move", true, nd))) return rc;      // (all the state checks chain_eval has)
     if (nsteps == 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    if ((rc = smc_workspace(ctx, N, nd))) return rc;
-    double* lp = ctx->smc_ws + 2 * N;
-    double* xp = lp + N;
+    SmcWs ws;
+    if ((rc = smc_workspace(ctx, N, nd, ws))) return rc;
+    double *lp = ws.lp, *xp = ws.xp;
     const int d = (int)nd;
     const size_t lds = sizeof(double) * (size_t)(nd * nd + 4 * nd);
     if (lds > 65536)

@@ -315,11 +315,18 @@ SobolLin sobol_lin(const gpb_ctx* ctx) {
                     ctx->mode == GPB_MODE_NO_PCA || ctx->mode == GPB_MODE_NO_PCA_EXPDIAG};
 }
 
+// the front of the context's sobol_ws as it stands
+SobolWs sobol_pieces(const gpb_ctx* ctx) {
+    SobolWs ws;
+    Carver<double> c(ctx->sobol_ws.get());
+    sobol_lay(ctx, c, ws, true);
+    return ws;
+}
+
 int launch_itab(gpb_ctx* ctx) {
     const int64_t N = ctx->N, Np = ctx->Np, P = ctx->P, dpad = ctx->dpad, nB = Np / 64;
-    double* Itab = ctx->sobol_ws;
-    double* Etab = Itab + P * N * dpad;
-    double* epart = Etab + P * N * dpad;
+    const SobolWs ws = sobol_pieces(ctx);
+    double *Itab = ws.Itab, *Etab = ws.Etab, *epart = ws.epart;
     hipLaunchKernelGGL(k_sobol_itab, dim3((unsigned)nB, (unsigned)P), dim3(64), 0, ctx->stream, ctx->X, ctx->ls, ctx->alpha,
                        sobol_box(ctx), (int)N, Np, (int)pad_front(Np, N), (int)ctx->d, (int)dpad, (int)nB, Itab, Etab, epart);
     GPB_HIP(hipGetLastError());
@@ -329,8 +336,8 @@ int launch_itab(gpb_ctx* ctx) {
 template <int NJ>
 int launch_pairs_t(gpb_ctx* ctx, double* part) {
     const int64_t N = ctx->N, Np = ctx->Np, P = ctx->P, d = ctx->d, dpad = ctx->dpad, nB = Np / 64;
-    const double* Itab = ctx->sobol_ws;
-    const double* Etab = Itab + P * N * dpad;
+    const SobolWs ws = sobol_pieces(ctx);
+    const double *Itab = ws.Itab, *Etab = ws.Etab;
     const size_t red = sizeof(double) * 4 * (2 * NJ + 1), tab = sizeof(double) * (size_t)(3 * 64 * dpad + SB_CST * dpad + 4 * 3 * dpad);
     const size_t sh = tab > red ? tab : red;
     const dim3 grid((unsigned)(nB * nB), (unsigned)(P * (P + 1) / 2), (unsigned)(dpad / NJ));
@@ -344,12 +351,13 @@ int launch_pairs_t(gpb_ctx* ctx, double* part) {
 
 }  // namespace
 
-// doubles of the tables and partials every Sobol call needs: I | E [P][N][dpad] | e partials [P][Np/64]
-int64_t sobol_tab_doubles(const gpb_ctx* ctx) { return 2 * ctx->P * ctx->N * ctx->dpad + ctx->P * (ctx->Np / 64); }
+void sobol_lay(const gpb_ctx* ctx, Carver<double>& c, SobolWs& ws, bool with_part) {
+    const int64_t P = ctx->P, nB = ctx->Np / 64;
+    ws.lay(c, P, ctx->N, ctx->dpad, nB, with_part ? P * (P + 1) / 2 * nB * nB * (2 * ctx->d + 1) : 0);
+}
 
-// Checks the state and the box of a Sobol call (GPB_E_STATE / GPB_E_ARG), keeps the box and (extra >= 0) sizes the workspace for
-// `extra` doubles behind the tables.
-int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi, bool need_transform, int64_t extra) {
+// Checks the state and the box of a Sobol call (GPB_E_STATE / GPB_E_ARG), keeps the box and selects the device.
+int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi, bool need_transform) {
     const std::string w(who);
     if (ctx->N == 0) GPB_FAIL(GPB_E_STATE, w + " before gpb_gp_set");
     if (ctx->multi) GPB_FAIL(GPB_E_STATE, w + ": a gpb_gp_set_multi context is fit-only (its GPs have different designs)");
@@ -364,22 +372,16 @@ int sobol_plan(gpb_ctx* ctx, const char* who, const double* lo, const double* hi
     if (ctx->P * (ctx->P + 1) / 2 > 65535 || ctx->Np / 64 > 255) GPB_FAIL(GPB_E_ARG, w + ": more than 361 GPs or 16320 design points");
     ctx->h_sobol_box.assign(lo, lo + ctx->d);
     ctx->h_sobol_box.insert(ctx->h_sobol_box.end(), hi, hi + ctx->d);
-    if (extra < 0) return 0;
     GPB_HIP(hipSetDevice(ctx->device));
-    return ctx_grow(ctx, ctx->sobol_ws, sobol_tab_doubles(ctx) + extra);
+    return 0;
 }
 
-// doubles behind the tables that launch_sobol needs: tile partials [P (P + 1) / 2][Np/64][Np/64][2d + 1]
-int64_t sobol_part_doubles(const gpb_ctx* ctx) {
-    const int64_t nB = ctx->Np / 64;
-    return ctx->P * (ctx->P + 1) / 2 * nB * nB * (2 * ctx->d + 1);
-}
-
-// e_dev [P], H_dev [P][P][2d + 1] of the planned box (sobol_plan with extra >= sobol_part_doubles)
+// e_dev [P], H_dev [P][P][2d + 1] of the planned box (sobol_ws sized for sobol_lay with its partials)
 int launch_sobol(gpb_ctx* ctx, double* e_dev, double* H_dev) {
     int rc = launch_itab(ctx);
     if (rc) return rc;
-    double* part = ctx->sobol_ws + sobol_tab_doubles(ctx);
+    const SobolWs ws = sobol_pieces(ctx);
+    double* part = ws.part;
     switch (sobol_window(ctx->dpad)) {
         case 8: rc = launch_pairs_t<8>(ctx, part); break;
         case 16: rc = launch_pairs_t<16>(ctx, part); break;
@@ -389,7 +391,7 @@ int launch_sobol(gpb_ctx* ctx, double* e_dev, double* H_dev) {
     }
     if (rc) return rc;
     const int64_t P = ctx->P, nB = ctx->Np / 64;
-    const double* epart = ctx->sobol_ws + 2 * P * ctx->N * ctx->dpad;
+    const double* epart = ws.epart;
     hipLaunchKernelGGL(k_sobol_sum, dim3((unsigned)(P * (P + 1) / 2)), dim3(256), 0, ctx->stream, part, epart, ctx->amp, (int)ctx->d,
                        (int)P, (int)nB, e_dev, H_dev);
     GPB_HIP(hipGetLastError());
@@ -409,7 +411,7 @@ int launch_sobol_main_effect(gpb_ctx* ctx, int64_t j, const double* t_dev, int64
     const int rc = launch_itab(ctx);
     if (rc) return rc;
     const int64_t N = ctx->N, Np = ctx->Np;
-    const double* Etab = ctx->sobol_ws + ctx->P * N * ctx->dpad;
+    const double* Etab = sobol_pieces(ctx).Etab;
     hipLaunchKernelGGL(k_sobol_main_effect, dim3((unsigned)((G + 63) / 64)), dim3(64), 0, ctx->stream, ctx->X, Etab, ctx->alpha, ctx->ls,
                        ctx->amp, t_dev, (int)G, (int)j, (int)N, Np, (int)pad_front(Np, N), (int)ctx->dpad, sobol_lin(ctx), zbuf_dev,
                        curve_dev);

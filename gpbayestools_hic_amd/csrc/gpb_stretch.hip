@@ -455,6 +455,8 @@ struct EmceePlan {
     int R = 1;
     bool sim = false, plain = false, premark = false, fuse_ap = false, balanced = false;
     int pre = 0;
+    McWs mc{};                     // the proposal workspace (ctx->mc_ws)
+    BalWs bal{};                   // balanced: the flags / ranks / scatter lists (ctx->bal_ws), else null
 };
 
 int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
@@ -485,9 +487,7 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     for (int e = 0; e < E; ++e)                        // all workspaces now: the loop holds pointers into them
         if ((rc = ensure_wcap(ctxs[e], chunk))) { if (e) ctx->err = ctxs[e]->err; return rc; }
     if (!pl.plain && (rc = ensure_lr_blocks(ctx, E))) return rc;
-    // proposal workspace: two sets of q[nh][d], factor[nh], lpq[nh] (the fused accept + proposal kernel reads one set and
-    // writes the other) and a second log-probability vector [nwalkers]
-    if ((rc = ctx_grow(ctx, ctx->mc_ws, 2 * nh * (d + 3)))) return rc;
+    if ((rc = ctx_carve(ctx, ctx->mc_ws, [&](Carver<double>& c) { pl.mc.lay(c, nh, d); }))) return rc;
     // the gather kernel counts the flags in front of each of its workgroups itself: fine for a rank's rows of an
     // ensemble, quadratic for very large batches, which keep the marking kernel with its per-workgroup counts
     pl.premark = !pl.plain && ctx->premark && chunk <= 16384;
@@ -504,7 +504,7 @@ int emcee_plan(gpb_ctx* const* ctxs, int E, int64_t nwalkers, EmceePlan& pl) {
     // the contiguous shares rarely differ by a tile.  0 = never (default), 1 = from 8 ranks on, 2 = always.
     pl.balanced = pl.pre == 2 && R > 1 && nh <= 16384 &&
                   (ctx->balance_shards == 2 || (ctx->balance_shards == 1 && R >= 8));
-    if (pl.balanced && (rc = ctx_grow(ctx, ctx->bal_ws, 4 * nh + 2 * (4 + chunk) + 16))) return rc;
+    if (pl.balanced && (rc = ctx_carve(ctx, ctx->bal_ws, [&](Carver<int>& c) { pl.bal.lay(c, nh, chunk); }))) return rc;
     if (pl.pre && (rc = ensure_cmp_rows(ctx, d))) return rc;
     return 0;
 }
@@ -529,27 +529,14 @@ extern "C" int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev,
     const int64_t nh = pl.nh, d = pl.d, chunk = pl.chunk, r0 = pl.r0;
     const int R = pl.R, pre = pl.pre;
     const bool sim = pl.sim, plain = pl.plain, premark = pl.premark, fuse_ap = pl.fuse_ap, balanced = pl.balanced;
-    double* qs[2] = {ctx->mc_ws, ctx->mc_ws + nh * (d + 2)};
-    double* factors[2] = {qs[0] + nh * d, qs[1] + nh * d};
-    double* lpqs[2] = {factors[0] + nh, factors[1] + nh};
-    double* lp2 = ctx->mc_ws + 2 * nh * (d + 2);
+    double *const *qs = pl.mc.q, *const *factors = pl.mc.factor, *const *lpqs = pl.mc.lpq, *lp2 = pl.mc.lp2;
     const Ensemble en{nh, (int)d, seed, half_bits(nwalkers), randomize_split ? 1 : 0};
     const dim3 g32((unsigned)((nh * 32 + 255) / 256));
-    int *bal_flags[2] = {nullptr, nullptr}, *bal_rank[2] = {nullptr, nullptr}, *bal_cmp[2] = {nullptr, nullptr},
-        *bal_meta[2] = {nullptr, nullptr};
-    if (balanced) {
-        const int64_t need = 4 * nh + 2 * (4 + chunk) + 16;
-        GPB_HIP(hipMemsetAsync(ctx->bal_ws, 0, sizeof(int) * (size_t)need, ctx->stream));
-        for (int b = 0; b < 2; ++b) {
-            bal_flags[b] = ctx->bal_ws + b * nh;
-            bal_rank[b] = ctx->bal_ws + 2 * nh + b * nh;
-            bal_cmp[b] = ctx->bal_ws + 4 * nh + b * (4 + chunk);
-            bal_meta[b] = ctx->bal_ws + 4 * nh + 2 * (4 + chunk) + 4 * b;
-        }
-    }
+    int *const *bal_flags = pl.bal.flags, *const *bal_rank = pl.bal.rank, *const *bal_cmp = pl.bal.cmp, *const *bal_meta = pl.bal.meta;
+    if (balanced) GPB_HIP(hipMemsetAsync(ctx->bal_ws, 0, sizeof(int) * (size_t)pl.bal.n, ctx->stream));
     if (pre) GPB_HIP(hipMemsetAsync(ctx->cmp_idx, 0, 2 * sizeof(int), ctx->stream));
-    if (sim) hipLaunchKernelGGL(k_fill, dim3((unsigned)((2 * nh * (d + 2) + 255) / 256)), dim3(256), 0, ctx->stream, ctx->mc_ws,
-                                2 * nh * (d + 2), -INFINITY);
+    if (sim) hipLaunchKernelGGL(k_fill, dim3((unsigned)((pl.mc.n_sets + 255) / 256)), dim3(256), 0, ctx->stream, qs[0], pl.mc.n_sets,
+                                -INFINITY);
     unsigned long long* const live = pre == 2 && ctx->profile ? ctx->rows_live : (unsigned long long*)nullptr;
     double* lp_cur = lp_dev;                           // fuse_ap: lp alternates between the caller's vector and lp2
     double* lp_alt = lp2;

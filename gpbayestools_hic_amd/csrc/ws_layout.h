@@ -1,0 +1,214 @@
+// ws_layout.h — what lies inside every context buffer that holds more than one piece: one struct of pointers per workspace and
+// the list of take() calls that places them (ws_carve.h).  Functions of plain integers, so tests/host/ws_carve_check.cpp runs
+// every one of them on the host.  The entry points size the buffers through ctx_carve (gpb_internal.h) with these lists and read
+// the pieces from the structs: no offset is written down a second time.
+#pragma once
+#include "ws_carve.h"
+
+namespace gpb {
+
+constexpr int64_t WS_PAD = 128;         // walker-batch padding granule (WPAD of gpb_internal.h)
+inline int64_t ws_round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// mc_ws (gpb_chain_emcee_run): two sets of proposals q [nh][d], stretch factors [nh] and their log-probabilities [nh] (the
+// fused accept + proposal kernel reads one set and writes the other), then a second log-probability vector [2 nh]
+struct McWs {
+    double *q[2], *factor[2], *lpq[2], *lp2;
+    int64_t n_sets;                 // doubles of the two sets in front of lp2
+    void lay(Carver<double>& c, int64_t nh, int64_t d) {
+        for (int b = 0; b < 2; ++b) {
+            q[b] = c.take<double>(nh * d);
+            factor[b] = c.take<double>(nh);
+            lpq[b] = c.take<double>(nh);
+        }
+        n_sets = c.total();
+        lp2 = c.take<double>(2 * nh);
+    }
+};
+
+// bal_ws (balanced shards of gpb_chain_emcee_run), per buffer set: the flags and ranks of all nh rows, this rank's counter +
+// index list [4 + chunk], four ints of slice bounds (room for four sets of them)
+struct BalWs {
+    int *flags[2], *rank[2], *cmp[2], *meta[2];
+    int64_t n;                      // ints in all
+    void lay(Carver<int>& c, int64_t nh, int64_t chunk) {
+        for (int b = 0; b < 2; ++b) flags[b] = c.take<int>(nh);
+        for (int b = 0; b < 2; ++b) rank[b] = c.take<int>(nh);
+        for (int b = 0; b < 2; ++b) cmp[b] = c.take<int>(4 + chunk);
+        meta[0] = c.take<int>(16);
+        meta[1] = meta[0] ? meta[0] + 4 : nullptr;
+        n = c.total();
+    }
+};
+
+// ptl_ws (gpb_chain_ptlmc_run): draws, proposals, their gradient, the other theta / dfval buffers [T][nd] each; the proposals'
+// lp and the other fval [T] each; the accept flags [T] (int)
+struct PtlWs {
+    double *rvalo, *thetap, *grad, *thetaB, *dfvalB, *lp, *fvalB;
+    int* acc;
+    void lay(Carver<double>& c, int64_t T, int64_t nd) {
+        rvalo = c.take<double>(T * nd);
+        thetap = c.take<double>(T * nd);
+        grad = c.take<double>(T * nd);
+        thetaB = c.take<double>(T * nd);
+        dfvalB = c.take<double>(T * nd);
+        lp = c.take<double>(T);
+        fvalB = c.take<double>(T);
+        acc = c.take<int>(T);
+    }
+};
+
+// smc_ws (gpb_chain_smc_*): weights, their scan, log-probabilities [N] each; one particle buffer [N][nd] (the gathered rows of
+// a reweighting — with their log-likelihoods in lp —, the proposals of a move step); cov [nd][nd]; mean [nd]
+struct SmcWs {
+    double *wgt, *cum, *lp, *xp, *cov, *mean;
+    void lay(Carver<double>& c, int64_t N, int64_t nd) {
+        wgt = c.take<double>(N);
+        cum = c.take<double>(N);
+        lp = c.take<double>(N);
+        xp = c.take<double>(N * nd);
+        cov = c.take<double>(nd * nd);
+        mean = c.take<double>(nd);
+    }
+};
+
+// design_ws (gpb_design_begin's block): x_c [C][d] | x_r [R][d] | w [Rp] | g [P] | s(c,c) [P][Cp] | V_c [P][Np][Cp] |
+// V_r [P][Np][Rp] | S_rc [P][Rp][Cp] | the candidates' simulation noise [P][Cp] (Cp, Rp: C, R padded to 128).  Every part
+// starts on an even offset: the GEMM's operands are read two at a time.
+struct DesignWs {
+    int64_t Cp, Rp;
+    double *xc, *xr, *w, *g, *dg, *vc, *vr, *s, *sc;
+    void lay(Carver<double>& c, int64_t C, int64_t R, int64_t d, int64_t P, int64_t Np) {
+        Cp = ws_round_up(C, WS_PAD);
+        Rp = ws_round_up(R, WS_PAD);
+        xc = c.take<double>(C * d, 2);
+        xr = c.take<double>(R * d, 2);
+        w = c.take<double>(Rp);
+        g = c.take<double>(P, 2);
+        dg = c.take<double>(P * Cp);
+        vc = c.take<double>(P * Np * Cp);
+        vr = c.take<double>(P * Np * Rp);
+        s = c.take<double>(P * Rp * Cp);
+        sc = c.take<double>(P * Cp);
+    }
+};
+
+// design_run (gpb_chain_design_run), per context: the picks' scaled rows U [T][P][Cp] | the pending u_r [P][Rp] | chunk
+// partials [P][nch][Cp] | scores J [Cp] | denominators [P]; the chain's first context also the pick (int) and the eligibility
+// flags [Cp] (bytes) of a run that was given none
+struct DesignRun {
+    double *U, *ur, *part, *J, *den;
+    int* pick;
+    uint8_t* elig;
+    void lay(Carver<double>& c, int64_t T, int64_t P, int64_t Cp, int64_t Rp, int64_t nch, bool first) {
+        U = c.take<double>(T * P * Cp);
+        ur = c.take<double>(P * Rp);
+        part = c.take<double>(P * nch * Cp);
+        J = c.take<double>(Cp);
+        den = c.take<double>(P, 2);
+        pick = c.take<int>(first ? 1 : 0, 2);
+        elig = c.take<uint8_t>(first ? Cp : 0);
+    }
+};
+
+// gpb_mcmc_diag's results in out_stage: rho [d][max_lag + 1] (n_rho doubles, 0 without the autocorrelation) | tau [d] |
+// moments [d][3] | rhat [d] | window [d] | nconst [d] (int, back to back)
+struct DiagStage {
+    double *rho, *tau, *moments, *rhat;
+    int *window, *nconst;
+    void lay(Carver<double>& c, int64_t n_rho, int64_t d) {
+        rho = c.take<double>(n_rho);
+        tau = c.take<double>(d);
+        moments = c.take<double>(3 * d);
+        rhat = c.take<double>(d);
+        window = c.take<int>(2 * d);
+        nconst = window ? window + d : nullptr;
+    }
+};
+
+// diag_ws (launch_mcmc_diag), G parameters at a time: Y [G][nsp][nwp] | lag partials [G][nband][128] | walker statistics
+// [G][nwp][nstats]
+struct DiagWs {
+    double *Y, *part, *stats;
+    void lay(Carver<double>& c, int64_t G, int64_t nsp, int64_t nwp, int64_t nband, int64_t nstats) {
+        Y = c.take<double>(G * nsp * nwp);
+        part = c.take<double>(G * nband * 128);
+        stats = c.take<double>(G * nwp * nstats);
+    }
+};
+
+// marg_ws (launch_chain_marginals), 8-byte units: edges | h1 | outside [d] | h2 | pairs [n_pairs][2] (int) | integer weights |
+// one code byte per (sample, parameter) of a sample group.  h1 | outside | h2 are zeroed and copied out as one run of counts.
+struct MargWs {
+    double* edges;
+    uint64_t *h1, *out, *h2, *qw;
+    int* pairs;
+    unsigned char* codes;
+    void lay(Carver<int64_t>& c, int64_t n_edges, int64_t n_h1, int64_t d, int64_t n_h2, int64_t n_pairs, int64_t n_qw,
+             int64_t n_code_bytes) {
+        edges = c.take<double>(n_edges);
+        h1 = c.take<uint64_t>(n_h1);
+        out = c.take<uint64_t>(d);
+        h2 = c.take<uint64_t>(n_h2);
+        pairs = c.take<int>(2 * n_pairs);
+        qw = c.take<uint64_t>(n_qw);
+        codes = c.take<unsigned char>(n_code_bytes);
+    }
+};
+
+// sl_scale (gpb_sliced.hip): row scales [P][Np128] | column scales [P] | row exponents [P][Np128] (int)
+struct SlScale {
+    double *rowscale, *colscale;
+    int* rowexp;
+    void lay(Carver<double>& c, int64_t P, int64_t Np128) {
+        rowscale = c.take<double>(P * Np128);
+        colscale = c.take<double>(P);
+        rowexp = c.take<int>(P * Np128);
+    }
+};
+
+// cv_ws (gpb_cv.hip): the folds of the planned call, idx [n_idx] | fold_ptr [nf + 1] (n_folds ints in all, none for plain
+// leave-one-out; padded to an even count: the doubles behind them stay aligned), then the leave-one-out path's partials
+struct CvWs {
+    int* folds;
+    double* part;
+    void lay(Carver<int>& c, int64_t n_folds, int64_t n_part) {
+        folds = c.take<int>(n_folds, 2);
+        part = c.take<double>(n_part);
+    }
+};
+
+// the front of sobol_ws (gpb_sobol.hip): the I and E tables [P][N][dpad] each | e partials [P][nB] | launch_sobol's tile
+// partials [P (P + 1) / 2][nB][nB][2d + 1] (n_part doubles; none for a call that only needs the tables).  What else a call needs
+// (scratch, staged results) it carves behind these.
+struct SobolWs {
+    double *Itab, *Etab, *epart, *part;
+    void lay(Carver<double>& c, int64_t P, int64_t N, int64_t dpad, int64_t nB, int64_t n_part) {
+        Itab = c.take<double>(P * N * dpad);
+        Etab = c.take<double>(P * N * dpad);
+        epart = c.take<double>(P * nB);
+        part = c.take<double>(n_part);
+    }
+};
+
+// gbuf (gpb_grad.hip), the pieces of one gradient evaluation of W rows, 32 doubles the granule: beta^T [P][Wld][Np] | dmean,
+// dvar [W][P][d] | the likelihood's weights of mean and variance [W][P] | mapped rows [W][d] | the map's Jacobian [W][d][din] |
+// the likelihood's global scratch | staged input rows | staged results
+struct GradWs {
+    double *bt, *dm, *dv, *wmu, *wv, *xg, *jm, *lw, *xin, *out;
+    void lay(Carver<double>& c, bool need_beta, int64_t P, int64_t Wld, int64_t Np, int64_t W, int64_t d, int64_t din, bool mapped,
+             int64_t lw_doubles, int64_t n_out) {
+        bt = c.take<double>(need_beta ? P * Wld * Np : 0, 32);
+        dm = c.take<double>(W * P * d, 32);
+        dv = c.take<double>(need_beta ? W * P * d : 0, 32);
+        wmu = c.take<double>(W * P, 32);
+        wv = c.take<double>(W * P, 32);
+        xg = c.take<double>(W * d, 32);
+        jm = c.take<double>(mapped ? W * d * din : 0, 32);
+        lw = c.take<double>(lw_doubles, 32);
+        xin = c.take<double>(W * (din > d ? din : d), 32);
+        out = c.take<double>(n_out, 32);
+    }
+};
+
+}  // namespace gpb

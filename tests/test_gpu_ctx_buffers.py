@@ -5,6 +5,7 @@ would be: no workspace sized by the old (P, Np) survives in a form its successor
 Shapes: A = (N 200, d 5, P 3) and B = (N 70, d 3, P 4: Np = 128, 48 rows of padding in front and 10 behind); query batches
 of 37 rows, then 200, so the walker workspaces grow once."""
 import ctypes
+import gc
 import os
 
 import numpy as np
@@ -79,6 +80,9 @@ def test_nothing_leaks(tmp_path):
     with nat.debug_library():
         lib = nat.load()
         mcmc._utility_engine()               # (whichever library it binds, it exists before the first reading and stays)
+        # (with GPB_DEBUG_LIB=1 the whole suite's engines live in this library: one that an earlier test dropped but the collector
+        # has not yet finalised would give its buffers back between two readings)
+        gc.collect()
         live0 = _pool_live(lib)
 
         eng = GPEngine(0)
