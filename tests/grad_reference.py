@@ -26,13 +26,16 @@ def state_from_oracle(emu):
 
 def state_from_emulator(emu):
     """the same state for a trained gpbayestools_hic_amd.Emulator, factorised by the oracle (scipy) from its design, its GP
-    targets and its hyper-parameters — nothing is read back from the device"""
+    targets and its hyper-parameters — nothing is read back from the device.  A stochastic-kriging emulator
+    (simulation_error=True) carries its per-point noise point_noise_ [P, N]: GP p is factored with the vector
+    emu.alpha + point_noise_[p] on its training diagonal."""
     X = np.asarray(emu._X_train, float)
     Z = np.asarray(emu._Z_train, float)
     kind = O.KIND_NAMES[emu.kernel_type_]
+    noise = getattr(emu, "point_noise_", None)
     L, a = [], []
     for p in range(Z.shape[0]):
-        Lp, ap = O.gp_factor(X, Z[p], emu.thetas_[p], kind, emu.alpha)
+        Lp, ap = O.gp_factor(X, Z[p], emu.thetas_[p], kind, emu.alpha if noise is None else emu.alpha + np.asarray(noise[p], float))
         L.append(_t(Lp)); a.append(_t(ap))
     no_pca = emu.perform_no_PCA_
     return dict(X=_t(X), thetas=_t(emu.thetas_), L=L, a=a, kind=kind, mode=int(emu._mode),

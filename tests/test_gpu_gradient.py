@@ -19,9 +19,11 @@ def _rowerr(g, ref):
     return np.abs(g - ref).max(1) / np.maximum(np.abs(ref).max(1), 1.0)
 
 
-def _emulator(tmp, N, d, M, P, kernel="RBF", no_pca=False, expdiag=False, ell=1.5, seed=0, mapped=False):
+def _emulator(tmp, N, d, M, P, kernel="RBF", no_pca=False, expdiag=False, ell=1.5, seed=0, mapped=False, yerr=0.01,
+              simulation_error=False):
     """an Emulator trained at fixed hyper-parameters on synthetic data, plus a Chain over it whose experiment is the noiseless
-    prediction at the truth point (5 % errors)"""
+    prediction at the truth point (5 % errors).  yerr: the training events' statistical errors, a number or a callable of the
+    observables Y -> [N, M]; simulation_error: stochastic kriging, those errors on the GPs' training diagonals"""
     from gpbayestools_hic_amd import synth
     from gpbayestools_hic_amd.emulator import Emulator
     from gpbayestools_hic_amd.mcmc import Chain
@@ -30,10 +32,10 @@ def _emulator(tmp, N, d, M, P, kernel="RBF", no_pca=False, expdiag=False, ell=1.
     X = synth.lhs(N, d, seed=synth.SEED + seed)
     Y = synth.observables(X, M, seed=synth.SEED + 1 + seed)
     tp, pf, ep = (os.path.join(tmp, n) for n in ("train.pkl", "par.txt", "exp.pkl"))
-    synth.write_training_pickle(tp, X, Y, 0.01)
+    synth.write_training_pickle(tp, X, Y, yerr(Y) if callable(yerr) else yerr)
     synth.write_parameter_file(pf, lo, hi)
     emu = Emulator(training_set_path=tp, parameter_file=pf, npc=P, device=0, perform_no_PCA=no_pca,
-                   logTrafo=expdiag, exp_and_cov_diagonal=expdiag, parameterTrafoPCA=mapped)
+                   logTrafo=expdiag, exp_and_cov_diagonal=expdiag, parameterTrafoPCA=mapped, simulation_error=simulation_error)
     ktype = {"RBF": "RBF", "Matern15": "Matern", "Matern25": "Matern25"}[kernel]
     ngp = M if no_pca else P
     if mapped:

@@ -74,3 +74,40 @@ def test_outside_rows_have_zero_gradient_and_two_emulators_add():
                      posterior=False)
     ok = np.arange(6) != 1
     assert np.max(np.abs(v[ok] - ref[ok]) / np.abs(ref[ok])) < 1e-12
+
+
+@pytest.mark.parametrize("mode", [O.MODE_PCA, O.MODE_NO_PCA])
+def test_vector_alpha_state_matches_oracle_and_central_differences(mode):
+    """stochastic kriging: every GP factored with its own vector alpha + s_p on the training diagonal.  state_from_emulator
+    reads the vector from point_noise_ (here off a stand-in carrying the attributes it reads of an Emulator); the value agrees
+    with the oracle's own vector-alpha emulator at 1e-12, autograd with central differences of the oracle at 1e-6, and the
+    noise reaches the factors (the scalar-alpha state gives another value)."""
+    import types
+    emu, yexp, cexp, Xw = _case(O.KIND_RBF, mode)
+    rng = np.random.default_rng(7)
+    s = rng.uniform(0.002, 0.2, (emu.npc, N))                 # a factor 100 across the points, another row per GP
+    emu.L, emu.a = [], []
+    for p in range(emu.npc):
+        L, a = O.gp_factor(emu.X, np.ascontiguousarray(emu.Z[:, p]), emu.thetas[p], emu.kind, emu.alpha_reg + s[p])
+        emu.L.append(L); emu.a.append(a)
+    no_pca = mode == O.MODE_NO_PCA
+    ns = types.SimpleNamespace
+    stand_in = ns(_X_train=emu.X, _Z_train=np.ascontiguousarray(emu.Z.T), kernel_type_="RBF", thetas_=emu.thetas,
+                  alpha=emu.alpha_reg, point_noise_=s, perform_no_PCA_=no_pca, _mode=mode, _A=emu.A, _cov_trunc=emu.cov_trunc,
+                  scaler=ns(mean_=emu.mu, scale_=emu.scale))
+    st = R.state_from_emulator(stand_in)
+    lo, hi = np.zeros(D), np.ones(D)
+    ref = _oracle_lp(emu, Xw, yexp, cexp)
+    got, g = R.value_and_grad(lambda x: R.log_posterior([st], x, lo, hi, yexp, cexp), Xw)
+    assert np.all(np.isfinite(ref))
+    assert np.max(np.abs(got - ref) / np.maximum(np.abs(ref), 1.0)) < 1e-12
+    stand_in.point_noise_ = None
+    plain = R.log_posterior([R.state_from_emulator(stand_in)], R._t(Xw), lo, hi, yexp, cexp).numpy()
+    assert np.min(np.abs(plain - ref) / np.maximum(np.abs(ref), 1.0)) > 1e-6
+    h = 1e-5
+    fd = np.empty_like(g)
+    for j in range(D):
+        e = np.zeros(D); e[j] = h
+        fd[:, j] = (_oracle_lp(emu, Xw + e, yexp, cexp) - _oracle_lp(emu, Xw - e, yexp, cexp)) / (2 * h)
+    scale = np.maximum(np.abs(g).max(1), 1.0)
+    assert np.all(np.abs(g - fd).max(1) / scale < 1e-6), np.abs(g - fd).max(1) / scale
