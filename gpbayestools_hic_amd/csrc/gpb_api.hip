@@ -14,12 +14,6 @@ using namespace gpb;
 
 namespace {
 
-int pick_dpad(int64_t d) {
-    const int opts[] = {8, 16, 20, 24, 32, 48, 64};     // 20: the reference's analyses have 17-20 model parameters
-    for (int o : opts) if (d <= o) return o;
-    return -1;
-}
-
 // [P][Wld] -> [W][P]
 __global__ void k_transpose_pw(const double* __restrict__ src, double* __restrict__ dst, int64_t W, int64_t Wld,
                                int P) {

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_kss(const double* __restrict__ Xs, int6
                 const double df = Xs[i * d + k] / l - Xs[j * d + k] / l;
                 r2 = fma(df, df, r2);
             }
-            v = amp[p] * shape_fn_c<KIND>(r2);
+            v = amp[p] * shape_fn<KIND>(r2);
         }
     }
     cov[((int64_t)p * Wld + i) * Wld + j] = v;
@@ -97,13 +97,12 @@ int launch_predict_cov(gpb_ctx* ctx, const double* Xs_dev, int64_t W, double* co
     const int64_t Wld = ctx->Wld;
     if ((rc = launch_vmat(ctx))) return rc;
     dim3 gk((unsigned)((Wc + 15) / 16), (unsigned)((Wc + 15) / 16), (unsigned)P);
-#define GPB_KSS(KIND)                                                                                        \
-    hipLaunchKernelGGL(k_kss<KIND>, gk, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, ctx->ls, (int)ctx->dpad, \
-                       ctx->amp, ctx->noise, ctx->covbuf, Wc)
-    if (ctx->kind == GPB_KERNEL_RBF) GPB_KSS(GPB_KERNEL_RBF);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_KSS(GPB_KERNEL_MATERN15);
-    else GPB_KSS(GPB_KERNEL_MATERN25);
-#undef GPB_KSS
+    rc = with_kind(ctx->kind, [&](auto K) {
+        hipLaunchKernelGGL(k_kss<decltype(K)::value>, gk, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, ctx->ls, (int)ctx->dpad,
+                           ctx->amp, ctx->noise, ctx->covbuf, Wc);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_kss");
     dim3 gc((unsigned)(Wc / 128), (unsigned)(Wc / 128), (unsigned)P);
     hipLaunchKernelGGL(k_cov_update, gc, dim3(256), 0, ctx->stream, ctx->vbuf, ctx->covbuf, Np, Wld, Wc);
     dim3 gp((unsigned)((W + 255) / 256), (unsigned)W, (unsigned)P);

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_design_kern(const double* __restrict__ 
     const int p = blockIdx.z;
     const int64_t r = (int64_t)blockIdx.y * 16 + (threadIdx.x >> 4), c = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
     double v = 0.0;
-    if (r < R && c < C) v = amp[p] * shape_fn_c<KIND>(design_r2(Xr + r * d, Xc + c * d, ls + p * dpad, d));
+    if (r < R && c < C) v = amp[p] * shape_fn<KIND>(design_r2(Xr + r * d, Xc + c * d, ls + p * dpad, d));
     S[((int64_t)p * Rp + r) * Cp + c] = v;
 }
 
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void k_design_row(const double* __restrict__ V
     if (threadIdx.x >= 64) return;
     double u = 0.0;
     if (c < C) {
-        const double k = amp[p] * shape_fn_c<KIND>(design_r2(Xc + (int64_t)cs * d, Xc + c * d, ls + p * dpad, d));
+        const double k = amp[p] * shape_fn<KIND>(design_r2(Xc + (int64_t)cs * d, Xc + c * d, ls + p * dpad, d));
         u = ((k - sv) - su) / sqrt(den[p]);
         dg[(int64_t)p * Cp + c] = fma(-u, u, dg[(int64_t)p * Cp + c]);
     }
@@ -288,13 +288,12 @@ extern "C" int gpb_design_begin(gpb_ctx* ctx, const double* Xc_dev, int64_t C, c
     if (rc) return rc;
     const int64_t k0 = pad_front(Np, ctx->N);          // a multiple of the GEMM's K-step
     const dim3 gk((unsigned)(L.Cp / 16), (unsigned)(L.Rp / 16), (unsigned)P);
-#define GPB_DS_KERN(KIND)                                                                                                       \
-    hipLaunchKernelGGL(k_design_kern<KIND>, gk, dim3(256), 0, st, L.xr, (int)R, L.xc, (int)C, (int)d, ctx->ls, (int)ctx->dpad, \
-                       ctx->amp, L.s, L.Rp, L.Cp)
-    if (ctx->kind == GPB_KERNEL_RBF) GPB_DS_KERN(GPB_KERNEL_RBF);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_DS_KERN(GPB_KERNEL_MATERN15);
-    else GPB_DS_KERN(GPB_KERNEL_MATERN25);
-#undef GPB_DS_KERN
+    rc = with_kind(ctx->kind, [&](auto K) {
+        hipLaunchKernelGGL(k_design_kern<decltype(K)::value>, gk, dim3(256), 0, st, L.xr, (int)R, L.xc, (int)C, (int)d, ctx->ls,
+                           (int)ctx->dpad, ctx->amp, L.s, L.Rp, L.Cp);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_design_kern");
     hipLaunchKernelGGL(k_design_gemm, dim3((unsigned)(L.Cp / 128), (unsigned)(L.Rp / 128), (unsigned)P), dim3(256), 0, st, L.vr,
                        L.vc, L.s, Np, k0, L.Rp, L.Cp, (int)R, (int)C);
     hipLaunchKernelGGL(k_design_diag, dim3((unsigned)(L.Cp / 64), (unsigned)P), dim3(256), 0, st, L.vc, ctx->amp, L.dg, Np, k0,
@@ -389,13 +388,12 @@ extern "C" int gpb_chain_design_run(gpb_ctx* const* ctxs, int E, int64_t T, uint
             hipLaunchKernelGGL(k_design_ur, dim3((unsigned)((Rp + 255) / 256), (unsigned)P), dim3(256), 0, st, L.s, L.dg, c->noise,
                                c->alpha_reg, c->design_noise ? L.sc : nullptr, pick, Rp, Cp, (int)R, run[e].ur, run[e].den);
             const dim3 gr((unsigned)(Cp / 64), (unsigned)P);
-#define GPB_DS_ROW(KIND)                                                                                                          \
-    hipLaunchKernelGGL(k_design_row<KIND>, gr, dim3(256), 0, st, L.vc, run[e].U, L.xc, c->ls, c->amp, run[e].den, pick,  \
-                       L.dg, c->Np, k0, Cp, (int)C, (int)c->d, (int)c->dpad, P, (int)t)
-            if (c->kind == GPB_KERNEL_RBF) GPB_DS_ROW(GPB_KERNEL_RBF);
-            else if (c->kind == GPB_KERNEL_MATERN15) GPB_DS_ROW(GPB_KERNEL_MATERN15);
-            else GPB_DS_ROW(GPB_KERNEL_MATERN25);
-#undef GPB_DS_ROW
+            const int rc = with_kind(c->kind, [&](auto K) {
+                hipLaunchKernelGGL(k_design_row<decltype(K)::value>, gr, dim3(256), 0, st, L.vc, run[e].U, L.xc, c->ls, c->amp,
+                                   run[e].den, pick, L.dg, c->Np, k0, Cp, (int)C, (int)c->d, (int)c->dpad, P, (int)t);
+                return 0;
+            });
+            if (rc) return dispatched(ctx, rc, "k_design_row");
         }
     }
     for (int e = 0; e < E; ++e) ctxs[e]->design_ready = false;     // S and s(c, c) are conditioned on the picks now

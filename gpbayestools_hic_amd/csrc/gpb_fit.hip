@@ -13,20 +13,6 @@
 
 namespace gpb {
 
-// ------------------------------------------------------------------ shape functions
-template <int KIND>
-__device__ __forceinline__ double shape_fn(double r2) {
-    if (KIND == GPB_KERNEL_RBF) {
-        return exp(-0.5 * r2);                                   // sk:kernels.py:1557
-    } else if (KIND == GPB_KERNEL_MATERN15) {
-        const double t = sqrt(r2) * 1.7320508075688772;          // sk:kernels.py:1721-1723
-        return (1.0 + t) * exp(-t);
-    } else {
-        const double t = sqrt(r2) * 2.23606797749979;            // sk:kernels.py:1724-1726
-        return (1.0 + t + t * t / 3.0) * exp(-t);
-    }
-}
-
 // ------------------------------------------------------------------ design scaling
 // Xsc[p][n][k] = X[n][k] / l_p[k]   (sklearn divides: sk:kernels.py:1556,1564)
 __global__ void k_scale_design(const double* __restrict__ X, const double* __restrict__ ls,
@@ -262,47 +248,30 @@ __global__ __launch_bounds__(256) void k_kmat_mfma(const double* __restrict__ Xc
         }
 }
 
-template <int KIND>
-static void launch_kmat_mfma(gpb_ctx* ctx) {
-    const int64_t nb = ctx->Np / 64;
-    dim3 grid((unsigned)(nb * (nb + 1) / 2), (unsigned)ctx->P);
-#define GPB_KM(DP)                                                                                                  \
-    hipLaunchKernelGGL((k_kmat_mfma<KIND, DP>), grid, dim3(256), 0, ctx->stream, ctx->Xc, ctx->dnorm, ctx->amp,     \
-                       ctx->noise, ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np,                            \
-                       ctx->n_diff > 0 ? ctx->gpform : nullptr,                                                     \
-                       reinterpret_cast<const int2*>(ctx->kmtiles.get()))
-    switch (ctx->dpad) {
-        case 8: GPB_KM(8); break;
-        case 16: GPB_KM(16); break;
-        case 20: GPB_KM(20); break;
-        case 24: GPB_KM(24); break;
-        case 32: GPB_KM(32); break;
-        case 48: GPB_KM(48); break;
-        default: GPB_KM(64); break;
-    }
-#undef GPB_KM
-}
-
-static void launch_kmat_diff(gpb_ctx* ctx, const int* form) {
-    dim3 grid((unsigned)(ctx->Np / 64), (unsigned)(ctx->Np / 64), (unsigned)ctx->P);
-    const size_t sh = 2 * 64 * (ctx->dpad + 1) * sizeof(double);
-#define GPB_KMAT(KIND)                                                                          \
-    hipLaunchKernelGGL(k_kmat<KIND>, grid, dim3(256), sh, ctx->stream, ctx->Xsc, ctx->amp,       \
-                       ctx->noise, ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np, (int)ctx->dpad, form)
-    if (ctx->kind == GPB_KERNEL_RBF) GPB_KMAT(GPB_KERNEL_RBF);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_KMAT(GPB_KERNEL_MATERN15);
-    else GPB_KMAT(GPB_KERNEL_MATERN25);
-#undef GPB_KMAT
-}
-
 int launch_kmat(gpb_ctx* ctx) {
     // each GP in its distance form (gpform); a launch with no GP is left out
-    if (ctx->n_diff < ctx->P) {
-        if (ctx->kind == GPB_KERNEL_RBF) launch_kmat_mfma<GPB_KERNEL_RBF>(ctx);
-        else if (ctx->kind == GPB_KERNEL_MATERN15) launch_kmat_mfma<GPB_KERNEL_MATERN15>(ctx);
-        else launch_kmat_mfma<GPB_KERNEL_MATERN25>(ctx);
-    }
-    if (ctx->n_diff > 0) launch_kmat_diff(ctx, ctx->n_diff < ctx->P ? ctx->gpform : nullptr);
+    const int rc = with_kind(ctx->kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        const int64_t nb = ctx->Np / 64;
+        const bool mixed = ctx->n_diff > 0 && ctx->n_diff < ctx->P;
+        if (ctx->n_diff < ctx->P) {
+            const int rc = with_dpad(ctx->dpad, [&](auto D) {
+                hipLaunchKernelGGL((k_kmat_mfma<KIND, decltype(D)::value>), dim3((unsigned)(nb * (nb + 1) / 2), (unsigned)ctx->P),
+                                   dim3(256), 0, ctx->stream, ctx->Xc, ctx->dnorm, ctx->amp, ctx->noise, ctx->alpha_reg, ctx->pnoise,
+                                   ctx->K, ctx->sel(), ctx->Np, mixed ? ctx->gpform : nullptr,
+                                   reinterpret_cast<const int2*>(ctx->kmtiles.get()));
+                return 0;
+            });
+            if (rc) return rc;
+        }
+        if (ctx->n_diff > 0)
+            hipLaunchKernelGGL(k_kmat<KIND>, dim3((unsigned)nb, (unsigned)nb, (unsigned)ctx->P), dim3(256),
+                               2 * 64 * (ctx->dpad + 1) * sizeof(double), ctx->stream, ctx->Xsc, ctx->amp, ctx->noise,
+                               ctx->alpha_reg, ctx->pnoise, ctx->K, ctx->sel(), ctx->Np, (int)ctx->dpad,
+                               mixed ? ctx->gpform : nullptr);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_kmat");
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -652,28 +621,6 @@ __global__ __launch_bounds__(256) void k_grad_final(const double* __restrict__ g
     }
 }
 
-template <int KIND>
-static int launch_grad_kind(gpb_ctx* ctx, int ntiles, double* gfinal) {
-    dim3 grid((unsigned)ntiles, (unsigned)ctx->P);
-#define GPB_GRAD(DP)                                                                              \
-    hipLaunchKernelGGL((k_lml_grad<KIND, DP>), grid, dim3(256), (128 * (DP + 1) + 4 * (DP + 2)) * sizeof(double), \
-                       ctx->stream, ctx->Xsc, ctx->amp, ctx->noise, ctx->alpha, ctx->T, ctx->gpart, ctx->sel(),   \
-                       ctx->Np, (int)ctx->d, ntiles)
-    switch (ctx->dpad) {
-        case 8: GPB_GRAD(8); break;
-        case 16: GPB_GRAD(16); break;
-        case 20: GPB_GRAD(20); break;
-        case 24: GPB_GRAD(24); break;
-        case 32: GPB_GRAD(32); break;
-        case 48: GPB_GRAD(48); break;
-        default: GPB_GRAD(64); break;
-    }
-#undef GPB_GRAD
-    hipLaunchKernelGGL(k_grad_final, dim3((unsigned)ctx->P, (unsigned)((ctx->d + 2 + 31) / 32)), dim3(256), 0, ctx->stream,
-                       ctx->gpart, gfinal, ntiles, (int)ctx->d);
-    return 0;
-}
-
 int launch_lml_grad(gpb_ctx* ctx, double* grad_dev) {
     const int64_t nt128 = (ctx->Np + 127) / 128;
     // 64-wide tiles while 128-wide ones would leave the chip underfilled (the rule of launch_trtri; option key 50 forces one)
@@ -690,9 +637,18 @@ int launch_lml_grad(gpb_ctx* ctx, double* grad_dev) {
     const int ntiles = (int)(nt64 * (nt64 + 1) / 2);
     const int64_t need = (int64_t)ctx->P * ntiles * (ctx->d + 2);
     if (int rc = ctx_grow(ctx, ctx->gpart, need)) return rc;
-    if (ctx->kind == GPB_KERNEL_RBF) launch_grad_kind<GPB_KERNEL_RBF>(ctx, ntiles, grad_dev);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) launch_grad_kind<GPB_KERNEL_MATERN15>(ctx, ntiles, grad_dev);
-    else launch_grad_kind<GPB_KERNEL_MATERN25>(ctx, ntiles, grad_dev);
+    const int rc = with_kind(ctx->kind, [&](auto K) {
+        return with_dpad(ctx->dpad, [&](auto D) {
+            constexpr int DP = decltype(D)::value;
+            hipLaunchKernelGGL((k_lml_grad<decltype(K)::value, DP>), dim3((unsigned)ntiles, (unsigned)ctx->P), dim3(256),
+                               (128 * (DP + 1) + 4 * (DP + 2)) * sizeof(double), ctx->stream, ctx->Xsc, ctx->amp, ctx->noise,
+                               ctx->alpha, ctx->T, ctx->gpart, ctx->sel(), ctx->Np, (int)ctx->d, ntiles);
+            return 0;
+        });
+    });
+    if (rc) return dispatched(ctx, rc, "k_lml_grad");
+    hipLaunchKernelGGL(k_grad_final, dim3((unsigned)ctx->P, (unsigned)((ctx->d + 2 + 31) / 32)), dim3(256), 0, ctx->stream,
+                       ctx->gpart, grad_dev, ntiles, (int)ctx->d);
     GPB_HIP(hipGetLastError());
     return 0;
 }

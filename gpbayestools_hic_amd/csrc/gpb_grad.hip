@@ -437,14 +437,13 @@ int gp_grad_rows(gpb_ctx* ctx, const double* Xg, int64_t W, bool need_var, bool 
     }
     const dim3 grid((unsigned)W, (unsigned)ctx->P);
     const int64_t pad = pad_front(Np, ctx->N);
-#define GPB_GG(KIND)                                                                                                         \
-    hipLaunchKernelGGL(k_gp_grad<KIND>, grid, dim3(256), 0, ctx->stream, Xg, ctx->d, ctx->X, (int)ctx->dpad, ctx->ls, ctx->amp, \
-                       ctx->alpha, need_var ? bt : nullptr, Np, pad, ctx->N, (int)ctx->d, (int)ctx->P, Wld, dmean,           \
-                       need_var ? dvar : nullptr)
-    if (ctx->kind == GPB_KERNEL_RBF) GPB_GG(GPB_KERNEL_RBF);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) GPB_GG(GPB_KERNEL_MATERN15);
-    else GPB_GG(GPB_KERNEL_MATERN25);
-#undef GPB_GG
+    rc = with_kind(ctx->kind, [&](auto K) {
+        hipLaunchKernelGGL(k_gp_grad<decltype(K)::value>, grid, dim3(256), 0, ctx->stream, Xg, ctx->d, ctx->X, (int)ctx->dpad, ctx->ls,
+                           ctx->amp, ctx->alpha, need_var ? bt : nullptr, Np, pad, ctx->N, (int)ctx->d, (int)ctx->P, Wld, dmean,
+                           need_var ? dvar : nullptr);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_gp_grad");
     GPB_HIP(hipGetLastError());
     return 0;
 }

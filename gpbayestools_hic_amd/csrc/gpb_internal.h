@@ -9,6 +9,7 @@
 #include "../../include/gpbayes.h"
 #include "../../include/gpbayes_debug.h"
 #include "dev_buf.h"
+#include "dispatch.h"
 #include "ws_layout.h"
 
 namespace gpb {
@@ -16,7 +17,6 @@ namespace gpb {
 constexpr int NB = 64;          // Cholesky diagonal block / padding granule of N
 constexpr int WPAD = 128;       // walker-batch padding granule (GEMM tile width)
 constexpr int KX_CHUNK = 64;    // design points per kcross workgroup (mean partial granule)
-constexpr int MAX_D = 64;
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 __host__ __device__ inline int64_t imin64(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -41,16 +41,16 @@ struct GpSel {
 // fall into the lightest row block — and the remainder (< 16 rows) behind.
 __host__ __device__ __forceinline__ int64_t pad_front(int64_t Np, int64_t N) { return ((Np - N) / 16) * 16; }
 
-// c k(r) / c as a function of the squared scaled distance, plain libm form (the joint covariance and the sequential design)
+// k(r) / c as a function of the squared scaled distance, plain libm form (fast_math.h has the fast forms of k_kmat_mfma and k_kcross)
 template <int KIND>
-__device__ __forceinline__ double shape_fn_c(double r2) {
+__device__ __forceinline__ double shape_fn(double r2) {
     if (KIND == GPB_KERNEL_RBF) {
-        return exp(-0.5 * r2);
+        return exp(-0.5 * r2);                                   // sk:kernels.py:1557
     } else if (KIND == GPB_KERNEL_MATERN15) {
-        const double t = sqrt(r2) * 1.7320508075688772;
+        const double t = sqrt(r2) * 1.7320508075688772;          // sk:kernels.py:1721-1723
         return (1.0 + t) * exp(-t);
     } else {
-        const double t = sqrt(r2) * 2.23606797749979;
+        const double t = sqrt(r2) * 2.23606797749979;            // sk:kernels.py:1724-1726
         return (1.0 + t + t * t / 3.0) * exp(-t);
     }
 }
@@ -273,6 +273,13 @@ struct gpb_ctx {
     } while (0)
 
 namespace gpb {
+// The result of a with_int / with_dpad / with_kind at a launch site (dispatch.h).  NO_CASE: the context holds a value that
+// `what` has no instantiation for, which the entry checks rule out: a list in this library is incomplete.
+inline int dispatched(gpb_ctx* ctx, int rc, const char* what) {
+    if (rc == NO_CASE) GPB_FAIL(GPB_E_STATE, std::string("gpb: internal: no instantiation of ") + what + " for this context");
+    return rc;
+}
+
 // The device buffers of a context: DevBuf members (dev_buf.h), allocated through these two and given back by `delete ctx`
 // once gpb_ctx_destroy has idled the streams.  Before a held buffer goes back to the cache, the context's stream and its
 // look-ahead stream are synchronised: nothing enqueued still uses it.  (Nothing is synchronised for an empty buffer or one

@@ -692,17 +692,15 @@ static bool lowrank_applies(const gpb_ctx* ctx) {
 static int launch_loglike_lowrank(gpb_ctx* ctx, int64_t W, double* ll_dev, bool accumulate, const BoxArgs& box,
                                   const PartArgs& part) {
     const dim3 grid((unsigned)((W + 63) / 64));
-#define GPB_LR(PPV)                                                                                              \
-    hipLaunchKernelGGL(k_loglike_lowrank<PPV>, grid, dim3(lr_threads<PPV>()), 0, ctx->stream, ctx->mean_pc, ctx->var_pc, ctx->Wld, \
-                       W, (int)ctx->P, ctx->lr_R, ctx->lr_v0, ctx->lr_cperp, ctx->lr_logdet0, ll_dev,              \
-                       accumulate ? 1 : 0, ctx->notpd, box, part)
-    switch (ctx->P) {                        // exact sizes: the work per walker grows with PP^3
-        case 1: GPB_LR(1); break;   case 2: GPB_LR(2); break;   case 3: GPB_LR(3); break;   case 4: GPB_LR(4); break;
-        case 5: GPB_LR(5); break;   case 6: GPB_LR(6); break;   case 7: GPB_LR(7); break;   case 8: GPB_LR(8); break;
-        case 9: GPB_LR(9); break;   case 10: GPB_LR(10); break; case 11: GPB_LR(11); break; case 12: GPB_LR(12); break;
-        case 13: GPB_LR(13); break; case 14: GPB_LR(14); break; case 15: GPB_LR(15); break; default: GPB_LR(16); break;
-    }
-#undef GPB_LR
+    // exact sizes: the work per walker grows with PP^3
+    const int rc = with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(ctx->P, [&](auto N) {
+        constexpr int PP = decltype(N)::value;
+        hipLaunchKernelGGL(k_loglike_lowrank<PP>, grid, dim3(lr_threads<PP>()), 0, ctx->stream, ctx->mean_pc, ctx->var_pc, ctx->Wld,
+                           W, (int)ctx->P, ctx->lr_R, ctx->lr_v0, ctx->lr_cperp, ctx->lr_logdet0, ll_dev, accumulate ? 1 : 0,
+                           ctx->notpd, box, part);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_loglike_lowrank");
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -844,10 +842,13 @@ int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double*
     // option key 49 = 0: the one-launch walk — the A/B, and the bit-identity test)
     double* blocks = (ctx->lr_split && ctx->lr_blocks.cap >= (int64_t)E * ctx->Wld) ? ctx->lr_blocks : nullptr;
     const dim3 grid((unsigned)((W + 63) / 64), blocks ? (unsigned)E : 1u);
-#define GPB_LRM(PPV)                                                                                             \
-    hipLaunchKernelGGL(k_loglike_lowrank_multi<PPV>, grid, dim3(lr_threads<PPV>()), 0, ctx->stream, tab, ctx->Wld, W, ll_dev, cmpv, inside_const, blocks)
-    if (pmax <= 4) GPB_LRM(4); else if (pmax <= 8) GPB_LRM(8); else if (pmax <= 12) GPB_LRM(12); else GPB_LRM(16);
-#undef GPB_LRM
+    const int rc = with_int<4, 8, 12, 16>(round_up(pmax, 4), [&](auto N) {
+        constexpr int PP = decltype(N)::value;
+        hipLaunchKernelGGL(k_loglike_lowrank_multi<PP>, grid, dim3(lr_threads<PP>()), 0, ctx->stream, tab, ctx->Wld, W, ll_dev, cmpv,
+                           inside_const, blocks);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_loglike_lowrank_multi");
     if (blocks)
         hipLaunchKernelGGL(k_lowrank_sum, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, ctx->stream, blocks, E, ctx->Wld, W,
                            ll_dev, cmpv, inside_const);

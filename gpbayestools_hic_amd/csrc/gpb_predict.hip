@@ -24,19 +24,6 @@
 
 namespace gpb {
 
-template <int KIND>
-__device__ __forceinline__ double shape_fn_p(double r2) {
-    if (KIND == GPB_KERNEL_RBF) {
-        return exp(-0.5 * r2);
-    } else if (KIND == GPB_KERNEL_MATERN15) {
-        const double t = sqrt(r2) * 1.7320508075688772;
-        return (1.0 + t) * exp(-t);
-    } else {
-        const double t = sqrt(r2) * 2.23606797749979;
-        return (1.0 + t + t * t / 3.0) * exp(-t);
-    }
-}
-
 // grid (chunk groups, P, walker tiles), 256 threads: lane = walker, the 4 waves stride the 64-point chunk's
 // design points; the design row is wave-uniform (scalar loads), the walker row lives in VGPRs.
 // DOT: r^2 = |a|^2 + |b|^2 - 2 a.b with a = design row / l - mu / l (Xc, its norms in dnorm) and b = walker / l -
@@ -656,55 +643,33 @@ static int kcross_geometry(gpb_ctx* ctx, int64_t Wuse, int64_t G, const int* nro
     return 0;
 }
 
-template <int KIND>
-static int launch_kcross_kind(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, int planes) {
+// a context's own launches: one instantiation per distance form; each launch computes the GPs of its form (ctx->gpform, chosen
+// from theta: choose_forms) and is left out when no GP has it — the usual case is the Gram launch alone, with no form table to read
+static int launch_kcross_own(gpb_ctx* ctx, const double* Xs_dev, int64_t W, int64_t Wuse, const int* nrows_dev, int planes) {
     KxGeo geo;
     if (const int rc = kcross_geometry(ctx, Wuse, ctx->P, nrows_dev, geo)) return rc;
-    const int wpl = geo.wpl, cpw = geo.cpw;
-    const dim3 grid = geo.grid;
-    // two instantiations, one per distance form; each launch computes the GPs of its form (ctx->gpform, chosen from theta:
-    // choose_forms) and is left out when no GP has it — the usual case is the Gram launch alone, with no form table to read
     const int* form = (ctx->n_diff > 0 && ctx->n_diff < ctx->P) ? ctx->gpform : nullptr;
-    const bool gram = ctx->n_diff < ctx->P, diff = ctx->n_diff > 0;
     int8_t* const slB = planes ? ctx->slB : nullptr;
     const double* const slcs = planes ? sliced_colscale(ctx) : nullptr;
-#define GPB_KX_LAUNCH(DP, DOT_, WPL_, XD)                                                                         \
-    do {                                                                                                          \
-        if (planes == 7)                                                                                          \
-            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_, 7>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
-                               XD, ctx->ls, ctx->amp, ctx->alpha, ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld,       \
-                               (int)ctx->P, ctx->dnorm, ctx->muS, cpw, nrows_dev, form, slB, slcs);               \
-        else if (planes)                                                                                          \
-            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_, 6>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
-                               XD, ctx->ls, ctx->amp, ctx->alpha, ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld,       \
-                               (int)ctx->P, ctx->dnorm, ctx->muS, cpw, nrows_dev, form, slB, slcs);               \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_kcross<KIND, DP, DOT_, WPL_>), grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, \
-                               XD, ctx->ls, ctx->amp, ctx->alpha, ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld,       \
-                               (int)ctx->P, ctx->dnorm, ctx->muS, cpw, nrows_dev, form, nullptr, nullptr);        \
-    } while (0)
-#define GPB_KX(DP)                                                                                               \
-    do {                                                                                                         \
-        if (wpl == 2) {                                                                                          \
-            if (gram) GPB_KX_LAUNCH(DP, true, (DP <= 32 ? 2 : 1), ctx->Xc);                                      \
-            if (diff) GPB_KX_LAUNCH(DP, false, (DP <= 32 ? 2 : 1), ctx->Xsc);                                    \
-        } else {                                                                                                 \
-            if (gram) GPB_KX_LAUNCH(DP, true, 1, ctx->Xc);                                                       \
-            if (diff) GPB_KX_LAUNCH(DP, false, 1, ctx->Xsc);                                                     \
-        }                                                                                                        \
-    } while (0)
-    switch (ctx->dpad) {
-        case 8: GPB_KX(8); break;
-        case 16: GPB_KX(16); break;
-        case 20: GPB_KX(20); break;
-        case 24: GPB_KX(24); break;
-        case 32: GPB_KX(32); break;
-        case 48: GPB_KX(48); break;
-        default: GPB_KX(64); break;
-    }
-#undef GPB_KX
-#undef GPB_KX_LAUNCH
-    return 0;
+    const auto launch = [&](auto kernel, const double* Xd) {
+        hipLaunchKernelGGL(kernel, geo.grid, dim3(256), 0, ctx->stream, Xs_dev, W, (int)ctx->d, Xd, ctx->ls, ctx->amp, ctx->alpha,
+                           ctx->KsT, ctx->mpart, ctx->N, ctx->Np, ctx->Wld, (int)ctx->P, ctx->dnorm, ctx->muS, geo.cpw, nrows_dev, form,
+                           slB, slcs);
+    };
+    const int rc = with_kind(ctx->kind, [&](auto K) {
+        return with_dpad(ctx->dpad, [&](auto D) {
+            return with_int<1, 2>(geo.wpl, [&](auto L) {
+                return with_int<0, 6, 7>(planes, [&](auto S) {
+                    constexpr int KIND = decltype(K)::value, DP = decltype(D)::value, SLICE = decltype(S)::value;
+                    constexpr int WPL = DP <= 32 ? decltype(L)::value : 1;      // (no two-walker kernels above 32 inputs)
+                    if (ctx->n_diff < ctx->P) launch(k_kcross<KIND, DP, true, WPL, SLICE>, ctx->Xc);
+                    if (ctx->n_diff > 0) launch(k_kcross<KIND, DP, false, WPL, SLICE>, ctx->Xsc);
+                    return 0;
+                });
+            });
+        });
+    });
+    return dispatched(ctx, rc, "k_kcross");
 }
 
 // K*^T and the mean partials of a batch: Xs_dev [W][d] on the device.  Sets the leading dimension of the batch's workspaces.
@@ -727,11 +692,7 @@ int launch_kcross(gpb_ctx* ctx, const double* Xs_dev, int64_t W, const int* nrow
     // 32 KB apart and k_predict_static ran 13 % slower (117 -> 133 us), k_kcross 24 % (20 -> 25 us)
     ctx->Wld = Wuse;
     ctx->last_W = W;
-    int rc;
-    if (ctx->kind == GPB_KERNEL_RBF) rc = launch_kcross_kind<GPB_KERNEL_RBF>(ctx, Xs_dev, W, Wuse, nrows_dev, planes);
-    else if (ctx->kind == GPB_KERNEL_MATERN15) rc = launch_kcross_kind<GPB_KERNEL_MATERN15>(ctx, Xs_dev, W, Wuse, nrows_dev, planes);
-    else rc = launch_kcross_kind<GPB_KERNEL_MATERN25>(ctx, Xs_dev, W, Wuse, nrows_dev, planes);
-    if (rc) return rc;
+    if (const int rc = launch_kcross_own(ctx, Xs_dev, W, Wuse, nrows_dev, planes)) return rc;
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -786,39 +747,17 @@ int launch_kcross_group(gpb_ctx* const* ctxs, const double* const* Xs, int E, in
     tab.E = E;
     KxGeo geo;
     if (const int rc = kcross_geometry(ctx, Wuse, G, nrows_dev, geo)) return rc;
-    const int wpl = geo.wpl, cpw = geo.cpw;
-    const dim3 grid = geo.grid;
-#define GPB_KXM(DP)                                                                                              \
-    do {                                                                                                         \
-        if (wpl == 2 && planes == 7)                                                                             \
-            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1), 7>), grid, dim3(256), 0, ctx->stream, tab, W, \
-                               (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
-        else if (wpl == 2 && planes)                                                                             \
-            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1), 6>), grid, dim3(256), 0, ctx->stream, tab, W, \
-                               (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
-        else if (wpl == 2)                                                                                       \
-            hipLaunchKernelGGL((k_kcross_multi<DP, (DP <= 32 ? 2 : 1)>), grid, dim3(256), 0, ctx->stream, tab, W, \
-                               (int)ctx->d, ctx->Np, Wuse, cpw, nrows_dev);                                       \
-        else if (planes == 7)                                                                                    \
-            hipLaunchKernelGGL((k_kcross_multi<DP, 1, 7>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d, \
-                               ctx->Np, Wuse, cpw, nrows_dev);                                                   \
-        else if (planes)                                                                                         \
-            hipLaunchKernelGGL((k_kcross_multi<DP, 1, 6>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d, \
-                               ctx->Np, Wuse, cpw, nrows_dev);                                                   \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_kcross_multi<DP, 1>), grid, dim3(256), 0, ctx->stream, tab, W, (int)ctx->d,    \
-                               ctx->Np, Wuse, cpw, nrows_dev);                                                   \
-    } while (0)
-    switch (ctx->dpad) {
-        case 8: GPB_KXM(8); break;
-        case 16: GPB_KXM(16); break;
-        case 20: GPB_KXM(20); break;
-        case 24: GPB_KXM(24); break;
-        case 32: GPB_KXM(32); break;
-        case 48: GPB_KXM(48); break;
-        default: GPB_KXM(64); break;
-    }
-#undef GPB_KXM
+    const int rc = with_dpad(ctx->dpad, [&](auto D) {
+        return with_int<1, 2>(geo.wpl, [&](auto L) {
+            return with_int<0, 6, 7>(planes, [&](auto S) {
+                constexpr int DP = decltype(D)::value, WPL = DP <= 32 ? decltype(L)::value : 1;
+                hipLaunchKernelGGL((k_kcross_multi<DP, WPL, decltype(S)::value>), geo.grid, dim3(256), 0, ctx->stream, tab, W,
+                                   (int)ctx->d, ctx->Np, Wuse, geo.cpw, nrows_dev);
+                return 0;
+            });
+        });
+    });
+    if (rc) return dispatched(ctx, rc, "k_kcross_multi");
     GPB_HIP(hipGetLastError());
     return 0;
 }
@@ -882,7 +821,7 @@ static std::pair<int, int> predict_tile_shape(const gpb_ctx* ctx, int64_t G, int
 // workgroup per tile in weight order — beyond co-residency the hardware dispatcher hands the next workgroup to whichever CU frees a
 // slot, which balances as well as ticket queues do (7-12 % faster at 384-768 walkers).
 template <class Src>
-static void predict_launch(gpb_ctx* ctx, const Src& src, int G, int64_t W, int tri_arg, const int* nrows_dev) {
+static int predict_launch(gpb_ctx* ctx, const Src& src, int G, int64_t W, int tri_arg, const int* nrows_dev) {
     const auto [T, TN] = predict_tile_shape(ctx, G, W, nrows_dev);
     const int64_t Wuse = round_up(W, WPAD);
     const int nI = (T == 128) ? (int)((ctx->Np + 127) / 128) : (int)(ctx->Np / 64), nW = (int)(Wuse / TN);
@@ -894,17 +833,16 @@ static void predict_launch(gpb_ctx* ctx, const Src& src, int G, int64_t W, int t
         const unsigned slots = 2u * (unsigned)ctx->num_cu;
         hipLaunchKernelGGL((k_predict<Src, 128, 4, 128, 16, true>), dim3(nblocks < slots ? nblocks : slots), dim3(256), 0, ctx->stream,
                            src, ctx->Np, ctx->Wld, G, nI, nW, xcd, ctx->tile_counter, nblocks, ctx->tile_trace, tri_arg, nrows_dev);
-        return;
+        return 0;
     }
     const int order = ctx->resident_order ? ctx->resident_order : 2;
-#define GPB_PRED(NN)                                                                                                       \
-    hipLaunchKernelGGL((k_predict_static<Src, 64, 4, NN, 16>), dim3(nblocks), dim3(256), 0, ctx->stream, src, ctx->Np, ctx->Wld, \
-                       G, nI, nW, xcd, nblocks, order, (unsigned)(ctx->num_cu / 8), ctx->tile_priority ? nI : 0, ctx->tile_trace, \
-                       tri_arg, nrows_dev)
-    if (TN == 32) GPB_PRED(32);
-    else if (TN == 128) GPB_PRED(128);
-    else GPB_PRED(64);
-#undef GPB_PRED
+    const int rc = with_int<32, 64, 128>(TN, [&](auto NN) {
+        hipLaunchKernelGGL((k_predict_static<Src, 64, 4, decltype(NN)::value, 16>), dim3(nblocks), dim3(256), 0, ctx->stream, src,
+                           ctx->Np, ctx->Wld, G, nI, nW, xcd, nblocks, order, (unsigned)(ctx->num_cu / 8),
+                           ctx->tile_priority ? nI : 0, ctx->tile_trace, tri_arg, nrows_dev);
+        return 0;
+    });
+    return dispatched(ctx, rc, "k_predict_static");
 }
 
 // V = L^-1 K*^T and its partials for E contexts of one shape whose batches are all fp64 or all digit planes of one depth, in one
@@ -927,15 +865,13 @@ static int vsq_launch(gpb_ctx* const* ctxs, int E, int64_t W, const int* nrows_d
         return E > 1 ? launch_vsq_sliced_multi(ctxs, E, W, nrows_dev, (int)kskip) : launch_vsq_sliced(ctx, W, nrows_dev, (int)kskip);
     const int tri_arg = (ctx->tri_skip ? 1 : 0) | ((int)kskip << 8);
     if (E == 1) {
-        predict_launch(ctx, PredOne{ctx->Linv, ctx->KsT, ctx->spart}, (int)G, W, tri_arg, nrows_dev);
-        return 0;
+        return predict_launch(ctx, PredOne{ctx->Linv, ctx->KsT, ctx->spart}, (int)G, W, tri_arg, nrows_dev);
     }
     PredTable tab;
     int g = 0;
     for (int e = 0; e < E; ++e)
         for (int pp = 0; pp < (int)ctxs[e]->P; ++pp, ++g) tab.gp[g] = PredGP{ctxs[e]->Linv, ctxs[e]->KsT, ctxs[e]->spart, (int)ctxs[e]->P, pp};
-    predict_launch(ctx, tab, (int)G, W, tri_arg, nrows_dev);
-    return 0;
+    return predict_launch(ctx, tab, (int)G, W, tri_arg, nrows_dev);
 }
 
 // live HIP-event timing of the dominant kernel (bench.py) into ctx: prof_begin before a launch over `gps` GPs, prof_end after it
@@ -1037,10 +973,13 @@ int launch_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, const double
                      int b_trans) {
     const int mode = b_trans & 3, T = (b_trans & 4) ? 64 : 128;
     dim3 grid((unsigned)((N + T - 1) / T), (unsigned)((M + T - 1) / T));
-#define GPB_TG(TT, MM) hipLaunchKernelGGL((k_test_gemm<TT, MM>), grid, dim3(256), 0, ctx->stream, A, B, C, M, N, K)
-    if (T == 128) { if (mode == 0) GPB_TG(128, 0); else if (mode == 1) GPB_TG(128, 1); else GPB_TG(128, 2); }
-    else          { if (mode == 0) GPB_TG(64, 0);  else if (mode == 1) GPB_TG(64, 1);  else GPB_TG(64, 2); }
-#undef GPB_TG
+    const int rc = with_int<64, 128>(T, [&](auto TT) {
+        return with_int<0, 1, 2>(mode, [&](auto MM) {
+            hipLaunchKernelGGL((k_test_gemm<decltype(TT)::value, decltype(MM)::value>), grid, dim3(256), 0, ctx->stream, A, B, C, M, N, K);
+            return 0;
+        });
+    });
+    if (rc) return dispatched(ctx, rc, "k_test_gemm");
     GPB_HIP(hipGetLastError());
     return 0;
 }

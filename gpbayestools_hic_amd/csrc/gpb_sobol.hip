@@ -382,14 +382,8 @@ int launch_sobol(gpb_ctx* ctx, double* e_dev, double* H_dev) {
     if (rc) return rc;
     const SobolWs ws = sobol_pieces(ctx);
     double* part = ws.part;
-    switch (sobol_window(ctx->dpad)) {
-        case 8: rc = launch_pairs_t<8>(ctx, part); break;
-        case 16: rc = launch_pairs_t<16>(ctx, part); break;
-        case 20: rc = launch_pairs_t<20>(ctx, part); break;
-        case 24: rc = launch_pairs_t<24>(ctx, part); break;
-        default: rc = launch_pairs_t<32>(ctx, part); break;
-    }
-    if (rc) return rc;
+    rc = with_int<8, 16, 20, 24, 32>(sobol_window(ctx->dpad), [&](auto NJ) { return launch_pairs_t<decltype(NJ)::value>(ctx, part); });
+    if (rc) return dispatched(ctx, rc, "k_sobol_pairs");
     const int64_t P = ctx->P, nB = ctx->Np / 64;
     const double* epart = ws.epart;
     hipLaunchKernelGGL(k_sobol_sum, dim3((unsigned)(P * (P + 1) / 2)), dim3(256), 0, ctx->stream, part, epart, ctx->amp, (int)ctx->d,

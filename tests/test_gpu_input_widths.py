@@ -1,5 +1,5 @@
 """GPU tier: every padded input width the distance kernels are instantiated or sized on — pick_dpad's 8, 16, 20, 24, 32, 48, 64
-(csrc/gpb_api.hip) — against the oracle, each with d == width (no padding column) and d == previous width + 1 (the most), for the
+(csrc/dispatch.h) — against the oracle, each with d == width (no padding column) and d == previous width + 1 (the most), for the
 three kernel families, both distance forms in one engine, one and two walkers per lane, and the fp64, seven-plane and six-plane
 arithmetic of K*.  The inputs are tests/width_cases.py; tests/test_width_cases.py shows on the oracle alone that they see a dropped
 last input column at more than 1e6 x every bar used here.

@@ -1,8 +1,8 @@
 """CPU tier: the inputs of tests/test_gpu_input_widths.py (tests/width_cases.py) held to the conditions under which that file's
 bars say something — on the oracle alone, no device.
 
-  * the width list is the one pick_dpad (csrc/gpb_api.hip) chooses from, read from the source text: a width added there fails
-    here until it gets cases;
+  * the width list is the one pick_dpad and every launch's with_dpad take their widths from (csrc/dispatch.h), read from the
+    source text: a width added there fails here until it gets cases;
   * every GP is in the distance form the cases intend, by the engine's rule S = sum (ptp / l)^2 > 1024 (gpb_internal.h
     gram_limit; restated as tests/test_gpu_edges.py does);
   * the inputs can see a wrong kernel: every query has max_i K*(x, x_i) > 0.05 for each GP, the oracle's variance is >= 1e-3 c,
@@ -28,9 +28,9 @@ SEEN = 1e6
 
 
 def test_the_width_list_is_pick_dpads():
-    src = open(os.path.join(REPO, "gpbayestools_hic_amd", "csrc", "gpb_api.hip")).read()
-    m = re.search(r"int\s+pick_dpad\s*\([^)]*\)\s*\{.*?opts\[\]\s*=\s*\{([^}]*)\}", src, re.S)
-    assert m, "pick_dpad's list of widths not found in gpb_api.hip"
+    src = open(os.path.join(REPO, "gpbayestools_hic_amd", "csrc", "dispatch.h")).read()
+    m = re.search(r"using\s+Widths\s*=\s*std::integer_sequence\s*<\s*int\s*,([^>]*)>", src)
+    assert m, "the list of widths (Widths) not found in dispatch.h"
     assert tuple(int(v) for v in m.group(1).split(",")) == WC.WIDTHS
 
 

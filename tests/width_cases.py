@@ -1,7 +1,7 @@
 """Inputs for the tests of the padded input widths (a helper module, not a test file; host only: numpy and synth).
 
 Every kernel that forms a scaled distance is instantiated or sized on the padded input width dpad that pick_dpad
-(csrc/gpb_api.hip) takes from WIDTHS.  DS holds two input counts per width: d == width (no padding column; k_lml_grad's noise
+(csrc/dispatch.h) takes from WIDTHS.  DS holds two input counts per width: d == width (no padding column; k_lml_grad's noise
 slot tid == DPAD + 1 is then d + 1) and d == previous width + 1 (the most padding columns).
 
 make_case(d, kind, seed) is one emulator of three GPs over N = 130 design points (Np = 192: 48 padding rows in front, 14 behind)
