@@ -87,11 +87,12 @@ class SMCSampler:
         cnt = raw.view(np.int64)
         out = dict(beta=float(raw[0]), logz=float(raw[1]), log_sigma=float(raw[2]), ess=float(raw[3]), dlogz=float(raw[4]),
                    naccept=int(cnt[10]), nan_moves=int(cnt[11]), nan_weights=int(cnt[12]), flags=int(cnt[13]))
+        # the cause first: without a weight every position resamples the last particle, and that ensemble's pivot flag follows
+        if out["flags"] & FLAG_NO_WEIGHT:
+            raise RuntimeError("SMC: no particle has a finite log-likelihood at stage %d" % (self.stage - 1))
         if out["flags"] & FLAG_PIVOT:
             raise RuntimeError("SMC: the particle covariance is not positive definite at stage %d (a degenerate ensemble: "
                                "non-positive pivot in its Cholesky factorisation)" % (self.stage - 1))
-        if out["flags"] & FLAG_NO_WEIGHT:
-            raise RuntimeError("SMC: no particle has a finite log-likelihood at stage %d" % (self.stage - 1))
         return out
 
     def state(self):

@@ -1,6 +1,7 @@
 """float64 numpy restatement of the tempered SMC sampler of csrc/gpb_smc.hip (Chain.run_SMC): reweighting with the bisection
 for the next beta, systematic resampling, the preconditioner, one move step and the driver, with every random number an
-input, plus an independent restatement of the device's Philox draws (oracle.stretch_oracle).
+input, plus an independent restatement of the device's Philox draws (oracle.stretch_oracle), a model of the reweighting
+kernel's chunked scan (device_scan) and the injected-weights recipe both test tiers use (injected_logl).
 
 The likelihood is any callable X [n, d] -> logl [n] that returns OUTSIDE (or less) for rows outside the prior box.  Draws come
 either from numpy (`NumpyDraws`) or from the device's counters (`PhiloxDraws`, what gpb_test_smc_draws reports)."""
@@ -13,6 +14,7 @@ BISECT = 60
 TARGET_ACC = 0.234
 OUTSIDE = -1e300
 POS_MAX = 1.0 - 2.0 ** -53
+RW_THREADS = 1024                # threads of k_smc_reweight's one workgroup
 
 
 def _key(seed):
@@ -94,13 +96,57 @@ def reweight(logl, beta_prev, ess_fraction):
     return dict(beta=beta, dlogz=dlogz, w=w, ess=(s1 * s1) / np.sum(w * w), nan_weights=int(np.sum(np.isnan(logl))))
 
 
-def resample(w, u):
-    """systematic resampling -> (ancestors [N], cum [N] inclusive normalised, positions [N])"""
+def device_scan(w, threads=RW_THREADS):
+    """the inclusive normalised scan as k_smc_reweight forms it: thread t of `threads` owns the contiguous chunk
+    [t C, (t + 1) C) with C = ceil(N / threads) (the last owner's chunk may be short, the threads behind it own nothing) and
+    sums it in index order; the chunks' bases are one sequential pass over the chunk totals; every entry is base + local sum,
+    divided by the pass's own total"""
     N = len(w)
-    cum = np.cumsum(w)
-    cum = cum / cum[-1]
+    C = -(-N // threads)
+    padded = np.zeros(threads * C)
+    padded[:N] = w                                             # (an entry nobody owns adds an exact zero)
+    local = np.cumsum(padded.reshape(threads, C), axis=1)
+    ends = np.cumsum(local[:, -1])
+    base = np.concatenate(([0.0], ends[:-1]))
+    return ((base[:, None] + local) / ends[-1]).reshape(-1)[:N]
+
+
+def resample(w, u, scan=None):
+    """systematic resampling -> (ancestors [N], cum [N] inclusive normalised, positions [N]); scan: the normalised scan
+    of the weights (np.cumsum divided by its last entry when not given, device_scan for the kernel's)"""
+    N = len(w)
+    if scan is None:
+        cum = np.cumsum(w)
+        cum = cum / cum[-1]
+    else:
+        cum = scan(w)
     pos = np.minimum((u + np.arange(N, dtype=np.float64)) / float(N), POS_MAX)
     return np.searchsorted(cum, pos, side="right"), cum, pos
+
+
+def knife_edges(anc, cum, pos, tol=1e-12):
+    """the positions within tol of the scan entry that decides their ancestor (cum[anc] above, cum[anc - 1] below): there a
+    scan that differs in its last bits may pick the neighbour"""
+    N = len(cum)
+    return np.minimum(np.abs(cum[np.minimum(anc, N - 1)] - pos),
+                      np.abs(np.where(anc > 0, cum[np.maximum(anc - 1, 0)], -1.0) - pos)) < tol
+
+
+INJECTED_SIZES = (1027, 2051, 4096, 16389)
+
+
+def injected_logl(N, threads=RW_THREADS):
+    """log-likelihoods with runs of zero weights and NaNs where the reweighting's chunked scan could trip:
+    4 standard_normal - 30, then -inf at the front, -1e300 (exp underflows to 0) at the end, five NaNs across the boundary
+    between chunks 4 and 5 (C = ceil(N / threads)), one NaN in the middle and two -inf at a third: six NaN weights"""
+    C = -(-N // threads)
+    logl = 4.0 * np.random.default_rng(N).standard_normal(N) - 30.0
+    logl[0:3] = -np.inf
+    logl[N - 2:] = -1e300
+    logl[5 * C - 2:5 * C + 3] = np.nan
+    logl[N // 2] = np.nan
+    logl[N // 3:N // 3 + 2] = -np.inf
+    return logl
 
 
 def precondition(x):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import ptlmc_reference as R
+from sampler_cases import mapped_chain, mapped_log_posterior, wide_chain, wide_start
 
 pytestmark = pytest.mark.gpu
 
@@ -35,20 +36,22 @@ def _emulator(tmp, N, d, M, P, kernel="RBF", ell=1.5, seed=0):
     return chain, emu, xstar
 
 
-def _start(chain, xstar, T, seed, gradient, temps, radius=0.03):
+def _start(chain, xstar, T, seed, gradient, temps, radius=0.03, theta=None):
+    """the start state around xstar in the unit box, or from the rows theta [T, d] given"""
     rng = np.random.default_rng(seed)
-    theta = np.clip(xstar + radius * rng.standard_normal((T, chain.ndim)), 0.02, 0.98)
+    if theta is None:
+        theta = np.clip(xstar + radius * rng.standard_normal((T, chain.ndim)), 0.02, 0.98)
     if gradient:
         lp, g = chain.log_posterior(theta, return_grad=True)
         return theta, lp / temps, g / temps[:, None]
     return theta, chain.log_posterior(theta) / temps, None
 
 
-def _sampler(chain, xstar, numtemps, numchain, gradient, samptunning, nsave, seed=11, maxtemp=20.0):
+def _sampler(chain, xstar, numtemps, numchain, gradient, samptunning, nsave, seed=11, maxtemp=20.0, theta=None):
     from gpbayestools_hic_amd import ptlmc
     T = numtemps + numchain
     temps = ptlmc.ladder(numtemps, numchain, maxtemp)
-    theta, fval, dfval = _start(chain, xstar, T, seed, gradient, temps)
+    theta, fval, dfval = _start(chain, xstar, T, seed, gradient, temps, theta=theta)
     covmat0, hc = ptlmc.proposal_factor(theta)
     s = ptlmc.PTLMCSampler(chain, temps, hc, covmat0, numtemps, numchain, samptunning, nsave,
                            ptlmc.TARACC_GRAD if gradient else ptlmc.TARACC_PLAIN, seed, gradient)
@@ -61,8 +64,36 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300))) if a.size else 0.0
 
 
-def _step_by_step(chain, s, temps, hc, covmat0, nsteps):
-    """nsteps single-step calls, each checked against the restatement from the device's state before it"""
+def _rel_inf(a, b):
+    """_rel where entries may be infinite: those are compared by equality (inf - inf must not reach _rel), the rest by _rel"""
+    a, b = np.asarray(a), np.asarray(b)
+    inf = np.isinf(b)
+    if not np.array_equal(a[inf], b[inf]) or np.any(np.isinf(a[~inf])):
+        return np.inf
+    return _rel(a[~inf], b[~inf])
+
+
+def _at_rows(lpf, rows):
+    """lpf evaluated at the rows of `rows` wherever a row of its argument agrees with one of them to 1e-12 entry by entry
+    (the bar theta itself is held to), at the argument's own row elsewhere.  The restatement's proposal and the device's
+    differ in their last bits (exp, log, cos and sin of the two sides round differently), and the chain's log-posterior and
+    gradient — the same device call on both sides, no part of the restated step — magnify that: an entry of the gradient
+    far below its row's largest has a condition number |H| |theta| / |g| of ~1e4 with respect to theta (measured at 66 rungs:
+    theta one bit apart, 1.84e-16, moved an entry of -0.0032 in a row of 0.16 by 1.5e-12 of itself).  Evaluated at the device's
+    own accepted rows, value and gradient are compared at one point and the bars test the step, not that magnification."""
+    def f(X):
+        X = np.array(X, dtype=np.float64)
+        D = np.max(np.abs(X[:, None, :] - rows[None, :, :]) / np.maximum(np.abs(X[:, None, :]), 1e-300), axis=2)
+        j = np.argmin(D, axis=1)
+        hit = D[np.arange(len(X)), j] <= 1e-12
+        X[hit] = rows[j[hit]]
+        return lpf(X)
+    return f
+
+
+def _step_by_step(chain, s, temps, hc, covmat0, nsteps, rel=_rel, each=None):
+    """nsteps single-step calls, each checked against the restatement from the device's state before it.  rel: the comparison
+    of theta / fval / dfval (_rel_inf where rungs sit outside the box); each(before, info, took): a test's own checks of a step"""
     lpf = (lambda X: chain.log_posterior(X, return_grad=True)) if s.gradient else chain.log_posterior
     temps13 = temps ** (1 / 3)
     near_ties = 0
@@ -70,27 +101,31 @@ def _step_by_step(chain, s, temps, hc, covmat0, nsteps):
         before = s.state()
         k = before["k"]
         dr = R.device_draws(s.seed, k, s.T, s.d)
-        ref, info = R.step(before, k, dr, lpf, temps, temps13, hc, covmat0, s.samptunning, s.taracc)
         acc0, swaps0 = s.naccept.cpu().numpy().copy(), s.nswap.cpu().numpy().copy()
         s.run(1)
         got = s.state()
         took = s.naccept.cpu().numpy() - acc0
+        with np.errstate(invalid="ignore"):                  # (-inf - -inf of a rung outside the box)
+            ref, info = R.step(before, k, dr, _at_rows(lpf, got["theta"]), temps, temps13, hc, covmat0, s.samptunning, s.taracc)
         tie = np.abs(info["delta"] - dr["logu_accept"]) < 1e-9
         assert np.array_equal(took.astype(bool)[~tie], info["accepted"][~tie]), k
+        if each is not None:
+            each(before, info, took)
         if np.any(tie & (took.astype(bool) != info["accepted"])):
             near_ties += 1                                   # a decision on a knife edge: compare from the next step on
             continue
         # the exchange took the same decisions at every pick (swaps per neighbour pair), so the order is the same
         assert np.array_equal(s.nswap.cpu().numpy() - swaps0, info["swaps"]), k
-        assert _rel(got["theta"], ref["theta"]) <= 1e-12, k
-        assert _rel(got["fval"], ref["fval"]) <= 1e-12, k
+        assert rel(got["theta"], ref["theta"]) <= 1e-12, k
+        assert rel(got["fval"], ref["fval"]) <= 1e-12, k
         if s.gradient:
-            assert _rel(got["dfval"], ref["dfval"]) <= 1e-12, k
+            assert rel(got["dfval"], ref["dfval"]) <= 1e-12, k
         assert abs(got["tau"] - ref["tau"]) <= 1e-12 * max(abs(ref["tau"]), 1.0), k
         assert abs(got["numtimes"] - ref["numtimes"]) <= 1e-12, k
         lp = chain.log_posterior(got["theta"])
         fin = np.isfinite(lp)
         assert _rel(got["fval"][fin] * temps[fin], lp[fin]) <= 1e-14, k
+        assert np.array_equal(got["fval"][~fin], lp[~fin]), k
         if k >= s.samptunning and k - s.samptunning < s.nsave:
             assert np.array_equal(s.save.cpu().numpy()[:, k - s.samptunning, :], got["theta"][s.numtemps:]), k
     return near_ties
@@ -103,7 +138,7 @@ def test_draws_match_restatement(tmp_path):
     from gpbayestools_hic_amd.engine import GPEngine
     with nat.debug_library():
         eng = GPEngine(0)
-    for (T, d, seed, k) in [(10, 4, 7, 0), (37, 9, 2 ** 40 + 3, 123), (130, 15, 12345, 2999)]:
+    for (T, d, seed, k) in [(10, 4, 7, 0), (37, 9, 2 ** 40 + 3, 123), (130, 15, 12345, 2999), (261, 127, 2 ** 35 + 9, 57)]:
         nrm = torch.empty((T, d), dtype=torch.float64, device="cuda:0")
         la = torch.empty(T, dtype=torch.float64, device="cuda:0")
         pk = torch.empty(5 * T, dtype=torch.int64, device="cuda:0")
@@ -243,3 +278,107 @@ def test_api_branch_and_refusals(tmp_path):
     chain.emuList = [Foreign()]
     with pytest.raises(NotImplementedError, match="foreign"):
         chain.samplerPTLMC(chain.log_posterior, draw, **kw)
+
+
+# ------------------------------------------------------------------ beyond one pass of the kernels' strided loops
+# k_ptl_exchange draws its 5 T picks in rounds of 256 (a second round from T = 52 on) and walks the rungs 256 at a time;
+# k_ptl_propose / k_ptl_accept give a parameter to each of 64 lanes (a second pass from d = 65 on).
+@pytest.mark.parametrize("gradient", [False, True])
+def test_default_ladder(tmp_path, gradient):
+    """run_MCMC_PTLMC's default of 50 + 16 = 66 rungs: 330 picks, a full round and one of 74; a tuning step, the boundary
+    and the saved samples"""
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s, temps, hc, cov0 = _sampler(chain, xstar, 50, 16, gradient, samptunning=6, nsave=6)
+    near = _step_by_step(chain, s, temps, hc, cov0, 12)
+    assert near <= 2
+    assert s.nswap.sum().item() > 0 and s.naccept.sum().item() > 0
+
+
+def test_notebook_ladder(tmp_path):
+    """100 + 30 = 130 rungs, the ladder the notebook runs: 650 picks, two full rounds and one of 138; and one call of ten
+    steps against ten calls of one, bit for bit"""
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s, temps, hc, cov0 = _sampler(chain, xstar, 100, 30, False, samptunning=4, nsave=4)
+    near = _step_by_step(chain, s, temps, hc, cov0, 8)
+    assert near <= 2 and s.nswap.sum().item() > 0 and s.naccept.sum().item() > 0
+    a, *_ = _sampler(chain, xstar, 100, 30, False, samptunning=4, nsave=6)
+    b, *_ = _sampler(chain, xstar, 100, 30, False, samptunning=4, nsave=6)
+    a.run(10)
+    for _ in range(10):
+        b.run(1)
+    sa, sb = a.state(), b.state()
+    for key in ("theta", "fval", "tau", "numtimes", "k"):
+        assert np.array_equal(sa[key], sb[key]), key
+    for t in ("save", "naccept", "nswap"):
+        assert np.array_equal(getattr(a, t).cpu().numpy(), getattr(b, t).cpu().numpy()), t
+
+
+@pytest.mark.parametrize("gradient", [False, True])
+def test_more_rungs_than_threads(tmp_path, gradient):
+    """200 + 61 = 261 rungs: 1305 picks (five full rounds and one of 25) and a second pass of every loop over the rungs in
+    the exchange's workgroup of 256"""
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s, temps, hc, cov0 = _sampler(chain, xstar, 200, 61, gradient, samptunning=3, nsave=3)
+    near = _step_by_step(chain, s, temps, hc, cov0, 6)
+    assert near <= 2 and s.nswap.sum().item() > 0 and s.naccept.sum().item() > 0
+
+
+def test_wide_odd_rows_plain(tmp_path):
+    """127 parameters (sampler_cases.wide_chain): the lanes of k_ptl_propose and k_ptl_accept make a second pass, and the last
+    normal of a row is half a pair"""
+    chain = wide_chain(str(tmp_path), 127)
+    s, temps, hc, cov0 = _sampler(chain, wide_start(127), 6, 4, False, samptunning=3, nsave=3)
+    assert s.d == 127
+    near = _step_by_step(chain, s, temps, hc, cov0, 6)
+    assert near <= 2 and s.naccept.sum().item() > 0
+
+
+def test_wide_odd_rows_gradient(tmp_path):
+    """a real parameterTrafoPCA emulator over 71 parameters (64 GP inputs): first the chain's gradient against autograd of
+    the torch restatement on eight rows at the bar of tests/test_gpu_gradient.py, then six steps of the gradient branch"""
+    from test_gpu_gradient import BAR, _rowerr
+    import grad_reference as G
+    chain, emu, mid = mapped_chain(tmp_path, 71)
+    assert chain.ndim == 71 and emu.PCA_new_design_points.shape[1] == 64
+    width = chain.max - chain.min
+    rng = np.random.default_rng(17)
+    X = mid + 0.02 * width * rng.standard_normal((8, 71))
+    lp, g = chain.log_posterior(X, return_grad=True)
+    assert np.array_equal(lp, chain.log_posterior(X)) and np.all(np.isfinite(lp))
+    v, gref = G.value_and_grad(mapped_log_posterior(chain, emu), X)
+    print("gradient over 71 mapped parameters: worst row %.3g of the bar" % (float(np.max(_rowerr(g, gref))) / BAR))
+    assert np.all(_rowerr(g, gref) <= BAR), _rowerr(g, gref)
+    theta = mid + 0.01 * width * rng.standard_normal((8, 71))
+    s, temps, hc, cov0 = _sampler(chain, mid, 4, 4, True, samptunning=3, nsave=3, theta=theta)
+    assert s.d == 71
+    near = _step_by_step(chain, s, temps, hc, cov0, 6)
+    assert near <= 2 and s.naccept.sum().item() > 0
+
+
+def test_rungs_outside_the_box(tmp_path):
+    """two adjacent tempered rungs and one untempered rung start outside the box (fval = -inf): a proposal that lands outside
+    is rejected (-inf - -inf is NaN, and NaN is not above log u), the swap test between two such rungs is NaN and does not
+    swap, and every step still agrees with the restatement"""
+    from gpbayestools_hic_amd import ptlmc
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    temps = ptlmc.ladder(6, 4, 20.0)
+    theta, _, _ = _start(chain, xstar, 10, 11, False, temps)
+    covmat0, hc = ptlmc.proposal_factor(theta)               # the proposal scale of the rows inside: steps of a few 0.01
+    theta[2, 0], theta[3, 1], theta[7, 2] = 1.2, -0.004, 1.2
+    fval = chain.log_posterior(theta) / temps
+    assert np.array_equal(np.flatnonzero(np.isinf(fval)), [2, 3, 7]) and np.all(fval[[2, 3, 7]] < 0)
+    s = ptlmc.PTLMCSampler(chain, temps, hc, covmat0, 6, 4, 3, 5, ptlmc.TARACC_PLAIN, 11, False)
+    s.set_state(theta, fval)
+    seen = dict(both=0)
+
+    def each(before, info, took):
+        out = ~np.all((info["thetap"] > chain.min) & (info["thetap"] < chain.max), axis=1)
+        assert np.array_equal(np.isinf(info["lp"]), out)
+        assert not np.any(took[out])                         # from inside or from outside: never accepted
+        was_out = np.isinf(before["fval"])
+        seen["both"] += int(np.sum(out & was_out))
+        assert np.all(took[~out & was_out] == 1)             # finite - -inf = +inf: back inside is always accepted
+
+    near = _step_by_step(chain, s, temps, hc, covmat0, 8, rel=_rel_inf, each=each)
+    assert near <= 2
+    assert seen["both"] >= 8, seen                           # the rungs 0.2 outside never come back within eight small steps

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import smc_reference as R
+from sampler_cases import wide_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,7 @@ def _check_stage(s, lc_normwise=False):
     # the ancestors from the device's own beta (the weights then agree to rounding)
     w, _ = R.weights(before["logl"], got["beta"] - before["beta"])
     anc, cum, pos = R.resample(w, u)
-    edge = np.minimum(np.abs(cum[np.minimum(anc, s.N - 1)] - pos), np.abs(np.where(anc > 0, cum[np.maximum(anc - 1, 0)], -1.0) - pos)) < 1e-12
+    edge = R.knife_edges(anc, cum, pos)       # within 1e-12 of the scan entry that decides (also tests/test_smc_reference.py)
     dev_anc = s.ancestors.cpu().numpy()
     assert int(edge.sum()) <= 2, int(edge.sum())
     assert np.array_equal(dev_anc[~edge], anc[~edge])
@@ -113,7 +114,8 @@ def test_draws_match_restatement():
     from gpbayestools_hic_amd.engine import GPEngine
     with nat.debug_library():
         eng = GPEngine(0)
-    for (N, d, seed, stage, k) in [(10, 4, 7, 0, 0), (37, 9, 2 ** 40 + 3, 5, 123), (130, 15, 12345, 77, 2999)]:
+    for (N, d, seed, stage, k) in [(10, 4, 7, 0, 0), (37, 9, 2 ** 40 + 3, 5, 123), (130, 15, 12345, 77, 2999),
+                                   (1027, 127, 2 ** 33 + 5, 3, 41), (16389, 5, 99, 1, 7)]:
         nrm = torch.empty((N, d), dtype=torch.float64, device="cuda:0")
         la = torch.empty(N, dtype=torch.float64, device="cuda:0")
         ur = torch.empty(1, dtype=torch.float64, device="cuda:0")
@@ -291,45 +293,11 @@ def test_limits_and_refusals(tmp_path):
         SMCSampler(chain, 64)
 
 
-def _wide_chain(tmp, D):
-    """a chain of D parameters: one parameterTrafoPCA emulator trained over 20 of them whose device map (gpb_param_map_set)
-    is told that the rows have D columns.  The GPs take at most 64 inputs and the map drops only a few columns, so an
-    Emulator trained over D > ~70 parameters does not exist; the C ABI's map reads any columns of a wider row, which is how
-    a chain gets more parameters than its GPs have inputs.  The likelihood is flat in columns 20 .. D - 1, the box is not."""
-    from gpbayestools_hic_amd import _native as nat
-    from gpbayestools_hic_amd import param_pca as pp
-    from gpbayestools_hic_amd.workload import build_multi_chain
-    chain, emus, info = build_multi_chain([(128, 12, 3, "RBF")], 20, workdir=tmp, mapped=True)
-    emu = emus[0]
-    eng = emu._engine_ready()
-    groups = emu._ppca.groups
-    G, maxpc = len(groups), int(max(g.pca.n_components_ for g in groups))
-    cols = np.arange(20, dtype=np.int64)          # the column bookkeeping of GPEngine.set_param_map over the trained 20
-    desc = np.full((G, 6), -1, dtype=np.int32)
-    tab = np.zeros((G, 4 + maxpc, 100))
-    for gi, (g, idx, grid) in enumerate(zip(groups, (pp.IDX_BULK, pp.IDX_SHEAR, pp.IDX_YLOSS),
-                                            (pp.T_GRID, pp.MUB_GRID, pp.YINIT_GRID))):
-        k = int(g.pca.n_components_)
-        cols = np.concatenate((np.delete(cols, idx), -1 - (gi * maxpc + np.arange(k))))
-        desc[gi, 0], desc[gi, 1:1 + len(idx)], desc[gi, 5] = gi, idx, k
-        tab[gi, 0], tab[gi, 1], tab[gi, 2], tab[gi, 3] = grid, g.scaler.mean_, g.scaler.scale_, g.pca.mean_
-        tab[gi, 4:4 + k] = g.pca.components_
-    col_src = np.ascontiguousarray(cols, dtype=np.int32)
-    assert col_src.shape[0] == eng.pmap_d_out
-    eng._ck(eng.lib.gpb_param_map_set(eng.h, D, eng.pmap_d_out, nat.ptr(col_src), G, nat.ptr(np.ascontiguousarray(desc)),
-                                      nat.ptr(np.ascontiguousarray(tab)), maxpc))
-    eng.pmap_d_in = D
-    chain.ndim = D
-    chain.min, chain.max = np.zeros(D), np.ones(D)
-    chain.prior_volume_ = 1.0
-    return chain
-
-
 def test_more_parameters_than_the_limit_is_an_argument_error(tmp_path):
     """a chain of 129 parameters: GPB_E_ARG from both entry points, before anything is enqueued"""
     import torch
     from gpbayestools_hic_amd import _native as nat
-    chain = _wide_chain(str(tmp_path), 129)
+    chain = wide_chain(str(tmp_path), 129)
     s = _sampler(chain, 64)                   # (the start particles are evaluated by the chain call, which has no such limit)
     assert np.all(np.isfinite(s.logl.cpu().numpy()))
     engs, arr, E = chain._contexts()
@@ -352,7 +320,7 @@ def test_stage_near_the_largest_d(tmp_path):
     127 * 1.1e-16 * cond, and that is 1e-10 for cond up to 7e3; of the 8128 entries of the factor of a sampled covariance
     (|Lc| up to 0.29, typical off-diagonal 0.29 / sqrt(N) = 0.013) the smallest are ~1e-6, where 1e-10 of the entry itself
     is less than that rounding.  x is held to 1e-12 of the unit box for the same reason: entries of x down to 1e-5 occur."""
-    chain = _wide_chain(str(tmp_path), 127)
+    chain = wide_chain(str(tmp_path), 127)
     s = _sampler(chain, 512)
     assert s.d == 127
     near = 0
@@ -415,3 +383,149 @@ def test_pickle_schema(tmp_path):
     assert out["acceptance"].shape == out["beta"].shape and np.all((out["acceptance"] >= 0) & (out["acceptance"] <= 1))
     again = chain.run_SMC(n_particles=256, nmcmc=5, seed=9)
     assert np.array_equal(again["chain"], out["chain"]) and again["logz"] == out["logz"]
+
+
+# ------------------------------------------------------------------ beyond one pass of the kernels' strided loops
+# k_smc_reweight: 1024 threads, a contiguous chunk of C = ceil(N / 1024) weights each, the first 16384 logl - max in LDS;
+# k_smc_propose: min(ceil(N / 4), 2 CUs) workgroups of four waves striding over the particles; k_smc_resample / k_smc_accept:
+# 256 rows per workgroup.  Every size above 1024 gives C > 1, every size that is no multiple of 256 a ragged last workgroup.
+def _stages_and_steps(tmp_path, N, d, stages, steps):
+    chain, emu, xstar = _emulator(str(tmp_path), 192, d, 8, 4)
+    s = _sampler(chain, N)
+    near = 0
+    for _ in range(stages):
+        _check_stage(s)
+        for _ in range(steps):
+            near += _check_step(chain, s, None)
+    assert near <= 2 and s.k == stages * steps and s.read_block()["naccept"] > 0
+    return s
+
+
+def test_ragged_two_entry_chunks(tmp_path):
+    """N = 1027 (a multiple of neither 4, 64 nor 256), d = 5: C = 2, thread 513 owns one weight, the threads from 514 on none;
+    the last quad of the proposals has one particle, the last workgroup of the resampling and of the accept three rows"""
+    _stages_and_steps(tmp_path, 1027, 5, 2, 3)
+
+
+def test_strided_proposals(tmp_path):
+    """N = 8 CUs + 3: workgroup 0 of k_smc_propose makes a second trip in which one of its four waves has no particle"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    N = 8 * cus + 3
+    assert N > 8 * cus and -(-N // 4) > 2 * cus               # more quads than workgroups: the particle loop strides
+    _stages_and_steps(tmp_path, N, 5, 1, 2)
+
+
+def test_default_size(tmp_path):
+    """run_SMC's default of 4096 particles: C = 4, two trips of the proposal loop on 256 CUs"""
+    s = _stages_and_steps(tmp_path, 4096, 5, 1, 2)
+    a, b = _sampler(s.chain, 4096), _sampler(s.chain, 4096)
+    a.reweight()
+    a.move(3)
+    b.reweight()
+    for _ in range(3):
+        b.move(1)
+    sa, sb = a.state(), b.state()
+    for key in sa:
+        assert np.array_equal(sa[key], sb[key]), key
+
+
+def test_past_the_lds_window(tmp_path):
+    """N = 16389, d = 4: C = 17, the last five logl - max are re-read from global memory in every pass of the bisection,
+    thread 964 owns one weight and the threads behind it none"""
+    _stages_and_steps(tmp_path, 16389, 4, 1, 1)
+
+
+def _injected(chain, N, logl, beta=0.0):
+    s = _sampler(chain, N)
+    s.set_state(np.random.default_rng(N).uniform(chain.min, chain.max, (N, s.d)), logl=logl, beta=beta)
+    return s
+
+
+@pytest.mark.parametrize("beta", [0.0, 0.37])
+@pytest.mark.parametrize("N", R.INJECTED_SIZES)
+def test_injected_weights(tmp_path, N, beta):
+    """log-likelihoods set by hand (smc_reference.injected_logl: runs of zero weights at both ends and inside, NaNs across a
+    chunk boundary), no chain evaluation: the stage against the restatement, the NaN counter, and no ancestor of weight zero.
+    tests/test_smc_reference.py shows on the host that the cap of 2 knife edges hides nothing here."""
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    logl = R.injected_logl(N)
+    s = _injected(chain, N, logl, beta)
+    _check_stage(s)
+    assert s.read_block()["nan_weights"] == 6
+    anc = s.ancestors.cpu().numpy()
+    assert np.all(np.isfinite(logl[anc]) & (logl[anc] > -1e300))
+    assert np.all(np.diff(anc) >= 0)
+
+
+def test_equal_weights(tmp_path):
+    """a constant log-likelihood: one stage reaches beta = 1 with ESS = N, every particle is its own ancestor"""
+    N = 1027
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s = _injected(chain, N, np.full(N, -12.5))
+    _check_stage(s)
+    blk = s.read_block()
+    assert blk["beta"] == 1.0 and blk["ess"] == float(N)       # every weight is exp(0) = 1: the sums are exact
+    u = R.device_draws(s.seed, 0, 0, 2, 1)["u_resample"]
+    assert 1e-9 < u < 1.0 - 1e-9                               # positions (u + i) / N well inside (i / N, (i + 1) / N)
+    assert np.array_equal(s.ancestors.cpu().numpy(), np.arange(N))
+
+
+@pytest.mark.parametrize("value", [np.nan, -np.inf])
+def test_no_finite_weight_raises(tmp_path, value):
+    """all NaN / all -inf: every weight is 0, the scan is 0 / 0, the search of k_smc_resample ends at its clamp N - 1; the
+    flag is raised on the host and a good state afterwards works"""
+    N = 1027
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s = _injected(chain, N, np.full(N, value))
+    s.reweight()
+    with pytest.raises(RuntimeError, match="no particle has a finite log-likelihood"):
+        s.read_block()
+    anc = s.ancestors.cpu().numpy()
+    assert np.all((anc >= 0) & (anc <= N - 1))
+    s.init_uniform()
+    _check_stage(s)
+    assert s.read_block()["nan_weights"] == 0
+
+
+def test_nan_proposals_are_counted_and_rejected(tmp_path):
+    """an indefinite experimental covariance makes every block NaN (tests/test_gpu_sampler.py does the same to the stretch
+    move).  A proposal outside the box never reaches the blocks: it takes the outside value and is rejected without being
+    counted, so first, at the stage's own proposal scale, the counter must equal the number of restated proposals inside the
+    box; then, with a proposal scale of 1e-9 that keeps every proposal inside, two move steps change neither x nor logl, count
+    2 N NaN proposals, accept nothing, and log_sigma falls by 0.234 / (s + 1) per step"""
+    N = 1027
+    chain, emu, xstar = _emulator(str(tmp_path), 192, 4, 8, 4)
+    s = _sampler(chain, N)
+    s.reweight()
+    s.move(3)
+    before = s.state()
+    assert before["nan_moves"] == 0 and before["naccept"] > 0 and before["s"] == 3
+
+    def proposals_inside(st):
+        xp = R.propose(st["x"], st["log_sigma"], st["Lc"], R.device_draws(s.seed, 0, st["k"], N, s.d)["normals"])
+        return np.all((xp > chain.min) & (xp < chain.max), axis=1)
+
+    good_cov = chain.expdata_cov
+    try:
+        chain.expdata_cov = -0.5 * np.eye(chain.nobs)
+        inside = 0
+        for _ in range(2):
+            inside += int(proposals_inside(s.state()).sum())
+            s.move(1)
+        mid = s.state()
+        assert 0 < inside < 2 * N and mid["nan_moves"] == inside and mid["naccept"] == before["naccept"]
+        assert np.array_equal(mid["x"], before["x"]) and np.array_equal(mid["logl"], before["logl"])
+        assert abs(mid["log_sigma"] - (before["log_sigma"] - 0.234 / 4.0 - 0.234 / 5.0)) <= 1e-12
+        # the same particles with a tiny proposal scale (set_state zeroes the counters and leaves Lc alone)
+        s.set_state(mid["x"], mid["logl"], mid["beta"], mid["logz"], np.log(1e-9), mid["stage"], mid["k"], mid["s"])
+        tiny = s.state()
+        assert np.array_equal(tiny["Lc"], before["Lc"]) and proposals_inside(tiny).all()
+        s.move(2)
+        got = s.state()
+    finally:
+        chain.expdata_cov = good_cov
+    assert np.array_equal(got["x"], before["x"]) and np.array_equal(got["logl"], before["logl"])
+    assert got["nan_moves"] == 2 * N and got["naccept"] == tiny["naccept"] == 0
+    assert abs(got["log_sigma"] - (tiny["log_sigma"] - 0.234 / 6.0 - 0.234 / 7.0)) <= 1e-12
+    _check_step(chain, s, None)                                # and the sampler carries on once the cause is gone

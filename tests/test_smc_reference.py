@@ -81,6 +81,54 @@ def test_systematic_resampling_counts():
             assert np.all(counts[w == 0.0] == 0)
 
 
+def test_device_scan_model():
+    """the chunked scan against np.cumsum: monotone, flat exactly over zero weights (also across a chunk boundary), 1 at the
+    end, and np.cumsum itself when every thread owns at most one entry"""
+    rng = np.random.default_rng(8)
+    for N in (5, 1024, 1027, 2051, 4096, 16389):
+        w = rng.exponential(size=N)
+        w[rng.integers(0, N, size=N // 4)] = 0.0
+        C = -(-N // R.RW_THREADS)
+        w[max(3 * C - 2, 0):3 * C + 2] = 0.0
+        w[0], w[N - 1] = 0.0, 0.5
+        cum = R.device_scan(w)
+        ref = np.cumsum(w) / np.sum(w)
+        assert cum.shape == (N,) and cum[-1] == 1.0 and np.all(np.diff(cum) >= 0)
+        assert np.all(np.diff(cum)[w[1:] == 0.0] == 0.0) and cum[0] == 0.0
+        assert np.max(np.abs(cum - ref)) <= 2 * N * 2.0 ** -53
+        if N <= R.RW_THREADS:
+            c1 = np.cumsum(w)
+            assert np.array_equal(cum, c1 / c1[-1])
+    # three threads over eight weights: chunks [0:3], [3:6], [6:8], bases 0, 6, 21 of a total of 36
+    assert np.array_equal(R.device_scan(np.arange(1.0, 9.0), threads=3), np.array([1, 3, 6, 10, 15, 21, 28, 36]) / 36.0)
+
+
+@pytest.mark.parametrize("beta_prev", [0.0, 0.37])
+@pytest.mark.parametrize("N", R.INJECTED_SIZES)
+def test_injected_weights_edges_under_both_scans(N, beta_prev):
+    """what the cap of 2 knife-edge ancestors per stage in tests/test_gpu_smc.py rests on, where no GPU is needed: with the
+    injected log-likelihoods the ancestors under np.cumsum and under the device's chunked scan differ at knife edges only,
+    and those number at most 2"""
+    logl = R.injected_logl(N)
+    assert int(np.sum(np.isnan(logl))) == 6
+    rw = R.reweight(logl, beta_prev, 0.5)
+    assert rw["nan_weights"] == 6 and beta_prev < rw["beta"] < 1.0
+    zero = rw["w"] == 0.0
+    assert zero[:3].all() and zero[N - 2:].all() and int(zero.sum()) == 13
+    worst = 0.0
+    for u in (0.0, 0.31, 0.999999, R.device_draws(11, 0, 0, 2, 1)["u_resample"]):     # the last: the GPU tier's seed and stage
+        anc, cum, pos = R.resample(rw["w"], u)
+        anc_dev, cum_dev, _ = R.resample(rw["w"], u, scan=R.device_scan)
+        edge = R.knife_edges(anc, cum, pos)
+        worst = max(worst, float(np.max(np.abs(cum_dev - cum))))
+        assert int(edge.sum()) <= 2, (u, int(edge.sum()))
+        assert np.array_equal(anc_dev[~edge], anc[~edge]), u
+        for a in (anc, anc_dev):
+            assert np.all(np.diff(a) >= 0) and not np.any(zero[a])
+    print("N=%d beta_prev=%g: the two scans differ by at most %.3g" % (N, beta_prev, worst))
+    assert worst <= 2 * N * 2.0 ** -53          # either scan: sums of at most N positive terms, each addition within 2^-53
+
+
 def test_preconditioner_and_degenerate_ensemble():
     rng = np.random.default_rng(1)
     x = rng.standard_normal((300, 5)) @ rng.standard_normal((5, 5)) + 3.0
