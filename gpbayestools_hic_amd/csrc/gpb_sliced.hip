@@ -30,7 +30,15 @@
 // tile (128 x 64 for small batches), waves of 32 rows x 64 (32) walkers (6 x 2 x 16 = 192 accumulator registers), stages of 48
 // (36) KB.  D = 7: 128 x 64 always, waves of 32 x 32 (7 x 16 = 112 accumulators, 162 registers in all; 32 x 64 would need ~280
 // of the 256 a wave has at two per SIMD), stages of 42 KB.
+//
+// K loop (round 20, profiles/r20_int8_kloop.txt; the index arithmetic is csrc/sl_index.h, proven on the host for every geometry by
+// tests/host/sl_index_check.cpp): a wave sets the sources of its <= 6 pieces of a stage once per tile, as wave-uniform pointers,
+// and moves each by its operand's stride (32 Np128 or 32 Wld bytes) after every stage — between a step's last MFMA and its last
+// DMA there is one vector add per DMA (v_lshl_add_u64: scalar base + the lane's offset) and no multiply; the stage buffers' LDS
+// offsets are counted round, not divided out.  Leaving out the steps of the diagonal block that are all zeros for a wave row (6 of
+// its 16 (wave row, step) pairs) was measured in the same round and not kept: alone it did not clear the round's bar.
 #include "gpb_internal.h"
+#include "sl_index.h"
 
 namespace gpb {
 
@@ -47,6 +55,7 @@ struct SlDig {
 constexpr int SL_DMAX = 7;                                                     // planes a buffer has room for
 constexpr int64_t SL_NP_MAX = 16384;                                           // D x Np x 2^14 < 2^31: the int32 sums are exact
 constexpr int SL_BM = 128;
+static_assert(SL_BM == SL_IDX_BM, "sl_index.h states the block tile's rows for the host check");
 // block tile 128 rows x (64 WTN) walkers: WTN = 2 for batches that fill the chip with 128 x 128 tiles, WTN = 1 (half the
 // accumulators, 3/4 of the bytes per K-step for half the MFMAs: bound by the operand feed) for smaller ones — a rank's share of a
 // sharded ensemble.  The shape never changes a bit: integer sums are exact and the epilogue's order is the row's.
@@ -131,26 +140,46 @@ __global__ __launch_bounds__(256) void k_sl_slice_linv(const double* __restrict_
 // (the planes of K*^T are written by k_kcross itself, SLICE form: gpb_predict.hip)
 
 // ---------------------------------------------------------------------------------------------------------------- the tile kernel
-// wave-uniform: this wave's share of the DMA of one K-step (k-blocks kb0, kb0 + 1) into stage buffer `buf`
+// This wave's 1-KB pieces of a stage (piece 8 c + wave for c < NPW) and where each comes from: wave-uniform pointers to lane 0's
+// granule, set once per tile (sl_src_offset at the tile's first K-step) and moved by the operand's stride after every stage
+// (sl_src_stride): the K loop rebuilds no address.  tests/host/sl_index_check.cpp holds the two forms together, inside the planes.
 template <int D, int WTN>
-__device__ __forceinline__ void sl_dma_stage(char* lds, int buf, const int8_t* __restrict__ Ap, const int8_t* __restrict__ Bp,
-                                             int64_t a_plane, int64_t b_plane, int64_t Np128, int64_t Wld, int64_t mb, int64_t nb,
-                                             int64_t kb0, int wave, int lane) {
+struct SlSrc {
+    const int8_t* p[SlGeo<D, WTN>::NPW];
+    int64_t stride[SlGeo<D, WTN>::NPW];
+};
+
+template <int D, int WTN>
+__device__ __forceinline__ void sl_dma_sources(SlSrc<D, WTN>& src, const int8_t* __restrict__ Ap, const int8_t* __restrict__ Bp,
+                                               int64_t a_plane, int64_t b_plane, int64_t Np128, int64_t Wld, int64_t mb, int64_t nb,
+                                               int64_t kb_first, int wave) {
     typedef SlGeo<D, WTN> G;
-    char* base = lds + buf * G::STAGE;
+#pragma unroll
+    for (int c = 0; c < G::NPW; ++c) {
+        const int ch = 8 * c + wave;                                    // wave-uniform
+        const bool none = c == G::NPW - 1 && G::REM != 0 && wave >= G::REM;      // (this wave has no such piece: never issued)
+        const SlChunk k = sl_chunk(none ? 0 : ch, D, WTN);
+        const int64_t ld = k.is_a ? Np128 : Wld;
+        src.p[c] = (k.is_a ? Ap : Bp) + sl_src_offset(k, k.is_a ? a_plane : b_plane, ld, k.is_a ? mb : nb, kb_first, 0);
+        src.stride[c] = none ? 0 : sl_src_stride(ld);
+    }
+}
+
+// wave-uniform: this wave's share of the DMA of the next K-step into the stage buffer at byte `stage` of the LDS; the sources then
+// move on one step.  A DMA's address is written as scalar base + the lane's 32-bit offset (16 lane); inside the K loop the compiler
+// forms it with one 64-bit vector add per DMA and issues the VGPR-address form (the SGPR-base form only in the prologue).
+template <int D, int WTN>
+__device__ __forceinline__ void sl_dma_stage(char* lds, int stage, SlSrc<D, WTN>& src, int wave, unsigned lane16) {
+    typedef SlGeo<D, WTN> G;
+    char* base = lds + stage;
 #pragma unroll
     for (int c = 0; c < G::NPW; ++c) {
         const int ch = 8 * c + wave;                                    // wave-uniform
         if (c == G::NPW - 1 && G::REM != 0 && wave >= G::REM) break;
-        const bool is_a = ch < G::A_CHUNKS;
-        const int cb = is_a ? ch : ch - G::A_CHUNKS;
-        const int per = is_a ? SL_BM / 64 : WTN;                        // 1-KB pieces per (plane, k-block)
-        const int t = cb / (2 * per), q = (cb / per) & 1, h = cb % per;
-        const int64_t ld = is_a ? Np128 : Wld, off = is_a ? mb : nb;
-        const int8_t* plane = is_a ? Ap + t * a_plane : Bp + t * b_plane;
-        const int8_t* src = plane + ((kb0 + q) * ld + off + 64 * h + lane) * 16;
-        __builtin_amdgcn_global_load_lds((const void*)src, (sl_lds_ptr)(base + ch * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void*)(src.p[c] + lane16), (sl_lds_ptr)(base + ch * 1024), 16, 0, 0);
     }
+#pragma unroll
+    for (int c = 0; c < G::NPW; ++c) src.p[c] += src.stride[c];
 }
 
 template <int N>
@@ -167,10 +196,10 @@ __device__ __forceinline__ void sl_wait_stage(bool more, bool full_count) {
 
 // fragments are read where they are used (the SIMD's other wave covers the LDS latency): A once, B per 32-walker n-tile
 template <int D, int WTN>
-__device__ __forceinline__ void sl_mma_step(const char* lds, int buf, int wm, int wn, int lane, v16i (&acc)[SlDig<D>::NLEV][WTN]) {
+__device__ __forceinline__ void sl_mma_step(const char* lds, int stage, int wm, int wn, int lane, v16i (&acc)[SlDig<D>::NLEV][WTN]) {
     typedef SlGeo<D, WTN> G;
     constexpr int LOW = SlDig<D>::LOW;
-    const char* base = lds + buf * G::STAGE;
+    const char* base = lds + stage;
     const int q = lane >> 5, r = lane & 31;
     v4i a[D];
 #pragma unroll
@@ -252,20 +281,27 @@ __device__ __forceinline__ void predict_sliced_body(const SlGP& G0, const SlTabl
         for (int j = 0; j < WTN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[l][j][r] = 0;
-    sl_dma_stage<D, WTN>(lds, 0, Ap, Bp, a_plane, b_plane, Np128, Wld, mb, nb, kb_first, wave, lane);
-    if (nsteps > 1) sl_dma_stage<D, WTN>(lds, 1, Ap, Bp, a_plane, b_plane, Np128, Wld, mb, nb, kb_first + 2, wave, lane);
+    const unsigned lane16 = (unsigned)lane * 16u;
+    SlSrc<D, WTN> src;
+    sl_dma_sources<D, WTN>(src, Ap, Bp, a_plane, b_plane, Np128, Wld, mb, nb, kb_first, wave);
+    sl_dma_stage<D, WTN>(lds, 0, src, wave, lane16);
+    if (nsteps > 1) sl_dma_stage<D, WTN>(lds, G::STAGE, src, wave, lane16);
+    // rd, wr: where in the LDS buffer s % 3, which step s reads, and buffer (s + 2) % 3, which its DMA fills, begin: counted round,
+    // so that the loop neither divides nor multiplies
+    int rd = 0, wr = 2 * G::STAGE;
     for (int s = 0; s < nsteps; ++s) {
         // stage s has landed for this wave (its own DMAs of stage s + 1 may still fly), every wave says so at the barrier, and
         // every wave has finished reading buffer (s + 2) % 3 = (s - 1) % 3 (its reads were consumed by the MFMAs of step s - 1)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         sl_wait_stage<D, WTN>(s + 1 < nsteps, fullc);
         __builtin_amdgcn_s_barrier();
-        sl_mma_step<D, WTN>(lds, s % 3, wm, wn, lane, acc);
+        sl_mma_step<D, WTN>(lds, rd, wm, wn, lane, acc);
         // the DMA of stage s + 2 BEHIND the step's MFMAs: a global_load_lds costs its wave ~60 cycles of issue, which then fall
         // into the time its queued MFMAs drain (issued first: 0.95 -> 0.74 ms on the micro-kernel, profiles/r06_sliced_model.txt);
         // buffer (s + 2) % 3 was last read in step s - 1, which every wave has left (the barrier above)
-        if (s + 2 < nsteps)
-            sl_dma_stage<D, WTN>(lds, (s + 2) % 3, Ap, Bp, a_plane, b_plane, Np128, Wld, mb, nb, kb_first + 2 * (int64_t)(s + 2), wave, lane);
+        if (s + 2 < nsteps) sl_dma_stage<D, WTN>(lds, wr, src, wave, lane16);
+        rd = rd == 2 * G::STAGE ? 0 : rd + G::STAGE;
+        wr = wr == 2 * G::STAGE ? 0 : wr + G::STAGE;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();

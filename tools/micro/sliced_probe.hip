@@ -25,12 +25,20 @@
 #include <string.h>
 #include <vector>
 #include <algorithm>
+#include "../../gpbayestools_hic_amd/csrc/sl_index.h"
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
 #define STAMP 1      // 1: stamp the wait + barrier of every step (diagnostic build; costs a few percent)
+// Round 20, the in-step loop of the 8-wave kernel (the library's): DMA sources set once per tile and moved by a stride
+// (csrc/sl_index.h).  The earlier form stays buildable for A/B runs of the same source: -DADDR_REBUILT=1 rebuilds every DMA
+// address from the step number.  (The round also measured leaving out the all-zero steps of the diagonal block, behind a second
+// switch; it was not kept: profiles/r20_int8_kloop.txt.)
+#ifndef ADDR_REBUILT
+#define ADDR_REBUILT 0
+#endif
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
 
 struct TileRec { int p, ib, wt, pad; };
@@ -384,6 +392,44 @@ __device__ __forceinline__ void dma_stage8(char* lds, int buf, const int8_t* __r
     }
 }
 
+// the library's form (sl_dma_sources, sl_dma_stage of gpb_sliced.hip): wave-uniform sources of this wave's pieces, set once per tile
+// at K-step 0 and moved by the operand's stride after every stage; the address of a DMA is a scalar base + the lane's 16 lane
+template <int D, int WTN>
+struct Src8 {
+    const int8_t* p[Geo8<D, WTN>::NPW];
+    int64_t stride[Geo8<D, WTN>::NPW];
+};
+
+template <int D, int WTN>
+__device__ __forceinline__ void dma_sources8(Src8<D, WTN>& src, const int8_t* __restrict__ Ap, const int8_t* __restrict__ Bp, int64_t Np,
+                                             int64_t Wld, int64_t mb, int64_t nb, int wave) {
+    typedef Geo8<D, WTN> G8;
+    const int64_t a_plane = (Np / 16) * Np * 16, b_plane = (Np / 16) * Wld * 16;
+#pragma unroll
+    for (int c = 0; c < G8::NPW; ++c) {
+        const int ch = 8 * c + wave;
+        const bool none = c == G8::NPW - 1 && G8::REM != 0 && wave >= G8::REM;
+        const gpb::SlChunk k = gpb::sl_chunk(none ? 0 : ch, D, WTN);
+        const int64_t ld = k.is_a ? Np : Wld;
+        src.p[c] = (k.is_a ? Ap : Bp) + gpb::sl_src_offset(k, k.is_a ? a_plane : b_plane, ld, k.is_a ? mb : nb, 0, 0);
+        src.stride[c] = none ? 0 : gpb::sl_src_stride(ld);
+    }
+}
+
+template <int D, int WTN>
+__device__ __forceinline__ void dma_next8(char* lds, int stage, Src8<D, WTN>& src, int wave, unsigned lane16) {
+    typedef Geo8<D, WTN> G8;
+    char* base = lds + stage;
+#pragma unroll
+    for (int c = 0; c < G8::NPW; ++c) {
+        const int ch = 8 * c + wave;
+        if (c == G8::NPW - 1 && G8::REM != 0 && wave >= G8::REM) break;
+        __builtin_amdgcn_global_load_lds((const void*)(src.p[c] + lane16), (lds_ptr)(base + ch * 1024), 16, 0, 0);
+    }
+#pragma unroll
+    for (int c = 0; c < G8::NPW; ++c) src.p[c] += src.stride[c];
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -488,7 +534,14 @@ __global__ __launch_bounds__(512, 2) void k_sliced8(const int8_t* __restrict__ A
         for (int j = 0; j < WTN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[l][j][r] = 0;
-    if (MODE & 1) {
+    constexpr bool ADVANCED = !PF && !ADDR_REBUILT;                       // the in-step loop moves its sources; the prefetch loop rebuilds
+    const unsigned lane16 = (unsigned)lane * 16u;
+    Src8<D, WTN> src;
+    if (ADVANCED && (MODE & 1)) {
+        dma_sources8<D, WTN>(src, Ap, Bp, Np, Wld, mb, nb, wave);
+        dma_next8<D, WTN>(lds, 0, src, wave, lane16);
+        if (nsteps > 1) dma_next8<D, WTN>(lds, G::STAGE_BYTES, src, wave, lane16);
+    } else if (MODE & 1) {
         dma_stage8<D, WTN>(lds, 0, Ap, Bp, Np, Wld, mb, nb, 0, wave, lane);
         if (nsteps > 1) dma_stage8<D, WTN>(lds, 1, Ap, Bp, Np, Wld, mb, nb, 2, wave, lane);
         if (PF && nsteps > 2) dma_stage8<D, WTN>(lds, 2, Ap, Bp, Np, Wld, mb, nb, 4, wave, lane);
@@ -525,6 +578,7 @@ __global__ __launch_bounds__(512, 2) void k_sliced8(const int8_t* __restrict__ A
         if (s < nsteps) step(s, f0, f1);
     } else {
         // fragments read in the step that uses them (the partner wave covers the LDS latency): stage s read, s + 1, s + 2 in flight
+        int wr = 2 * G::STAGE_BYTES;                                     // where buffer (s + 2) % 3 begins: counted round
         for (int s = 0; s < nsteps; ++s) {
             const unsigned long long w0 = STAMP ? __builtin_amdgcn_s_memtime() : 0;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -532,7 +586,9 @@ __global__ __launch_bounds__(512, 2) void k_sliced8(const int8_t* __restrict__ A
             __builtin_amdgcn_s_barrier();
             if (STAMP) stall += __builtin_amdgcn_s_memtime() - w0;
             auto dma = [&]() {
-                if ((MODE & 1) && s + 2 < nsteps) dma_stage8<D, WTN>(lds, (s + 2) % 3, Ap, Bp, Np, Wld, mb, nb, 2 * (int64_t)(s + 2), wave, lane);
+                if (!((MODE & 1) && s + 2 < nsteps)) return;
+                if constexpr (ADVANCED) dma_next8<D, WTN>(lds, wr, src, wave, lane16);
+                else dma_stage8<D, WTN>(lds, (s + 2) % 3, Ap, Bp, Np, Wld, mb, nb, 2 * (int64_t)(s + 2), wave, lane);
             };
             if ((MODE & 6) != 6) dma();
             if constexpr (POS == 8 && WTN == 2) { if ((MODE & 6) == 6) mma_step8_ordered<D, LOW>(lds, s % 3, wm, wn, lane, acc, dma); }
@@ -547,6 +603,7 @@ __global__ __launch_bounds__(512, 2) void k_sliced8(const int8_t* __restrict__ A
                 }
                 mma_step8<D, LOW, WTN>(f, acc);
             }
+            wr = wr == 2 * G::STAGE_BYTES ? 0 : wr + G::STAGE_BYTES;
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
