@@ -79,6 +79,7 @@ BOUNDARY = {
     "gpb_emcee_run": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_u64, c_u64, C.c_double, C.c_int, VP, VP, C.c_double,
                                 C.c_double, VP, VP, VP]),
     "gpb_chain_supported": (C.c_int, [VP, C.c_int]),
+    "gpb_chain_like_set": (C.c_int, [VP, C.c_int, VP, VP, VP]),
     "gpb_chain_logpost": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, C.c_double, C.c_double]),
     "gpb_chain_emcee_run": (C.c_int, [VP, C.c_int, VP, VP, c_i64, c_i64, c_u64, c_u64, C.c_double, C.c_int, VP, VP,
                                       C.c_double, C.c_double, VP, VP, VP]),

@@ -158,6 +158,7 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     // whatever was installed for the previous GPs (observable transform sized [old P][M], likelihood block, low-rank
     // factors, parameter map) does not describe the new ones: it has to be set again
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
+    ++ctx->like_epoch;                                 // (a coupled chain likelihood built on this context is stale)
     ctx->M = 0;
     ctx->A.release(); ctx->mu.release(); ctx->scale.release(); ctx->C0.release(); ctx->yexp.release();
     ctx->Cexp.release(); ctx->lr_R.release(); ctx->lr_v0.release(); ctx->pmap_int.release(); ctx->pmap_tab.release();
@@ -601,6 +602,7 @@ extern "C" int gpb_emu_set_transform(gpb_ctx* ctx, int mode, int64_t M, const do
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t P = ctx->P;
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
+    ++ctx->like_epoch;                                 // (a coupled chain likelihood built on this context is stale)
     int rc;
     if ((rc = ctx_replace(ctx, ctx->A, P * M))) return rc;
     if ((rc = ctx_replace(ctx, ctx->mu, M))) return rc;
@@ -865,6 +867,7 @@ extern "C" int gpb_like_set(gpb_ctx* ctx, const double* yexp_host, const double*
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t M = ctx->M;
     ctx->have_like = ctx->lr_ok = false;
+    ++ctx->like_epoch;
     int rc;
     if ((rc = ctx_replace(ctx, ctx->yexp, M))) return rc;
     if ((rc = ctx_replace(ctx, ctx->Cexp, M * M))) return rc;

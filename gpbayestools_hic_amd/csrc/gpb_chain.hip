@@ -58,6 +58,7 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
                const double* hi_dev, double outside, double inside_const, int premarked, const int* cmpv) {
     gpb_ctx* c0 = ctxs[0];
     int rc;
+    if ((rc = coupling_check(ctxs, E, "gpb_chain_logpost"))) return rc;
     for (int e = 0; e < E; ++e)
         if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
     if ((rc = ensure_lr_blocks(c0, E))) return rc;
@@ -69,7 +70,9 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
     // (2) V = L^-1 K*^T with the fused sum of squares: ONE launch for each run of emulators whose designs pad to the same
     //     Np (the reference's analyses: nine emulators on one design) instead of one partly filled launch per emulator;
     // (3) the block log-likelihoods, added up in emuList order: one launch that walks the emulators (k_loglike_lowrank_multi)
-    //     when every block takes the low-rank kernel, else one launch per emulator.
+    //     when every block takes the low-rank kernel, else one launch per emulator.  A chain whose experimental covariance
+    //     couples its emulators (gpb_chain_like_set) has no blocks to add: the GPs' sums per emulator (k_finalize), then
+    //     one launch of the joint kernel (gpb_coupled.hip).
     const double* Xg[MAX_CHAIN_CTX];
     gpb_ctx* mapped[MAX_CHAIN_CTX];
     int nmapped = 0;
@@ -103,6 +106,11 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
         if ((rc = launch_vsq(ctxs + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
         e += n;
     }
+    if (coupling_installed(c0)) {
+        for (int e = 0; e < E; ++e)
+            if ((rc = launch_finalize(ctxs[e], W, true))) { c0->err = ctxs[e]->err; return rc; }
+        return launch_loglike_coupled(ctxs, E, W, ll_dev, cmpv, inside_const);
+    }
     bool taken;
     if ((rc = launch_loglike_lowrank_chain(ctxs, E, W, ll_dev, cmpv, inside_const, &taken)) || taken) return rc;
     for (int e = 0; e < E; ++e) {
@@ -123,6 +131,11 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
 int chain_eval(gpb_ctx* const* ctxs, int E, const double* X, int64_t W, double* lp, const double* lo, const double* hi,
                double outside, double inside_const) {
     if (gpb_chain_supported(ctxs, E) == 1) return gpb_chain_logpost(ctxs, E, X, W, lp, lo, hi, outside, inside_const);
+    if (coupling_installed(ctxs[0])) {                 // the sum of the emulators' blocks below is not this chain's likelihood
+        gpb_ctx* ctx = ctxs[0];
+        GPB_FAIL(GPB_E_STATE, "gpb: a coupled chain likelihood is installed (gpb_chain_like_set), but the contexts no longer "
+                              "take the compacted chain call");
+    }
     // The sum of the emulators' block likelihoods in emuList order (accumulate from the second on), the prior box over the
     // ORIGINAL parameters with the last: gpb_logpost, or gpb_loglike + gpb_box_finish where the last emulator's GPs see mapped
     // parameters.  Those go into the emulator's own staging buffer, as in chain_rows (sized here, on the caller's device).

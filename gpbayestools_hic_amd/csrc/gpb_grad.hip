@@ -540,6 +540,36 @@ extern "C" int gpb_chain_logpost_grad(gpb_ctx* const* ctxs, int E, const double*
     }
     // the log-posterior, as every sampler evaluates it
     if ((rc = chain_eval(ctxs, E, Xs_dev, W, ll_dev, lo_dev, hi_dev, outside_value, inside_const))) return rc;
+    // A coupled chain (gpb_chain_like_set; chain_eval has checked the coupling): the likelihood's weights of all emulators come
+    // from ONE factorisation per row, so first every emulator's GP derivatives, means and variances, then the joint launch, then
+    // the folds in emuList order.
+    if (coupling_installed(c0)) {
+        double *wmu[MAX_CHAIN_CTX], *wv[MAX_CHAIN_CTX];
+        for (int e = 0; e < E; ++e) {
+            gpb_ctx* c = ctxs[e];
+            GradWs& g = ws[e];
+            const double* Xg = Xs_dev;
+            if (c->pmap_d_in > 0) {
+                if ((rc = gpb_param_map(c, Xs_dev, W, g.xg)) || (rc = launch_pmap_jac(c, Xs_dev, W, g.jm))) { c0->err = c->err; return rc; }
+                Xg = g.xg;
+            }
+            if ((rc = gp_grad_rows(c, Xg, W, true, true, g.bt, g.dm, g.dv))) { c0->err = c->err; return rc; }
+            wmu[e] = g.wmu;
+            wv[e] = g.wv;
+        }
+        if ((rc = launch_like_w_coupled(ctxs, E, W, wmu, wv))) return rc;
+        const int64_t n = W * nd;
+        for (int e = 0; e < E; ++e) {
+            gpb_ctx* c = ctxs[e];
+            GradWs& g = ws[e];
+            hipLaunchKernelGGL(k_grad_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, g.wmu, g.wv, g.dm, g.dv,
+                               (int)c->P, (int)c->d, c->pmap_d_in > 0 ? g.jm : nullptr, (int)nd, W, grad_dev, e > 0 ? 1 : 0);
+        }
+        hipLaunchKernelGGL(k_grad_finish, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, c0->stream, Xs_dev, W, (int)nd, lo_dev,
+                           hi_dev, ll_dev, grad_dev);
+        GPB_HIP(hipGetLastError());
+        return 0;
+    }
     // the gradient, emulator after emulator (fp64 throughout), added up in emuList order
     for (int e = 0; e < E; ++e) {
         gpb_ctx* c = ctxs[e];

@@ -238,6 +238,20 @@ struct gpb_ctx {
     bool force_generic_mvn = false; // test hook: bypass the register-resident MVN fast path
     int fuse_finalize = 1;          // block log-likelihood kernels sum the predict partials themselves (P <= 32)
     int64_t mvn_wg_switch = 768;   // batches up to this size use one workgroup per walker (32 < M <= 64)
+    // ---- coupled chain likelihood (gpb_coupled.hip; coupled_setup.h has the algebra) ----------------------
+    // like_epoch: counts the replacements of this context's transform / likelihood block (gpb_gp_set, gpb_emu_set_transform,
+    // gpb_like_set).  cpl: the joint tables of the chain whose FIRST context this is (gpb_chain_like_set) — the member
+    // contexts in emuList order with their epochs at set time: a member whose epoch has moved on makes the coupling stale.
+    uint64_t like_epoch = 0;
+    struct Coupling {
+        bool on = false;
+        int PT = 0, PP = 0;            // GPs of the chain, and the kernels' padded order (64 or 128)
+        std::vector<gpb_ctx*> members;
+        std::vector<uint64_t> epochs;
+        double cperp = 0.0, logdet0 = 0.0;
+        const double *RT = nullptr, *v0 = nullptr;     // pieces of cpl_tab (CoupledWs)
+    } cpl;
+    gpb::DevBuf<double> cpl_tab;
 
     // ---- parameterTrafoPCA input map (gpb_pmap.hip) ------------------------------------
     gpb::DevBuf<int> pmap_int;       // col_src[d_out] | group descriptors [G][6]
@@ -526,6 +540,14 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
 // sequence of gpb_param_map / gpb_loglike / gpb_box_finish / gpb_logpost
 int chain_eval(gpb_ctx* const* ctxs, int E, const double* X, int64_t W, double* lp, const double* lo, const double* hi,
                double outside, double inside_const);
+// ---- a chain whose experimental covariance couples its emulators (gpb_coupled.hip) -------------------------
+inline bool coupling_installed(const gpb_ctx* c0) { return c0->cpl.on; }
+// GPB_E_STATE (message on ctxs[0]) when ctxs[0] holds a coupling that is stale or was set for another list of contexts
+int coupling_check(gpb_ctx* const* ctxs, int E, const char* who);
+// step (3) of chain_rows for a coupled chain, from the emulators' finalised mean_pc / var_pc: ll[cmp[4 + w]] = r + inside_const
+int launch_loglike_coupled(gpb_ctx* const* ctxs, int E, int64_t W, double* ll_dev, const int* cmpv, double inside_const);
+// the gradient's weights of all W rows: -t and 1/2 t^2 - 1/2 diag(R^T S^-1 R) into the emulators' wmu / wv [W][P_e]
+int launch_like_w_coupled(gpb_ctx* const* ctxs, int E, int64_t W, double* const* wmu, double* const* wv);
 // test hooks
 int launch_test_gemm(gpb_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B,
                      double* C, int b_trans);

@@ -191,6 +191,16 @@ struct SobolWs {
     }
 };
 
+// cpl_tab (gpb_coupled.hip): the joint tables of a coupled chain likelihood, R^T [PP][PP] (row p: column p of R, zero beyond
+// the chain's PT GPs) | v0 [PP]
+struct CoupledWs {
+    double *RT, *v0;
+    void lay(Carver<double>& c, int64_t PP) {
+        RT = c.take<double>(PP * PP, 2);
+        v0 = c.take<double>(PP, 2);
+    }
+};
+
 // gbuf (gpb_grad.hip), the pieces of one gradient evaluation of W rows, 32 doubles the granule: beta^T [P][Wld][Np] | dmean,
 // dvar [W][P][d] | the likelihood's weights of mean and variance [W][P] | mapped rows [W][d] | the map's Jacobian [W][d][din] |
 // the likelihood's global scratch | staged input rows | staged results

@@ -69,6 +69,7 @@ class GPEngine:
         elif stream is not None:
             self._ck(self.lib.gpb_ctx_set_stream(self.h, nat.VP(int(stream))))
         self.N = self.d = self.P = self.M = 0
+        self.mode = None                         # the transform's mode (set_transform)
         # option key 51 (csrc/gpb_sliced.hip): the context starts at PREDICT_SLICED_DEFAULT (seven int8 digit planes); the
         # GPB_PREDICT_SLICED environment hook gives every engine of the process another value (0: the fp64 kernel, 1: six planes)
         # — the whole test suite runs under it this way
@@ -489,6 +490,7 @@ class GPEngine:
     def set_transform(self, mode, mu, A=None, cov_trunc=None, scale=None):
         mu = nat.f64(mu)
         self.M = mu.shape[0]
+        self.mode = int(mode)
         A = None if A is None else nat.f64(A)
         cov_trunc = None if cov_trunc is None else nat.f64(cov_trunc)
         scale = None if scale is None else nat.f64(scale)

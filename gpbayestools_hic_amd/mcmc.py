@@ -7,7 +7,9 @@ compute_log_likelihood_for_chain`.
 Every emulator prediction, covariance assembly, Cholesky and quadratic form runs in the HIP
 engine.  When all emulators in `emuList` are this package's `Emulator`, a log-probability call
 is E fused `gpb_loglike` block evaluations plus one box kernel; rows never leave HBM between
-them.  Foreign emulators (anything with the reference's predict protocol) go through
+them.  An experimental covariance that couples different emulators (correlated systematics,
+`Chain.set_systematics`) is evaluated by the coupled kernel from the same per-GP means and
+variances (gpb_chain_like_set).  Foreign emulators (anything with the reference's predict protocol) go through
 `_predict` on the host and the generic batched device MVN (`gpb_mvn_loglike`).
 """
 import logging
@@ -106,6 +108,7 @@ class Chain:
         errs = np.nan_to_num(np.abs(np.array([data[k]["obs"][1] for k in data.keys()])))
         cov = np.zeros((vals.shape[1], vals.shape[1]))
         np.fill_diagonal(cov, errs.flatten() ** 2)       # (nobs x nobs whatever the number of events, as the reference fills it)
+        self._stat_errors = errs.flatten()[:cov.shape[0]].copy()      # set_systematics' default statistical errors
         return vals, cov
 
     def state_digest_cached(self):
@@ -212,29 +215,86 @@ class Chain:
     def _native(self):
         return len(self.emuList) > 0 and all(isinstance(e, Emulator) for e in self.emuList)
 
+    def set_systematics(self, sources, stat=None):
+        """Correlated systematic uncertainties: sources [K, nobs], row k the fully correlated one-sigma shift of source k over
+        the observables of all emulators (a normalisation or luminosity uncertainty: a fraction of expdata; zero where the
+        source does not act).  Sets expdata_cov = diag(stat^2) + sum_k s_k s_k^T, with stat [nobs] defaulting to the errors
+        read from the experiment file (the square roots of the present diagonal).  Returns self."""
+        S = np.atleast_2d(np.asarray(sources, dtype=np.float64))
+        if S.ndim != 2 or S.shape[1] != self.nobs:
+            raise ValueError("set_systematics: sources must be [K, %d], got %s" % (self.nobs, np.shape(sources)))
+        if stat is None:                         # (a chain unpickled from before this method: the present diagonal's roots)
+            stat = getattr(self, "_stat_errors", None)
+            stat = np.sqrt(np.diag(self.expdata_cov)) if stat is None else stat
+        stat = np.asarray(stat, dtype=np.float64).reshape(-1)
+        if stat.shape[0] != self.nobs:
+            raise ValueError("set_systematics: stat must hold %d errors" % self.nobs)
+        cov = np.zeros((self.nobs, self.nobs))
+        np.fill_diagonal(cov, stat ** 2)
+        for s in S:
+            cov += np.outer(s, s)
+        self.expdata_cov = cov
+        return self
+
+    _coupled = False                             # expdata_cov has entries that couple different emulators ...
+    _coupled_why = None                          # ... and why the device's coupled likelihood does not serve them (None: it does)
+
     def _prepare_blocks(self):
-        """Hand every emulator its slice of the experimental data.  The fused path needs the
-        experimental covariance to be block-diagonal over the emulators (it is diagonal in the
-        reference, src/mcmc.py:320-322)."""
-        # (engines by their serial numbers: the id() of a closed engine can come back with the next one created)
-        sig = (id(self.expdata), id(self.expdata_cov), tuple(id(e) for e in self.emuList),
-               tuple(getattr(e._engine, "serial", None) for e in self.emuList))
-        if sig == self._like_sig:
+        """Hand every emulator its slice of the experimental data (gpb_chain_like_set).  An experimental covariance that
+        couples different emulators — the reference adds whatever expdata_cov holds, src/mcmc.py:288-293 — installs the
+        coupled likelihood in the first emulator's context when it applies (every emulator in PCA mode, at most 128 GPs
+        and 2048 observables in all, the compacted chain call available, covariance positive definite); when it does not,
+        log_posterior / log_likelihood take the generic route (_predict + the dense device MVN) and the C-driven loops
+        raise NotImplementedError.  A block-diagonal covariance takes the block path as before."""
+        import ctypes
+        from . import _native as nat
+        # (engines by their serial numbers: the id() of a closed engine can come back with the next one created; the
+        # experiment's arrays and the emulators by identity, and the signature keeps them alive: the id() of a dropped
+        # covariance can come back with the next one assigned, block-diagonal then, coupled now)
+        prev = self._like_sig
+        serials = tuple(getattr(e._engine, "serial", None) for e in self.emuList)
+        if (prev is not None and prev[0] is self.expdata and prev[1] is self.expdata_cov and len(prev[2]) == len(self.emuList)
+                and all(a is b for a, b in zip(prev[2], self.emuList)) and prev[3] == serials):
             return
+        engs = [emu._engine_ready() for emu in self.emuList]
+        nobs = sum(emu.nobs for emu in self.emuList)
+        if nobs != self.nobs:
+            raise ValueError("emulators provide %d observables, experiment has %d" % (nobs, self.nobs))
+        cov = nat.f64(self.expdata_cov)
+        yexp = nat.f64(self.expdata[0])
+        if cov.shape != (nobs, nobs):
+            raise ValueError("experimental covariance is %s, the emulators provide %d observables" % (cov.shape, nobs))
+        mask = np.zeros(cov.shape, dtype=bool)
         i0 = 0
-        mask = np.zeros_like(self.expdata_cov, dtype=bool)
-        for emu in self.emuList:
-            k = emu.nobs
-            eng = emu._engine_ready()
-            eng.set_likelihood(self.expdata[0, i0:i0 + k], self.expdata_cov[i0:i0 + k, i0:i0 + k])
-            mask[i0:i0 + k, i0:i0 + k] = True
-            i0 += k
-        if i0 != self.nobs:
-            raise ValueError("emulators provide %d observables, experiment has %d" % (i0, self.nobs))
-        if np.any(self.expdata_cov[~mask] != 0.0):
-            raise ValueError("experimental covariance couples different emulators; "
-                             "the fused likelihood needs it block-diagonal")
-        self._like_sig = (sig[0], sig[1], sig[2], tuple(e._engine.serial for e in self.emuList))
+        for emu, eng in zip(self.emuList, engs):
+            assert eng.M == emu.nobs
+            mask[i0:i0 + emu.nobs, i0:i0 + emu.nobs] = True
+            i0 += emu.nobs
+        applies = ctypes.c_int(0)
+        arr = (nat.C.c_void_p * len(engs))(*[g.h for g in engs])
+        engs[0]._ck(engs[0].lib.gpb_chain_like_set(arr, len(engs), nat.ptr(yexp), nat.ptr(cov), ctypes.byref(applies)))
+        self._coupled = bool(np.any(cov[~mask] != 0.0))
+        self._coupled_why = None
+        if self._coupled and not applies.value:
+            from .engine import MODE_PCA
+            ngp = sum(g.P for g in engs)
+            if any(g.mode != MODE_PCA for g in engs):
+                self._coupled_why = "an emulator is not in PCA mode"
+            elif ngp > 128 or nobs > 2048:
+                self._coupled_why = "%d GPs and %d observables exceed the limits of 128 and 2048" % (ngp, nobs)
+            elif engs[0].lib.gpb_chain_supported(arr, len(engs)) != 1:
+                self._coupled_why = "the emulators do not take the compacted chain call"
+            else:
+                self._coupled_why = ("experimental + truncation covariance is not positive definite, or an emulator's "
+                                     "transform is rank deficient")
+        self._like_sig = (self.expdata, self.expdata_cov, tuple(self.emuList), tuple(e._engine.serial for e in self.emuList))
+
+    def _coupled_fallback(self):
+        """True when expdata_cov couples the emulators and the device's coupled likelihood does not apply (the dense route)"""
+        if not self._native():
+            return False
+        self._prepare_blocks()
+        return self._coupled and self._coupled_why is not None
 
     inside_const = EXTRA_STD_CONST               # what the reference adds to every row inside the box
 
@@ -248,13 +308,21 @@ class Chain:
             self._box_key = key
         return self._box_dev
 
-    use_chain_call = True                        # False: sequence the emulators from Python (A/B tests)
+    # False: sequence the emulators from Python (A/B tests).  The per-emulator sequence is a sum of blocks and has no coupled
+    # counterpart: with a coupled experimental covariance the C chain call is always used, whatever this says.
+    use_chain_call = True
 
     def _contexts(self):
         """(engines, ctypes array of their contexts, count) of emuList, ready for a C call that takes the chain: every
-        emulator has its block of the experimental data, a fitted engine, and enqueues on torch's current stream."""
+        emulator has its block of the experimental data, a fitted engine, and enqueues on torch's current stream.
+        NotImplementedError when expdata_cov couples the emulators and the device's coupled likelihood does not apply: the C
+        calls would evaluate another likelihood."""
         from . import _native as nat
         self._prepare_blocks()
+        if self._coupled and self._coupled_why is not None:
+            raise NotImplementedError("the experimental covariance couples different emulators and the device's coupled "
+                                      "likelihood does not apply (%s): only log_posterior / log_likelihood evaluate it, "
+                                      "through the dense route" % self._coupled_why)
         engs = [e._engine_ready() for e in self.emuList]
         for g in engs:
             g._need_data()
@@ -265,7 +333,10 @@ class Chain:
         """(engines, ctypes array of their contexts) when the C ABI can evaluate the whole chain in one call
         (gpb_chain_logpost / gpb_chain_emcee_run: rows outside the prior box skipped, one emulator after the other on
         one stream), else None."""
-        if not (self.use_chain_call and self._native()):
+        if not self._native():
+            return None
+        self._prepare_blocks()
+        if not (self.use_chain_call or self._coupled):
             return None
         engs, arr, n = self._contexts()
         return (engs, arr) if engs[0].lib.gpb_chain_supported(arr, n) == 1 else None
@@ -297,6 +368,9 @@ class Chain:
             e0._ck(e0.lib.gpb_chain_logpost(arr, len(engs), nat.ptr(X_dev), X_dev.shape[0], nat.ptr(out), nat.ptr(lo_dev),
                                             nat.ptr(hi_dev), float(outside), EXTRA_STD_CONST))
             return out
+        if self._coupled:                            # (the blocks below do not add up to a coupled likelihood)
+            raise NotImplementedError("log_prob_device: the experimental covariance couples different emulators and the "
+                                      "emulators do not take the compacted chain call")
         for i, emu in enumerate(self.emuList):      # all engines enqueue on torch's current stream: ordered
             eng = emu._engine_ready()
             mapped = getattr(emu, "parameterTrafoPCA_", False)
@@ -312,7 +386,9 @@ class Chain:
 
     def _log_prob(self, X, outside):
         X = np.array(X, ndmin=2, dtype=np.float64)
-        if self._native():
+        # (a coupled experimental covariance that the device's coupled likelihood does not serve: the generic path below,
+        # which adds the whole expdata_cov to the emulators' block-diagonal covariance as the reference does)
+        if self._native() and not self._coupled_fallback():
             import torch
             dev = torch.device("cuda", self.device)
             # long inputs (a stored chain, src/mcmc.py:729-749) go through in slabs: the K*^T workspace is

@@ -504,6 +504,26 @@ GPB_API int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev, do
                         uint64_t seed, uint64_t step0, double a, int randomize_split,
                         const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
                         double* chain_dev, double* lpchain_dev, int64_t* naccept_dev);
+/* gpb_chain_like_set <- the experiment of a whole chain: expdata[0, :], expdata_cov[:, :] over the MT = sum M_e observables
+ *   of ctxs[0..E) in emuList order, where expdata_cov may couple the emulators (a shared normalisation uncertainty, errors
+ *   correlated across emulators): the reference adds whatever expdata_cov holds and factorises the full matrix per row
+ *   (src/mcmc.py:288-293).  Every emulator's own diagonal block is installed through gpb_like_set, so all that reads a
+ *   block per emulator keeps working.  When cov_exp_host has a non-zero entry outside the blocks, the joint tables of the
+ *   coupled likelihood are built in ctxs[0] (host, O(MT^3) once): the covariance of a row is C0 + A^T diag(g) A with
+ *   C0 = blockdiag(C_trunc,e) + C_exp and A = blockdiag(A_e), so a row costs one PT x PT Cholesky, PT = sum P_e GPs.
+ *   *applies_host = 1: the coupling is installed and gpb_chain_logpost, gpb_chain_emcee_run, gpb_chain_smc_reweight /
+ *   gpb_chain_smc_move, gpb_chain_ptlmc_run and gpb_chain_logpost_grad evaluate the coupled likelihood for exactly this
+ *   list of contexts (rows whose S is not positive definite: NaN, counted with ctxs[0]).  That needs every emulator in
+ *   PCA mode, PT <= 128, MT <= 2048, gpb_chain_supported == 1, C0 positive definite and A of full rank.
+ *   *applies_host = 0 (return value still 0): the matrix is block-diagonal (the chain's block path, as before), or one of
+ *   those conditions fails — then nothing is installed and the caller evaluates the dense matrix itself
+ *   (gpb_emu_predict + gpb_mvn_loglike).  cov_exp_host = NULL clears a coupling and leaves the blocks.
+ *   A later gpb_like_set, gpb_emu_set_transform or gpb_gp_set on any member makes the coupling stale: the chain calls then
+ *   fail with GPB_E_STATE until gpb_chain_like_set is called again; they never evaluate the block-diagonal likelihood in
+ *   its place.  The member contexts must outlive the coupling.  GPB_E_ARG: a null pointer or context, E outside 1 .. 64,
+ *   contexts on different devices or streams.  Synchronises. */
+GPB_API int gpb_chain_like_set(gpb_ctx* const* ctxs, int E, const double* yexp_host /*[MT]*/,
+                       const double* cov_exp_host /*[MT,MT], or NULL: clear the coupling*/, int* applies_host);
 /* gpb_chain_logpost_grad <- Chain.log_posterior / log_likelihood together with the gradient in the chain's parameters,
  *   the (lp, grad) tuple the reference's PTLMC sampler takes from its logpostfunc (src/mcmc.py:446-453, 499-528, 545-569).
  *   ll_dev receives bit for bit what gpb_chain_logpost writes (or, for contexts it does not accept, what the per-emulator
