@@ -8,7 +8,8 @@ src/mcmc.py log-posterior loop): hand-written HIP kernels for gfx950 behind a C 
 __version__ = "0.1.0"
 
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
-           "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals"]
+           "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals", "PosteriorClusters",
+           "posterior_clusters"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -31,6 +32,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
         import importlib
         mod = importlib.import_module(".marginals", __name__)
         return mod if name == "marginals" else mod.PosteriorMarginals
+    if name in ("PosteriorClusters", "posterior_clusters"):
+        from . import clusters
+        return getattr(clusters, name)
     if name == "WalkerSharding":
         from .dist import WalkerSharding
         return WalkerSharding

@@ -66,6 +66,8 @@ BOUNDARY = {
     "gpb_mcmc_diag": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_double, C.c_int, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_marginals": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, VP, c_i64, VP, C.c_double, C.c_int,
                                       VP, VP, VP]),
+    "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                   VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_like_set": (C.c_int, [VP, VP, VP]),
     "gpb_loglike": (C.c_int, [VP, VP, c_i64, C.c_int, VP, C.c_int, VP]),
     "gpb_logpost": (C.c_int, [VP, VP, c_i64, VP, C.c_int, VP, VP, C.c_double, C.c_double]),

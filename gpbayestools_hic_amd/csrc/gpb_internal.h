@@ -155,6 +155,7 @@ struct gpb_ctx {
     // of a sample group; marg_ws_bytes caps the last two (option key 52 lowers it, in the debug build only: the grouping's test)
     gpb::DevBuf<int64_t> marg_ws;
     int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
+    gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

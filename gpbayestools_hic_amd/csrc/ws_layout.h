@@ -156,6 +156,45 @@ struct MargWs {
     }
 };
 
+// kmeans_ws (gpb_chain_kmeans), 8-byte units.  A run that is zeroed at the start of a call (state0, state_bytes): counters [4] |
+// centres [R][k][d] | shift [R] | integer sums acc [R][k][d], wq [R][k], cnt [R][k], iner [R] | seed rows [R][k] | changed, done,
+// conv, niter, fi [R] each (int, back to back).  Behind it: mean | scale [2 d] | moment sums [5 d + 1] and their workgroup
+// partials [nb][5 d + 1] | with seeding the uniforms [R][k], the range sums [R][nb], the chosen range [R] (int) and (sum in
+// front, target) [R][2] | effective weights [S] | one label byte per (restart, row).
+struct KmeansWs {
+    int64_t *state0, state_bytes;
+    int64_t *counters, *acc, *wq, *cnt, *iner, *seed;
+    double *cen, *shift, *ms, *mom, *part, *u, *bs, *selv, *weff;
+    int *changed, *done, *conv, *niter, *fi, *selb;
+    unsigned char* lab;
+    void lay(Carver<int64_t>& c, int64_t S, int64_t R, int64_t k, int64_t d, int64_t nb, int seeding) {
+        const int64_t at0 = c.total();
+        state0 = counters = c.take<int64_t>(4);
+        cen = c.take<double>(R * k * d);
+        shift = c.take<double>(R);
+        acc = c.take<int64_t>(R * k * d);
+        wq = c.take<int64_t>(R * k);
+        cnt = c.take<int64_t>(R * k);
+        iner = c.take<int64_t>(R);
+        seed = c.take<int64_t>(R * k);
+        changed = c.take<int>(5 * R);
+        done = changed ? changed + R : nullptr;
+        conv = changed ? changed + 2 * R : nullptr;
+        niter = changed ? changed + 3 * R : nullptr;
+        fi = changed ? changed + 4 * R : nullptr;
+        state_bytes = 8 * (c.total() - at0);
+        ms = c.take<double>(2 * d);
+        mom = c.take<double>(5 * d + 1);
+        part = c.take<double>(nb * (5 * d + 1));
+        u = c.take<double>(seeding ? R * k : 0);
+        bs = c.take<double>(seeding ? R * nb : 0);
+        selb = c.take<int>(seeding ? R : 0);
+        selv = c.take<double>(seeding ? 2 * R : 0);
+        weff = c.take<double>(S);
+        lab = c.take<unsigned char>(R * S);
+    }
+};
+
 // sl_scale (gpb_sliced.hip): row scales [P][Np128] | column scales [P] | row exponents [P][Np128] (int)
 struct SlScale {
     double *rowscale, *colscale;

@@ -722,6 +722,75 @@ class GPEngine:
                                               nat.ptr(out.get("h2")), nat.ptr(out.get("outside"))))
         return out
 
+    KMEANS_MAX_K, KMEANS_MAX_RESTARTS = 32, 16
+
+    def chain_kmeans(self, x_dev, layout="steps", k=10, n_init=10, init=None, u=None, weights=None, max_iter=300, tol=1e-4,
+                     standardize=True, return_labels=False):
+        """Weighted k-means of the rows of a chain that lies on the device (gpb_chain_kmeans), n_init restarts in lock-step:
+        x_dev and layout as chain_marginals takes them (a flat [S, ndim] particle set: x_dev[:, None, :]; ndim <= 64).  Exactly
+        one of init [n_init, k, ndim] (the starting centres, in the chain's units) and u [n_init, k] (uniforms in [0, 1) that
+        drive the k-means++ seeding) is given; weights [nsteps] (numpy or torch cuda, non-negative; one walker only).  The rows
+        are standardised on the fly (standardize=False: taken as they are); a row with a non-finite coordinate is skipped.
+        Returns a dict of numpy arrays: "centers" [n_init, k, ndim] (the chain's units), "inertia", "n_iter", "converged"
+        [n_init], "size" (rows of positive weight, int64) and "wsum" [n_init, k], "mean", "scale" [ndim], "seed_index"
+        [n_init, k] (int64; -1 with init), "best", "n_skipped" (ints) and, with return_labels, "labels" [S] (a torch int32
+        cuda tensor: the best restart's labels in row order — the outer axis of the memory layout first —, -1 for a skipped
+        row).  Integer accumulation: equal inputs give equal bits, and a restart's result does not depend on the restarts that
+        share the call.  The engine lends its device and stream only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        if layout not in ("steps", "walkers"):
+            raise ValueError("layout: 'steps' ([nsteps, nwalkers, ndim]) or 'walkers' ([nwalkers, nsteps, ndim])")
+        if not _is_torch(x_dev) or x_dev.dim() != 3:
+            raise ValueError("x_dev: expected a three-dimensional torch tensor")
+        if not x_dev.is_cuda or x_dev.device.index != self.device or str(x_dev.dtype) != "torch.float64":
+            raise ValueError("x_dev: expected a torch.float64 tensor on cuda:%d" % self.device)
+        ts, tw = (0, 1) if layout == "steps" else (1, 0)
+        n, nw, d = int(x_dev.shape[ts]), int(x_dev.shape[tw]), int(x_dev.shape[2])
+        if d > 1 and x_dev.stride(2) != 1:
+            raise ValueError("x_dev: expected unit stride along the parameters")
+        ss, ws = int(x_dev.stride(ts)), int(x_dev.stride(tw))
+        # an axis of extent 1 has no meaningful stride: give it the one of a contiguous array
+        if nw == 1 and layout == "steps":
+            ws = d
+        if n == 1 and layout == "walkers":
+            ss = d
+        if nw == 1 and layout == "walkers":
+            ws = max(ws, ss * n)
+        if n == 1 and layout == "steps":
+            ss = max(ss, ws * nw)
+        k, R = int(k), int(n_init)
+        if (init is None) == (u is None):
+            raise ValueError("exactly one of init [n_init, k, ndim] and u [n_init, k]")
+        if init is not None:
+            init = nat.f64(init)
+            if init.shape != (R, k, d):
+                raise ValueError("init: expected [%d, %d, %d]" % (R, k, d))
+        else:
+            u = nat.f64(u)
+            if u.shape != (R, k):
+                raise ValueError("u: expected [%d, %d]" % (R, k))
+        if weights is not None:
+            if not _is_torch(weights):
+                weights = torch.as_tensor(nat.f64(weights).reshape(-1), device=dev)
+            weights = self._dev(weights, (n,), "weights", contiguous=False)
+        Rk = (max(R, 0), max(k, 0))
+        out = {"centers": np.empty(Rk + (d,)), "inertia": np.empty(Rk[0]), "n_iter": np.empty(Rk[0], dtype=np.int32),
+               "converged": np.empty(Rk[0], dtype=np.int32), "size": np.empty(Rk, dtype=np.int64), "wsum": np.empty(Rk),
+               "mean": np.empty(d), "scale": np.empty(d), "seed_index": np.empty(Rk, dtype=np.int64)}
+        best, nskip = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+        labels = torch.empty(n * nw, dtype=torch.int32, device=dev) if return_labels else None
+        self._ck(self.lib.gpb_chain_kmeans(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, nat.ptr(weights), k, R, int(max_iter), float(tol),
+                                           1 if standardize else 0, nat.ptr(init), nat.ptr(u), nat.ptr(out["centers"]),
+                                           nat.ptr(out["inertia"]), nat.ptr(out["n_iter"]), nat.ptr(out["converged"]),
+                                           nat.ptr(out["size"]), nat.ptr(out["wsum"]), nat.ptr(out["mean"]), nat.ptr(out["scale"]),
+                                           nat.ptr(out["seed_index"]), nat.ptr(best), nat.ptr(nskip), nat.ptr(labels)))
+        out["best"], out["n_skipped"] = int(best[0]), int(nskip[0])
+        if return_labels:
+            out["labels"] = labels
+        return out
+
     def emu_predict_jac(self, Xs):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
         the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""

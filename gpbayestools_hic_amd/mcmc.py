@@ -579,6 +579,34 @@ class Chain:
         xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
         return marginals(xd[:, discard::thin], layout="walkers", **kw)
 
+    def posterior_clusters(self, chain=None, discard=0, thin=1, n_clusters=10, n_init=10, **kw):
+        """Representative parameter sets of the posterior: PosteriorClusters (clusters.py) of a stored [nwalkers, nsteps, ndim]
+        array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first
+        `discard` steps and thinned by `thin`, or of a flat [S, ndim] particle set (the `chain` of a pocoMC / run_SMC pickle,
+        with kw weights=, logl= and num_samples=; discard and thin do not apply).  k-means of the standardised rows on the
+        device (gpb_chain_kmeans; the array is uploaded in its own layout and read through its strides) — what
+        examples/generate_posterior_clusters.py computes with scikit-learn; kw (init, seed, max_iter, tol, standardize,
+        return_labels) as clusters.posterior_clusters takes them.  `.savetxt()` writes the reference's cluster_centers.txt."""
+        from .clusters import posterior_clusters
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        x = np.asarray(chain, dtype=np.float64)
+        if x.ndim not in (2, 3):
+            raise ValueError("posterior_clusters: chain must be [nwalkers, nsteps, ndim] or [S, ndim], got %s" % (np.shape(chain),))
+        kw.setdefault("names", list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[-1] else None)
+        kw.setdefault("device", self.device or 0)
+        if x.ndim == 2:
+            return posterior_clusters(x, n_clusters, n_init, **kw)
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+            raise ValueError("posterior_clusters: discard >= 0, thin >= 1 and at least one step must remain")
+        import torch
+        xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", kw["device"]))
+        return posterior_clusters(xd[:, discard::thin], n_clusters, n_init, layout="walkers", **kw)
+
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a

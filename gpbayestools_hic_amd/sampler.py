@@ -285,6 +285,16 @@ class StretchSampler:
         kw.setdefault("names", list(names) if names else None)
         return marginals(x, layout="steps", **kw)
 
+    def clusters(self, discard=0, thin=1, **kw):
+        """PosteriorClusters of chain[discard::thin] (clusters.py): k-means of the standardised samples, computed on the stored
+        chain where it lies on the device, through its strides (gpb_chain_kmeans); kw (n_clusters, n_init, init, seed,
+        max_iter, tol, standardize, return_labels) as clusters.posterior_clusters takes them."""
+        from .clusters import posterior_clusters
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return posterior_clusters(x, layout="steps", **kw)
+
 
 class _HostLogProb:
     """minimal chain-like object around a host callable f(X[w, ndim]) -> lp[w]"""

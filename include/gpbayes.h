@@ -404,6 +404,57 @@ GPB_API int gpb_chain_marginals(gpb_ctx* ctx, const double* x_dev, int64_t nstep
                         const double* w_dev /*[nsteps] or NULL*/, double wscale, int on_device,
                         int64_t* h1 /*[d,B] or NULL*/, int64_t* h2 /*[npairs,B,B] or NULL*/, int64_t* outside /*[d] or NULL*/);
 
+/* ---- posterior clusters of a resident chain --------------------------------------------------------------------------------- *
+ * gpb_chain_kmeans <- examples/generate_posterior_clusters.py: `StandardScaler().fit_transform(chain)`, `KMeans(n_clusters,
+ *                     n_init=10).fit(...)`, `scaler.inverse_transform(kmeans.cluster_centers_)` — weighted k-means of the rows of a
+ *                     chain that already lies in device memory, R restarts in lock-step: every pass reads a row once per group of
+ *                     restarts whose centres fit a workgroup's LDS (all of them at k d <= 200 or so) and serves all their centres.
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  x_dev, nsteps, nwalkers, d and the
+ *   strides exactly as gpb_chain_marginals reads them (the same aliasing rule; a flat [S, d] set is nsteps = S, nwalkers = 1); the
+ *   rows are counted outer axis first (the axis whose stride spans the other).  w_dev [nsteps] or NULL: non-negative weights,
+ *   nwalkers == 1 only.  k clusters, R restarts (sklearn's n_init), max_iter >= 1, tol >= 0, standardize 0 / 1.
+ *   Exactly one of init_host [R, k, d] (the starting centres, in the chain's own units) and u_host [R, k] (uniforms in [0, 1) that
+ *   drive the seeding below) is non-NULL: the device draws no random number.
+ *   1. MOMENTS.  Per column the weighted mean and the population standard deviation (ddof = 0), compensated sums in a fixed order.
+ *      A column whose values are all equal has mean = that value and scale 1 (decided by min == max, not from a rounded variance);
+ *      so has one whose standard deviation is 0.  standardize = 0: mean = 0, scale = 1.  A row with a non-finite coordinate has
+ *      weight 0 from here on, label -1, and is counted in n_skipped.  z = (x - mean) / scale is formed on the fly in every pass.
+ *   2. SEEDING (u_host): the published k-means++ (Arthur & Vassilvitskii 2007).  Centre 0 of restart r is the first row whose
+ *      running weight sum exceeds u[r, 0] W; centre c the first row whose running sum of w_i D_i exceeds u[r, c] sum w D, D_i the
+ *      squared distance to the nearest centre chosen so far.  The running sum is hierarchical and fixed by S: one add after the
+ *      other over the 64 rows of a wave, the 4 waves of a tile, the tiles of a range, the ranges.  If sum w D == 0 (fewer distinct
+ *      rows than centres) centre c repeats centre c - 1.  sklearn's own seeding (greedy, 2 + log k trials, Mersenne stream) is NOT
+ *      reproduced; parity with sklearn goes through init_host.
+ *   3. LLOYD, sklearn's loop: assign every row to the nearest centre (ties: the lowest index); move every centre to the weighted
+ *      mean of its rows; a restart stops when the labels of its rows of positive weight equal the previous iteration's, or when the
+ *      summed squared centre shift is <= tol * mean_j var(z_j) (the weighted variances: 1 for a standardised column that is not
+ *      constant), or after max_iter iterations; then one more assignment against the final centres gives labels, sizes and the
+ *      inertia sum w_i min_c |z_i - c|^2.  n_iter counts as sklearn's n_iter_.  DEVIATION: a cluster that loses all its weight
+ *      keeps its centre and reports size 0 (sklearn relocates it).  A stopped restart is frozen while the others go on.
+ *   4. The best restart has the lowest inertia; the lowest index wins a tie.
+ *   REPRODUCIBLE SUMS: a centre is sum_i llrint(z_ij w_i 2^F) / sum_i llrint(w_i 2^G), 64-bit integer sums (LDS and global integer
+ *   atomics) with F = 61 - e, 2^e > max_j sum_i w_i |z_ij|, and G = 61 - e(W) (G = 0 without weights); the inertia is the integer
+ *   sum of llrint(w_i D_i 2^FI), FI from the bound sum w D <= 2 sum w |z|^2 + 2 W |c_0|^2.  Equal inputs give equal bits; a
+ *   restart's bits do not depend on the restarts that share the call, and with init_host not on the layout.  A centre coordinate
+ *   is within n_c 2^-(F + 1) / W_c of the exact weighted mean of its rows: 2^-(F + 1) <= 2^-39 at S = 2^23 without weights.
+ *   Outputs in host memory (NULL: skipped); the call synchronises.
+ *     centers [R, k, d]   in the chain's own units (c scale + mean)       inertia [R], n_iter [R], converged [R] (0 / 1)
+ *     size [R, k]         rows of positive weight per cluster             wsum [R, k]  their weight
+ *     mean [d], scale [d] what z was formed with                          seed_index [R, k]  the seeded rows (-1 with init_host)
+ *     best                the best restart                                n_skipped    rows with a non-finite coordinate
+ *     labels_dev [S]      (int32, DEVICE memory, optional) the best restart's labels in row order, -1 for a skipped row
+ *   Errors (GPB_E_ARG): nsteps, nwalkers or d below 1; d above 64; nsteps nwalkers above 2^31 - 1; strides that let two elements
+ *   alias; weights with nwalkers != 1, or negative or not finite; k outside 1 .. 32; R outside 1 .. 16; max_iter < 1; tol negative
+ *   or not finite; standardize not 0 / 1; both or neither of init_host and u_host; init_host not finite; u_host outside [0, 1); k
+ *   above the number of rows with positive weight. */
+GPB_API int gpb_chain_kmeans(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                     int64_t step_stride, int64_t walker_stride, const double* w_dev /*[nsteps] or NULL*/, int k, int R,
+                     int max_iter, double tol, int standardize, const double* init_host /*[R,k,d] or NULL*/,
+                     const double* u_host /*[R,k] or NULL*/, double* centers /*[R,k,d]*/, double* inertia /*[R]*/,
+                     int32_t* n_iter /*[R]*/, int32_t* converged /*[R]*/, int64_t* size /*[R,k]*/, double* wsum /*[R,k]*/,
+                     double* mean /*[d]*/, double* scale /*[d]*/, int64_t* seed_index /*[R,k]*/, int32_t* best,
+                     int64_t* n_skipped, int32_t* labels_dev /*[S], device, or NULL*/);
+
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324
  * gpb_loglike    <- -1/2 dY^T C^-1 dY - sum log diag chol(C), C = cov_model + cov_exp
