@@ -68,6 +68,10 @@ BOUNDARY = {
                                       VP, VP, VP]),
     "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "gpb_maxpro_lhd": (C.c_int, [VP, c_i64, c_i64, C.c_int, C.c_int, VP, c_u64, c_i64, c_i64, C.c_int, C.c_double, C.c_double,
+                                 VP, VP, VP, VP, VP, VP]),
+    "gpb_maxpro_criterion": (C.c_int, [VP, VP, c_i64, c_i64, VP, VP]),
+    "gpb_maxpro_run_order": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, VP]),
     "gpb_like_set": (C.c_int, [VP, VP, VP]),
     "gpb_loglike": (C.c_int, [VP, VP, c_i64, C.c_int, VP, C.c_int, VP]),
     "gpb_logpost": (C.c_int, [VP, VP, c_i64, VP, C.c_int, VP, VP, C.c_double, C.c_double]),

@@ -156,6 +156,7 @@ struct gpb_ctx {
     gpb::DevBuf<int64_t> marg_ws;
     int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
+    gpb::DevBuf<int64_t> maxpro_ws;  // MaxPro Latin-hypercube designs (gpb_maxpro.hip): MaxproWs of ws_layout.h
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

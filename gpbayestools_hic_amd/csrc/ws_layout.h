@@ -195,6 +195,28 @@ struct KmeansWs {
     }
 };
 
+// maxpro_ws (gpb_maxpro.hip), 8-byte units: the pair matrices T [R][n][n] | row sums [R][n] | per restart (sum, best sum, start
+// sum, sum of the best levels) [R][4] | (accepted, consumed) [R][2] | levels and best levels [R][d][n] each (int, a column
+// contiguous) | the trace [R][n_trace] (int; none without a trace) | for a real design (R == 1): x [d][n], the scores [n] and the
+// run order [n] (int)
+struct MaxproWs {
+    double *T, *rowsum, *sums, *x, *score;
+    int64_t* counts;
+    int *lev, *best, *trace, *order;
+    void lay(Carver<int64_t>& c, int64_t n, int64_t d, int64_t R, int64_t n_trace, int real) {
+        T = c.take<double>(R * n * n);
+        rowsum = c.take<double>(R * n);
+        sums = c.take<double>(R * 4);
+        counts = c.take<int64_t>(R * 2);
+        lev = c.take<int>(real ? 0 : R * d * n);
+        best = c.take<int>(real ? 0 : R * d * n);
+        trace = c.take<int>(real ? 0 : R * n_trace);
+        x = c.take<double>(real ? d * n : 0);
+        score = c.take<double>(real ? n : 0);
+        order = c.take<int>(real ? n : 0);
+    }
+};
+
 // sl_scale (gpb_sliced.hip): row scales [P][Np128] | column scales [P] | row exponents [P][Np128] (int)
 struct SlScale {
     double *rowscale, *colscale;

@@ -791,6 +791,84 @@ class GPEngine:
             out["labels"] = labels
         return out
 
+    MAXPRO_N, MAXPRO_D, MAXPRO_MAX_RESTARTS, MAXPRO_MAX_BLOCK = (4, 4096), (2, 64), 16, 64
+
+    def _maxpro_shape(self, n, d):
+        if not self.MAXPRO_N[0] <= n <= self.MAXPRO_N[1]:
+            raise ValueError("maxpro: n = %d outside %d .. %d" % ((n,) + self.MAXPRO_N))
+        if not self.MAXPRO_D[0] <= d <= self.MAXPRO_D[1]:
+            raise ValueError("maxpro: d = %d outside %d .. %d" % ((d,) + self.MAXPRO_D))
+
+    def maxpro_lhd(self, init, seed, n_stages, blocks_per_stage, block=32, temp0=0.001, cool=0.75, restart0=0, return_trace=False):
+        """Maximum-projection Latin hypercubes by simulated annealing over column-wise swaps on the device (gpb_maxpro_lhd;
+        DESIGN.md section 24): init [R, n, d] integer levels, every column a permutation of 0 .. n - 1 (R <= 16 independent
+        restarts, 4 <= n <= 4096, 2 <= d <= 64); stage k of n_stages runs blocks_per_stage blocks of `block` proposals at the
+        temperature temp0 cool^k; the draws are keyed by (seed, block, restart0 + r, slot).  Returns a dict of numpy arrays:
+        "levels" [R, n, d] (int32, the best levels each restart has seen), "f_start", "f_best" [R] (f = ln sum of the pair terms;
+        f_best recomputed from the levels), "lnpsi_start", "lnpsi" [R] (the MaxPro criterion), "accepted", "consumed" [R] (int64)
+        and, with return_trace, "trace" [R, n_stages blocks_per_stage] (int32: per block the accepted slot, or -1).  The engine
+        lends its device and stream only."""
+        self._check_pid()
+        init = np.asarray(init)
+        if init.ndim != 3 or not np.issubdtype(init.dtype, np.integer):
+            raise ValueError("init: expected integer levels [R, n, d]")
+        R, n, d = (int(v) for v in init.shape)
+        self._maxpro_shape(n, d)
+        if not 1 <= R <= self.MAXPRO_MAX_RESTARTS:
+            raise ValueError("init: %d restarts, outside 1 .. %d" % (R, self.MAXPRO_MAX_RESTARTS))
+        if not 1 <= int(block) <= self.MAXPRO_MAX_BLOCK:
+            raise ValueError("block = %d outside 1 .. %d" % (block, self.MAXPRO_MAX_BLOCK))
+        if int(n_stages) < 1 or int(blocks_per_stage) < 1:
+            raise ValueError("n_stages and blocks_per_stage must be at least 1")
+        if not np.array_equal(np.sort(init, axis=1), np.broadcast_to(np.arange(n)[None, :, None], init.shape)):
+            raise ValueError("init: every column must be a permutation of 0 .. n - 1")
+        init = np.ascontiguousarray(init, dtype=np.int32)
+        nb = int(n_stages) * int(blocks_per_stage)
+        out = {"levels": np.empty((R, n, d), dtype=np.int32), "f_start": np.empty(R), "f_best": np.empty(R),
+               "accepted": np.empty(R, dtype=np.int64), "consumed": np.empty(R, dtype=np.int64)}
+        trace = np.empty((R, nb), dtype=np.int32) if return_trace else None
+        self._ck(self.lib.gpb_maxpro_lhd(self.h, n, d, R, int(restart0), nat.ptr(init), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_stages),
+                                         int(blocks_per_stage), int(block), float(temp0), float(cool), nat.ptr(out["levels"]),
+                                         nat.ptr(out["f_start"]), nat.ptr(out["f_best"]), nat.ptr(out["accepted"]),
+                                         nat.ptr(out["consumed"]), nat.ptr(trace)))
+        const = (3.0 * d - np.log(0.5 * n * (n - 1))) / d
+        out["lnpsi_start"], out["lnpsi"] = out["f_start"] / d + const, out["f_best"] / d + const
+        if return_trace:
+            out["trace"] = trace
+        return out
+
+    def maxpro_criterion(self, X, return_sum=False):
+        """ln psi of a design X [n, d] in the unit cube (gpb_maxpro_criterion), psi = (mean over pairs of
+        1 / prod_c (x_ic - x_jc)^2)^(1/d) (Joseph, Gul, Ba 2015): +inf when two rows share a coordinate.  return_sum: also the sum
+        of the scaled pair terms prod_c (e^1.5 (x_ic - x_jc))^-2."""
+        self._check_pid()
+        X = nat.f64(X)
+        if X.ndim != 2:
+            raise ValueError("X: expected [n, d]")
+        self._maxpro_shape(*X.shape)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X: must be finite")
+        out = np.zeros(2)
+        self._ck(self.lib.gpb_maxpro_criterion(self.h, nat.ptr(X), X.shape[0], X.shape[1], nat.ptr(out[:1]), nat.ptr(out[1:])))
+        return (float(out[0]), float(out[1])) if return_sum else float(out[0])
+
+    def maxpro_run_order(self, X, first=-1):
+        """The greedy run order of a design X [n, d] (gpb_maxpro_run_order): row `first` (-1: the row nearest the cube's
+        centre), then again and again the row with the smallest sum of its pair terms with the rows chosen so far, the lowest
+        index at a tie.  Returns the order [n] (int32, 0-based row indices)."""
+        self._check_pid()
+        X = nat.f64(X)
+        if X.ndim != 2:
+            raise ValueError("X: expected [n, d]")
+        self._maxpro_shape(*X.shape)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X: must be finite")
+        if not -1 <= int(first) < X.shape[0]:
+            raise ValueError("first = %d outside -1 .. n - 1" % first)
+        order = np.empty(X.shape[0], dtype=np.int32)
+        self._ck(self.lib.gpb_maxpro_run_order(self.h, nat.ptr(X), X.shape[0], X.shape[1], int(first), nat.ptr(order)))
+        return order
+
     def emu_predict_jac(self, Xs):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
         the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""

@@ -236,7 +236,8 @@ GPB_API int gpb_emu_main_effect(gpb_ctx* ctx, const double* lo_host /*[d]*/, con
                         const double* t /*[G]*/, int64_t G, int on_device, double* curve /*[G,M]*/);
 
 /* ---- variance-reduction sequential design: where the next model runs go ------------------------------------------------ *
- * (the reference's design.py is a one-shot space-filling generator; nothing there chooses a second wave from a fitted emulator.)
+ * (the reference's design.py is a one-shot space-filling generator — gpb_maxpro_lhd below is its counterpart; nothing there
+ * chooses a second wave from a fitted emulator.)
  * Needs only what is resident after gpb_gp_factor — X, theta, L^-1 — and no training output.  For GP p, amplitude c, kernel k,
  * tau = sigma_n^2 + alpha, v(a) = L^-1 k(X, a), the posterior covariance of the latent function (no White term) is
  *   s(a, b) = c k(a, b) - v(a)^T v(b)
@@ -454,6 +455,36 @@ GPB_API int gpb_chain_kmeans(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, 
                      int32_t* n_iter /*[R]*/, int32_t* converged /*[R]*/, int64_t* size /*[R,k]*/, double* wsum /*[R,k]*/,
                      double* mean /*[d]*/, double* scale /*[d]*/, int64_t* seed_index /*[R,k]*/, int32_t* best,
                      int64_t* n_skipped, int32_t* labels_dev /*[S], device, or NULL*/);
+
+/* ---- maximum-projection Latin-hypercube designs -------------------------------------------------------------------------------- *
+ * gpb_maxpro_lhd, gpb_maxpro_run_order <- src/design.py:64-74, R's `MaxProRunOrder(MaxProLHD(npoints, ndim)$Design)`;
+ * gpb_maxpro_criterion: the criterion that generator minimises, for any design.
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  2 <= d <= 64, 4 <= n <= 4096.
+ *   Levels l[i][c] in {0 .. n-1}, every column a permutation; the design is x = (l + 0.5) / n.  Pair terms
+ *   t_ij = prod_c (s (l_ic - l_jc))^-2 with s = e^1.5 / n, the objective f = ln sum_{i<j} t_ij, and the criterion of Joseph, Gul, Ba
+ *   (2015), psi = (mean_{i<j} prod_c (x_ic - x_jc)^-2)^(1/d):  ln psi = (f + 3 d - ln(n (n - 1) / 2)) / d  (csrc/maxpro_index.h).
+ *   gpb_maxpro_lhd: simulated annealing over column-wise swaps, R <= 16 independent restarts from init_levels [R, n, d].  Stage k
+ *   of n_stages has the temperature temp0 cool^k and runs blocks_per_stage blocks; a block is `block` (1 .. 64) proposals, all
+ *   drawn and evaluated at the block's starting state; in slot order the first that passes ln u < -(f' - f) / temp is applied,
+ *   the rest of the block is discarded.  A proposal (column, rows a != b, u) is decoded from Philox4x32-10 with the counter
+ *   (global block index, restart0 + r, slot, 11): a restart's result depends on its start and its index alone.  The pair matrix
+ *   and f are rebuilt from the levels at every stage start.  Per restart: levels_out [R, n, d] the best levels seen, f_start,
+ *   f_best (recomputed from those levels), accepted and consumed proposals, and trace [R, n_stages blocks_per_stage] (or NULL):
+ *   per block the accepted slot, or -1.  Host memory; the call synchronises once before the annealing and once behind it.
+ *   Errors (GPB_E_ARG): n, d, R, block outside their limits; a column that is no permutation; a start whose f is not finite (two
+ *   rows adjacent in every column of a wide design); temperatures that are not positive and finite; more than 2^31 - 1 blocks.
+ *   gpb_maxpro_criterion: ln psi of a real design X [n, d] (host), +inf when two rows share a coordinate; sum_out (or NULL) the sum
+ *   of the pair terms prod_c (e^1.5 (x_ic - x_jc))^-2.
+ *   gpb_maxpro_run_order: order_out [n] (int32): row `first` (-1: the row nearest the cube's centre), then again and again the
+ *   row with the smallest sum of its pair terms with the rows chosen so far; the lowest index wins a tie. */
+GPB_API int gpb_maxpro_lhd(gpb_ctx* ctx, int64_t n, int64_t d, int R, int restart0, const int32_t* init_levels /*[R,n,d]*/,
+                   uint64_t seed, int64_t n_stages, int64_t blocks_per_stage, int block, double temp0, double cool,
+                   int32_t* levels_out /*[R,n,d]*/, double* f_start /*[R]*/, double* f_best /*[R]*/, int64_t* accepted /*[R]*/,
+                   int64_t* consumed /*[R]*/, int32_t* trace /*[R, n_stages blocks_per_stage] or NULL*/);
+GPB_API int gpb_maxpro_criterion(gpb_ctx* ctx, const double* X /*[n,d]*/, int64_t n, int64_t d, double* lnpsi_out,
+                         double* sum_out /*or NULL*/);
+GPB_API int gpb_maxpro_run_order(gpb_ctx* ctx, const double* X /*[n,d]*/, int64_t n, int64_t d, int64_t first,
+                         int32_t* order_out /*[n]*/);
 
 /* ---- likelihood block: replaces Chain._predict + mvn_loglike for ONE emulator ---- *
  * gpb_like_set   <- expdata[i0:i0+M], expdata_cov[i0:i0+M, i0:i0+M]    src/mcmc.py:139,302-324

@@ -3,6 +3,7 @@
 Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
     python tools/make_goldens.py            # needs /root/reference, scikit-learn, dill
+    python tools/make_goldens.py g13_design # that golden alone
 
 The reference (Hendrik1704/GPBayesTools-HIC) has no tests or golden vectors of
 its own, so parity is pinned by vectors captured here from the
@@ -470,8 +471,50 @@ def g6_mvn(mcmc):
     np.savez_compressed(os.path.join(OUT, "g6_mvn.npz"), **out)
 
 
+G13_PARFILE = """# a three-parameter model
+norm: $N$, 10.0, 20.0   # normalisation
+tau_fs: $\\tau_{fs}$, 0.1, 1.5
+eta_over_s: $\\eta/s$, 0.0, 0.3
+"""
+
+
+def g13_design():
+    """src/design.py's Design on a pre-seeded cache file (its generate_lhs loads npoints12_ndim3_seed42.npy and never reaches R):
+    the cache array, the parameter file's text, and the reference's array / points / min / max / type for the main and the
+    validation design with the text of two written files each."""
+    from pathlib import Path
+    from src.design import Design
+    rng = np.random.default_rng(1300)
+    n, d, seed = 12, 3, 42
+    cache = np.concatenate([np.arange(1, n + 1, dtype=np.float64)[:, None],
+                            np.stack([(rng.permutation(n) + 0.5) / n for _ in range(d)], axis=1)], axis=1)
+    lhs_dir = Path(_work) / "cache" / "lhs"
+    lhs_dir.mkdir(parents=True, exist_ok=True)
+    np.save(lhs_dir / "npoints{}_ndim{}_seed{}.npy".format(n, d, seed), cache)
+    parfile = Path(_work) / "g13_pars.txt"
+    parfile.write_text(G13_PARFILE)
+    out = {"cache": cache, "parfile": np.array(G13_PARFILE), "npoints": n, "seed": seed}
+    for validation in (False, True):
+        des = Design(str(parfile), npoints=n, validation=validation, seed=seed)
+        base = Path(_work) / "g13_out"
+        des.write_files(base)
+        k = "val_" if validation else "main_"
+        out[k + "array"] = np.array(des.array)
+        out[k + "asarray"] = np.asarray(des)
+        out[k + "points"] = np.array(des.points)
+        out[k + "min"], out[k + "max"] = des.min, des.max
+        out[k + "type"], out[k + "ndim"] = np.array(des.type), des.ndim
+        out[k + "keys"] = np.array(list(des.pardict.keys()))
+        for name in (des.points[0], des.points[-1]):
+            out[k + "file_" + name] = np.array((base / des.type / name).read_text())
+    np.savez_compressed(os.path.join(OUT, "g13_design.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["g13_design"]:          # (one golden alone: the others stay as committed)
+        g13_design()
+        return
     Emulator, mcmc = _import_reference()
     g1_kernels()
     g2_gpr()
@@ -483,6 +526,7 @@ def main():
     g9_loading(Emulator)
     g10_learning_curve(Emulator)
     g11_trained_objects(Emulator)
+    g13_design()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
