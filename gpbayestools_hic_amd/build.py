@@ -8,8 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpbayes.so")
 LIB_DEBUG = os.path.join(HERE, "libgpbayes_debug.so")
 SOURCES = ["gpb_api.hip", "gpb_fit.hip", "gpb_chol.hip", "gpb_predict.hip", "gpb_sliced.hip", "gpb_like.hip", "gpb_coupled.hip", "gpb_chain.hip", "gpb_stretch.hip", "gpb_cov.hip", "gpb_pmap.hip", "gpb_pool.hip",
-           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip"]
-HEADERS = ["gpb_internal.h", "dispatch.h", "dev_buf.h", "ws_carve.h", "ws_layout.h", "coupled_setup.h", "sl_index.h", "gemm_tile.h", "block_reduce.h", "chol_block.h", "fast_math.h", "philox.h", "maxpro_index.h",os.path.join("..", "..", "include", "gpbayes.h"),
+           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip", "gpb_curves.hip"]
+HEADERS = ["gpb_internal.h", "dispatch.h", "dev_buf.h", "ws_carve.h", "ws_layout.h", "coupled_setup.h", "sl_index.h", "gemm_tile.h", "block_reduce.h", "chol_block.h", "fast_math.h", "philox.h", "maxpro_index.h", "curve_fn.h", "order_key.h", os.path.join("..", "..", "include", "gpbayes.h"),
            os.path.join("..", "..", "include", "gpbayes_debug.h")]
 
 

@@ -155,6 +155,7 @@ struct gpb_ctx {
     // of a sample group; marg_ws_bytes caps the last two (option key 52 lowers it, in the debug build only: the grouping's test)
     gpb::DevBuf<int64_t> marg_ws;
     int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
+    gpb::DevBuf<int64_t> curves_ws;  // posterior curves and trace histograms (gpb_curves.hip): CurvesWs of ws_layout.h
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
     gpb::DevBuf<int64_t> maxpro_ws;  // MaxPro Latin-hypercube designs (gpb_maxpro.hip): MaxproWs of ws_layout.h
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the

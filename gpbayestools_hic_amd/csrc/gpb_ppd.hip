@@ -16,6 +16,7 @@
 // row — not on M, the other rows, ld, or the outputs that share the call.  No floating-point atomics.
 #include "gpb_internal.h"
 #include "block_reduce.h"
+#include "order_key.h"
 #include <math.h>
 
 namespace gpb {
@@ -55,15 +56,7 @@ __global__ __launch_bounds__(PPD_THREADS) void k_ppd_moments(const double* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------- order statistics
-// unsigned keys in the order of the doubles (-0.0 in front of +0.0)
-__device__ __forceinline__ unsigned long long ppd_key(double x) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ppd_unkey(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
+// (ppd_key / ppd_unkey, the unsigned keys in the order of the doubles: order_key.h)
 // Rank r keeps the digits found so far (prefix[r], the undecided bits zero) and its rank among the keys that share them (rem[r]).
 // Ranks with equal prefixes form a group and share one 256-bin histogram: a pass costs one LDS atomic per key and GROUP that the
 // key belongs to (one group in the first pass, at most 2 nq in the last).

@@ -156,6 +156,29 @@ struct MargWs {
     }
 };
 
+// curves_ws (gpb_chain_curves), 8-byte units, R = ncurves G rows and nr = 2 nq ranks per row: grid [R] | aux [2 d] | per
+// (row, rank) the digits found so far, the rank among the keys that share them and the distinct prefixes of the row's ranks
+// [R][nr] each | the digit histograms [R][nr][256] (u32) | curve descriptors [ncurves][5], every rank's group [R][nr] and the
+// groups per row [R] (int).  Nothing in it grows with the number of samples.  gpb_chain_trace_hist keeps its edges here.
+struct CurvesWs {
+    double *grid, *aux;
+    uint64_t *prefix, *gprefix;
+    int64_t* rem;
+    unsigned* hist;
+    int *desc, *grp, *ngrp;
+    void lay(Carver<int64_t>& c, int64_t ncurves, int64_t R, int64_t nr, int64_t d2) {
+        grid = c.take<double>(R);
+        aux = c.take<double>(d2);
+        prefix = c.take<uint64_t>(R * nr);
+        gprefix = c.take<uint64_t>(R * nr);
+        rem = c.take<int64_t>(R * nr);
+        hist = c.take<unsigned>(R * nr * 256);
+        desc = c.take<int>(ncurves * 5);
+        grp = c.take<int>(R * nr);
+        ngrp = c.take<int>(R);
+    }
+};
+
 // kmeans_ws (gpb_chain_kmeans), 8-byte units.  A run that is zeroed at the start of a call (state0, state_bytes): counters [4] |
 // centres [R][k][d] | shift [R] | integer sums acc [R][k][d], wq [R][k], cnt [R][k], iner [R] | seed rows [R][k] | changed, done,
 // conv, niter, fi [R] each (int, back to back).  Behind it: mean | scale [2 d] | moment sums [5 d + 1] and their workgroup

@@ -722,6 +722,97 @@ class GPEngine:
                                               nat.ptr(out.get("h2")), nat.ptr(out.get("outside"))))
         return out
 
+    def _chain_view(self, x_dev, layout):
+        """(nsteps, nwalkers, ndim, step stride, walker stride) of a device chain as chain_marginals takes it"""
+        if layout not in ("steps", "walkers"):
+            raise ValueError("layout: 'steps' ([nsteps, nwalkers, ndim]) or 'walkers' ([nwalkers, nsteps, ndim])")
+        if not _is_torch(x_dev) or x_dev.dim() != 3:
+            raise ValueError("x_dev: expected a three-dimensional torch tensor")
+        if not x_dev.is_cuda or x_dev.device.index != self.device or str(x_dev.dtype) != "torch.float64":
+            raise ValueError("x_dev: expected a torch.float64 tensor on cuda:%d" % self.device)
+        ts, tw = (0, 1) if layout == "steps" else (1, 0)
+        n, nw, d = int(x_dev.shape[ts]), int(x_dev.shape[tw]), int(x_dev.shape[2])
+        if d > 1 and x_dev.stride(2) != 1:
+            raise ValueError("x_dev: expected unit stride along the parameters")
+        ss, ws = int(x_dev.stride(ts)), int(x_dev.stride(tw))
+        # an axis of extent 1 has no meaningful stride: give it the one of a contiguous array
+        if nw == 1 and layout == "steps":
+            ws = d
+        if n == 1 and layout == "walkers":
+            ss = d
+        if nw == 1 and layout == "walkers":
+            ws = max(ws, ss * n)
+        if n == 1 and layout == "steps":
+            ss = max(ss, ws * nw)
+        return n, nw, d, ss, ws
+
+    CURVE_FNS = {"zeta_over_s": 0, "eta_over_s": 1, "y_loss": 2, "delta": 3}
+    CURVES_MAX, CURVES_MAX_GRID = 8, 1024
+
+    def chain_curves(self, x_dev, layout="steps", desc=None, grid=None, q=None, aux=None, values=False, on_device=False):
+        """Order statistics over all samples of parametrised curves of a chain that lies on the device (gpb_chain_curves): x_dev
+        and layout as chain_marginals takes them; desc [ncurves, 5] int32 rows (fn, col0 .. col3; -1 unused; CURVE_FNS), grid
+        [ncurves, G], q the levels in [0, 1] (at most 16; None: no select), aux = truth [ndim] | width [ndim] for fn 3.  Sample
+        s = step * nwalkers + walker in either layout.  Returns a dict: "order" [ncurves, G, nq, 2] (with q), the two order
+        statistics numpy's percentile interpolates between, selected exactly WITHOUT forming the [G, S] values; "values"
+        [ncurves, G, S] (values=True), the materialised curves — meant for small S and for fn 3.  numpy out, or with on_device
+        torch tensors (asynchronous).  The engine lends its device, stream and buffer cache only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        n, nw, d, ss, ws = self._chain_view(x_dev, layout)
+        S = n * nw
+        desc = np.ascontiguousarray(np.asarray(desc, dtype=np.int32).reshape(-1, 5))
+        ncurves = int(desc.shape[0])
+        grid = nat.f64(np.asarray(grid, dtype=np.float64).reshape(ncurves, -1))
+        G = int(grid.shape[1])
+        aux = None if aux is None else nat.f64(np.asarray(aux, dtype=np.float64).reshape(-1))
+        if aux is not None and aux.shape[0] != 2 * d:
+            raise ValueError("aux: expected truth [%d] | width [%d]" % (d, d))
+        nq = 0
+        if q is not None:
+            q = nat.f64(np.atleast_1d(np.asarray(q, dtype=np.float64))).reshape(-1)
+            nq = int(q.shape[0])
+        shapes = {}
+        if q is not None:
+            shapes["order"] = (ncurves, G, nq, 2)
+        if values:
+            shapes["values"] = (ncurves, G, S)
+        if on_device:
+            out = {k: torch.empty(s, dtype=torch.float64, device=dev) for k, s in shapes.items()}
+        else:
+            out = {k: np.empty(s) for k, s in shapes.items()}
+        self._ck(self.lib.gpb_chain_curves(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, ncurves, nat.ptr(desc), nat.ptr(aux), nat.ptr(grid),
+                                           G, nat.ptr(q), nq, 1 if on_device else 0, nat.ptr(out.get("order")),
+                                           nat.ptr(out.get("values")), S))
+        return out
+
+    def chain_trace_hist(self, x_dev, layout="steps", edges=None, on_device=False, outputs=None):
+        """The walkers' distribution step by step (gpb_chain_trace_hist): x_dev and layout as chain_marginals takes them, edges
+        [ndim, B + 1] with its bin rule, B <= 64.  Returns a dict of int64 arrays: "hist" [ndim, nsteps, B], hist[j, t, b] the
+        walkers of step t with parameter j in bin b — np.histogram2d(step, value, bins=[nsteps, edges[j]]) — and "outside"
+        [ndim, nsteps].  numpy out, or with on_device torch tensors (asynchronous)."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        n, nw, d, ss, ws = self._chain_view(x_dev, layout)
+        edges = nat.f64(edges)
+        if edges.ndim != 2 or edges.shape[0] != d or edges.shape[1] < 2:
+            raise ValueError("edges: expected [%d, B + 1]" % d)
+        B = int(edges.shape[1]) - 1
+        names = ("hist", "outside")
+        outputs = names if outputs is None else tuple(outputs)
+        if any(k not in names for k in outputs):
+            raise ValueError("outputs: names among %s" % (names,))
+        shapes = {"hist": (d, n, B), "outside": (d, n)}
+        if on_device:
+            out = {k: torch.empty(shapes[k], dtype=torch.int64, device=dev) for k in outputs}
+        else:
+            out = {k: np.empty(shapes[k], dtype=np.int64) for k in outputs}
+        self._ck(self.lib.gpb_chain_trace_hist(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, nat.ptr(edges), B, 1 if on_device else 0,
+                                               nat.ptr(out.get("hist")), nat.ptr(out.get("outside"))))
+        return out
+
     KMEANS_MAX_K, KMEANS_MAX_RESTARTS = 32, 16
 
     def chain_kmeans(self, x_dev, layout="steps", k=10, n_init=10, init=None, u=None, weights=None, max_iter=300, tol=1e-4,

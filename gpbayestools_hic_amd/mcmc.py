@@ -579,6 +579,69 @@ class Chain:
         xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
         return marginals(xd[:, discard::thin], layout="walkers", **kw)
 
+    def _stored_for_curves(self, who, chain, discard, thin, weights):
+        """the chain argument of posterior_curves / closure_delta / trace_histogram: (a flat [S, ndim] numpy set, None) or (None,
+        the device view [nwalkers, nsteps', ndim] of the stored array without `discard` steps, thinned by `thin`)"""
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        x = np.asarray(chain, dtype=np.float64)
+        if x.ndim == 2:
+            return x, None
+        if x.ndim != 3:
+            raise ValueError("%s: chain must be [nwalkers, nsteps, ndim] or [S, ndim], got %s" % (who, np.shape(chain)))
+        if weights is not None:
+            raise ValueError("%s: weights go with a flat [S, ndim] particle set" % who)
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+            raise ValueError("%s: discard >= 0, thin >= 1 and at least one step must remain" % who)
+        import torch
+        xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
+        return None, xd[:, discard::thin]
+
+    def posterior_curves(self, chain=None, discard=0, thin=1, weights=None, **kw):
+        """The posterior of the functions zeta/s (T), eta/s (mu_B) and <y_loss> (y_init): PosteriorCurves (curves.py) — median
+        and 68 / 95 / 99.7 % bands over ALL samples, PlotMCMC.ipynb's plot_*_posterior — of a stored [nwalkers, nsteps, ndim]
+        array (self.chain by default, read from mcmc_path when it is not in memory) without its first `discard` steps and
+        thinned by `thin`, or of a flat [S, ndim] particle set with its `weights`.  Selected exactly on the device without
+        forming the [S, 100] arrays (gpb_chain_curves); kw (curves, columns, grid, levels, truth, return_values) as
+        curves.posterior_curves takes them."""
+        from .curves import posterior_curves
+        flat, xd = self._stored_for_curves("posterior_curves", chain, discard, thin, weights)
+        kw.setdefault("device", self.device or 0)
+        if flat is not None:
+            return posterior_curves(flat, weights=weights, **kw)
+        return posterior_curves(xd, layout="walkers", **kw)
+
+    def closure_delta(self, truth, chain=None, discard=0, thin=1, prior_ranges=None, weights=None, **kw):
+        """The closure verdict against the true parameters `truth` [ndim]: ClosureDelta (curves.py) — PlotMCMC.ipynb's Delta_d,
+        its per-sample distribution's histogram and quantiles, and every parameter's share — of the stored chain as
+        posterior_curves takes it.  prior_ranges [ndim, 2]: default the prior box min / max."""
+        from .curves import closure_delta
+        flat, xd = self._stored_for_curves("closure_delta", chain, discard, thin, weights)
+        if prior_ranges is None:
+            prior_ranges = np.stack([self.min, self.max], axis=1)
+        nd = (flat if flat is not None else xd).shape[-1]
+        kw.setdefault("names", list(self.pardict) if len(getattr(self, "pardict", ())) == nd else None)
+        kw.setdefault("device", self.device or 0)
+        if flat is not None:
+            return closure_delta(flat, truth, prior_ranges, weights=weights, **kw)
+        return closure_delta(xd, truth, prior_ranges, layout="walkers", **kw)
+
+    def trace_histogram(self, chain=None, discard=0, thin=1, bins=30, range=None):
+        """The walkers' distribution step by step: TraceHistogram (curves.py), PlotMCMC.ipynb's plot_chain_histogram — per
+        parameter np.histogram2d(step, value, bins=[nsteps, 30])'s counts — of a stored [nwalkers, nsteps, ndim] array as
+        posterior_curves takes it, counted on the device (gpb_chain_trace_hist).  range: default every parameter's extent
+        over the chain, as the notebook's call takes it; [ndim, 2] for fixed edges."""
+        from .curves import trace_histogram
+        flat, xd = self._stored_for_curves("trace_histogram", chain, discard, thin, None)
+        if flat is not None:
+            raise ValueError("trace_histogram: chain must be [nwalkers, nsteps, ndim] (a flat set has no steps)")
+        names = list(self.pardict) if len(getattr(self, "pardict", ())) == xd.shape[-1] else None
+        return trace_histogram(xd, bins=bins, range=range, layout="walkers", names=names, device=self.device or 0)
+
     def posterior_clusters(self, chain=None, discard=0, thin=1, n_clusters=10, n_init=10, **kw):
         """Representative parameter sets of the posterior: PosteriorClusters (clusters.py) of a stored [nwalkers, nsteps, ndim]
         array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first

@@ -295,6 +295,34 @@ class StretchSampler:
         kw.setdefault("names", list(names) if names else None)
         return posterior_clusters(x, layout="steps", **kw)
 
+    def curves(self, discard=0, thin=1, **kw):
+        """PosteriorCurves of chain[discard::thin] (curves.py): median and credible bands of zeta/s (T), eta/s (mu_B) and
+        <y_loss> (y_init) over all stored samples, selected on the device without forming the per-sample curves
+        (gpb_chain_curves); kw (curves, columns, grid, levels, truth, return_values) as curves.posterior_curves takes them."""
+        from .curves import posterior_curves
+        x, _ = self._stored_view(discard, thin)
+        return posterior_curves(x, layout="steps", **kw)
+
+    def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
+        """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
+        chain object's prior box."""
+        from .curves import closure_delta
+        x, _ = self._stored_view(discard, thin)
+        if prior_ranges is None:
+            prior_ranges = np.stack([self.chain_obj.min, self.chain_obj.max], axis=1)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return closure_delta(x, truth, prior_ranges, layout="steps", **kw)
+
+    def trace_histogram(self, discard=0, thin=1, **kw):
+        """TraceHistogram of chain[discard::thin] (curves.py): the walkers' distribution step by step, counted on the device
+        (gpb_chain_trace_hist); kw (bins, range) as curves.trace_histogram takes them."""
+        from .curves import trace_histogram
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return trace_histogram(x, layout="steps", **kw)
+
 
 class _HostLogProb:
     """minimal chain-like object around a host callable f(X[w, ndim]) -> lp[w]"""

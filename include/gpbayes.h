@@ -405,6 +405,52 @@ GPB_API int gpb_chain_marginals(gpb_ctx* ctx, const double* x_dev, int64_t nstep
                         const double* w_dev /*[nsteps] or NULL*/, double wscale, int on_device,
                         int64_t* h1 /*[d,B] or NULL*/, int64_t* h2 /*[npairs,B,B] or NULL*/, int64_t* outside /*[d] or NULL*/);
 
+/* ---- posterior bands of the parametrised curves, closure distance, trace histograms ------------------------------------------ *
+ * gpb_chain_curves     <- examples/PlotMCMC.ipynb (plot_zeta_s_posterior, plot_eta_s_posterior, plot_yloss_posterior): the posterior
+ *                         of the functions zeta/s (T), eta/s (mu_B), <y_loss> (y_init) — `np.percentile(curves[S, 100], ..., axis=0)`
+ *                         over ALL samples of a chain — and (compute_Delta_d, create_Delta_d_distribution) the closure distance
+ * gpb_chain_trace_hist <- plot_chain_histogram: `np.histogram2d(step, value, bins=[n_steps, 30])` per parameter
+ *   The context gives the device, the stream and the buffer cache only.  x_dev, nsteps, nwalkers, d and the strides exactly as
+ *   gpb_chain_marginals reads them (the same aliasing rule; a flat [S, d] set is nsteps = S, nwalkers = 1).
+ * gpb_chain_curves: sample s = t * nwalkers + w, whatever the memory layout; S = nsteps nwalkers <= 2^31 - 1.  Curve c < ncurves
+ *   has the descriptor desc_host[c] = (fn, col0, col1, col2, col3) and the grid grid_host[c][0 .. G); its value for sample s at grid
+ *   point g is v(c, g, s) = curve_value(fn, theta_s[cols], aux, grid[c][g]) of csrc/curve_fn.h, every operation rounded on its own
+ *   (no fused multiply-add), as numpy's vectorised forms round them:
+ *     fn 0  zeta/s   cols (zmax, T0, sigma+, sigma-):  zmax exp(-((g - T0) (g - T0)) / (2 (s s))),  s = sigma- if g < T0 else sigma+
+ *     fn 1  eta/s    cols (e0, e2, e4; col3 = -1): 0 <= g <= 0.2: e0 + (e2 - e0) (g / 0.2); 0.2 < g < 0.4: e2 + (e4 - e2) ((g - 0.2)
+ *                    / 0.2); g >= 0.4: e4; g < 0: 0
+ *     fn 2  y_loss   cols (y2, y4, y6; col3 = -1): 0 <= g <= 2: y2 (g / 2); 2 < g < 4: y2 + (y4 - y2) ((g - 2) / 2); g >= 4: y4 +
+ *                    (y6 - y4) ((g - 4) / 2); g < 0: 0
+ *     fn 3  delta    (sum_j ((theta_j - truth_j) / width_j)^2) / d, j ascending, one add after the other; aux_host = truth [d] |
+ *                    width [d]; the columns and the grid value are ignored
+ *   Outputs (NULL: skipped, its work too) in host memory when on_device = 0 (the call synchronises) or device memory (asynchronous):
+ *     order [ncurves, G, nq, 2]   the order statistics v_(k) and v_(min(k + 1, S - 1)) over s, k = floor(q (S - 1)) — gpb_ppd_summary's
+ *                                 contract, the levels converted as it converts them.  Exact: a radix select on the order-preserving
+ *                                 64-bit key, eight passes of 8 bits; nothing is sorted or interpolated.  NO [G, S] ARRAY IS FORMED:
+ *                                 every pass evaluates v again from the sample's parameters.  Workspace: 256-bin digit tables and
+ *                                 the ranks' prefixes per (curve, grid point, rank) — a function of ncurves, G and nq, not of S.
+ *     values [ncurves, G, ldv]    v itself, element (c, g, s) at (c G + g) ldv + s: for small S, and for fn 3, whose [1, S] row feeds
+ *                                 gpb_ppd_summary and gpb_chain_marginals.  Evaluated by the same code as the select's passes.
+ *   All accumulation is integer (LDS and global integer atomics): the results do not depend on the layout, the slabs the samples are
+ *   counted in, on_device, or on the curves and grid points that share the call.  Inputs must be finite (the caller checks).
+ *   Errors (GPB_E_ARG): the shapes and strides rule of gpb_chain_marginals; S above 2^31 - 1; ncurves outside 1 .. 8; G outside
+ *   1 .. 1024; with order nq outside 1 .. 16 or a level outside [0, 1]; fn outside 0 .. 3; a needed column outside [0, d); fn 3
+ *   without aux or with a truth that is not finite or a width that is not finite and positive; values with ldv < S; a grid value that
+ *   is not finite.
+ * gpb_chain_trace_hist: hist[j][t][b] = the walkers of step t whose parameter j lies in bin b of edges_host [d, B + 1] by
+ *   gpb_chain_marginals' BIN RULE (searched in the edges, the last edge inclusive, NaN and the rest outside -> outside[j][t]).
+ *   Integer counts, written once per (step, parameter): no dependence on layout or on_device.  The step axis needs no binning:
+ *   histogram2d's bins = n_steps over [0, n_steps - 1] puts step t in bin t.
+ *   Errors (GPB_E_ARG): the shapes and strides rule; B outside 1 .. 64; edges that are not finite and strictly increasing. */
+GPB_API int gpb_chain_curves(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                     int64_t step_stride, int64_t walker_stride, int ncurves, const int32_t* desc_host /*[ncurves,5]*/,
+                     const double* aux_host /*[2d] or NULL*/, const double* grid_host /*[ncurves,G]*/, int G,
+                     const double* q_host /*[nq]*/, int nq, int on_device, double* order /*[ncurves,G,nq,2] or NULL*/,
+                     double* values /*[ncurves,G,ldv] or NULL*/, int64_t ldv);
+GPB_API int gpb_chain_trace_hist(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                         int64_t step_stride, int64_t walker_stride, const double* edges_host /*[d,B+1]*/, int B, int on_device,
+                         int64_t* hist /*[d,nsteps,B] or NULL*/, int64_t* outside /*[d,nsteps] or NULL*/);
+
 /* ---- posterior clusters of a resident chain --------------------------------------------------------------------------------- *
  * gpb_chain_kmeans <- examples/generate_posterior_clusters.py: `StandardScaler().fit_transform(chain)`, `KMeans(n_clusters,
  *                     n_init=10).fit(...)`, `scaler.inverse_transform(kmeans.cluster_centers_)` — weighted k-means of the rows of a

@@ -3,7 +3,7 @@
 Generate tests/golden/*.npz by RUNNING THE REFERENCE in the build container.
 
     python tools/make_goldens.py            # needs /root/reference, scikit-learn, dill
-    python tools/make_goldens.py g13_design # that golden alone
+    python tools/make_goldens.py g13_design # that golden alone (g15_curves likewise)
 
 The reference (Hendrik1704/GPBayesTools-HIC) has no tests or golden vectors of
 its own, so parity is pinned by vectors captured here from the
@@ -510,10 +510,49 @@ def g13_design():
     np.savez_compressed(os.path.join(OUT, "g13_design.npz"), **out)
 
 
+def g15_curves():
+    """examples/PlotMCMC.ipynb's parametrization_* functions, its percentile code (np.percentile(curves[S, 100], ..., axis=0) for
+    the median and the 68 / 95 / 99.7 % bands) and compute_Delta_d / create_Delta_d_distribution, applied to 48 samples of 20
+    parameters drawn inside the notebook's prior_ranges.  The cells that define them are read from the notebook's JSON and
+    executed here, at golden-making time; nothing in them that needs matplotlib is called.  Only arrays are written."""
+    import json
+    with open(os.path.join(REF, "examples", "PlotMCMC.ipynb")) as f:
+        cells = ["".join(c["source"]) for c in json.load(f)["cells"] if c["cell_type"] == "code"]
+    ns = {"np": np}
+    for want in ("prior_ranges = [", "def compute_Delta_d", "def parametrization_eta_over_s_vs_mu_B",
+                 "def parametrization_zeta_over_s_vs_T", "def parametrization_y_loss_vs_y_init"):
+        (src,) = [c for c in cells if want in c]
+        exec(compile(src, "PlotMCMC.ipynb", "exec"), ns)
+    pr = np.array(ns["prior_ranges"], dtype=np.float64)
+    rng = np.random.default_rng(1500)
+    S, d = 48, pr.shape[0]
+    samples = pr[:, 0] + (pr[:, 1] - pr[:, 0]) * rng.random((S, d))
+    truth = pr[:, 0] + (pr[:, 1] - pr[:, 0]) * rng.random(d)
+    grids = {"zeta": np.linspace(0., 0.5, 100), "eta": np.linspace(0., 0.6, 100), "yloss": np.linspace(0., 6.2, 100)}
+    calls = {"zeta": lambda p, g: ns["parametrization_zeta_over_s_vs_T"](p[15], p[16], p[17], p[18], g, 0.),
+             "eta": lambda p, g: ns["parametrization_eta_over_s_vs_mu_B"](p[12], p[13], p[14], g),
+             "yloss": lambda p, g: ns["parametrization_y_loss_vs_y_init"](p[2], p[3], p[4], g)}
+    out = {"prior_ranges": pr, "samples": samples, "truth": truth, "levels": np.array([68, 95, 99.7])}
+    for k, g in grids.items():
+        post = np.array([calls[k](samples[s], g) for s in range(S)])
+        pct = [np.percentile(post, 50, axis=0)]
+        for CL in [68, 95, 99.7]:
+            low, high = np.percentile(post, [50 - CL / 2., 50 + CL / 2.], axis=0)
+            pct += [low, high]
+        out[k + "_grid"], out[k + "_curves"], out[k + "_pct"], out[k + "_truth"] = g, post, np.array(pct), calls[k](truth, g)
+    chain = samples.reshape(4, 12, d)                    # [nwalkers, nsteps, ndim], as the notebook's pickles hold a chain
+    out["Delta_d"] = ns["compute_Delta_d"](ns["prior_ranges"], truth, chain)
+    out["Delta_d_distribution"] = np.array(ns["create_Delta_d_distribution"](ns["prior_ranges"], truth, chain))
+    np.savez_compressed(os.path.join(OUT, "g15_curves.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:] == ["g13_design"]:          # (one golden alone: the others stay as committed)
         g13_design()
+        return
+    if sys.argv[1:] == ["g15_curves"]:
+        g15_curves()
         return
     Emulator, mcmc = _import_reference()
     g1_kernels()
@@ -527,6 +566,7 @@ def main():
     g10_learning_curve(Emulator)
     g11_trained_objects(Emulator)
     g13_design()
+    g15_curves()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
