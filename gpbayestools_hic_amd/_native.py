@@ -69,6 +69,7 @@ BOUNDARY = {
     "gpb_chain_curves": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, VP, VP,
                                    c_i64]),
     "gpb_chain_trace_hist": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, VP, VP]),
+    "gpb_sens_accumulate": (C.c_int, [VP, c_i64, c_i64, c_i64, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_maxpro_lhd": (C.c_int, [VP, c_i64, c_i64, C.c_int, C.c_int, VP, c_u64, c_i64, c_i64, C.c_int, C.c_double, C.c_double,

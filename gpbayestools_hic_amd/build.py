@@ -8,7 +8,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpbayes.so")
 LIB_DEBUG = os.path.join(HERE, "libgpbayes_debug.so")
 SOURCES = ["gpb_api.hip", "gpb_fit.hip", "gpb_chol.hip", "gpb_predict.hip", "gpb_sliced.hip", "gpb_like.hip", "gpb_coupled.hip", "gpb_chain.hip", "gpb_stretch.hip", "gpb_cov.hip", "gpb_pmap.hip", "gpb_pool.hip",
-           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip", "gpb_curves.hip"]
+           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip", "gpb_curves.hip", "gpb_sens.hip"]
+# per-source compiler flags.  gpb_sens.hip: its two-double dot products and its bit-for-bit R / I formulas hold only if no product
+# is fused into a sum (hipcc's default -ffp-contract=fast fuses in the backend, past pragmas and the __d*_rn intrinsics)
+SOURCE_FLAGS = {"gpb_sens.hip": ["-ffp-contract=off"]}
 HEADERS = ["gpb_internal.h", "dispatch.h", "dev_buf.h", "ws_carve.h", "ws_layout.h", "coupled_setup.h", "sl_index.h", "gemm_tile.h", "block_reduce.h", "chol_block.h", "fast_math.h", "philox.h", "maxpro_index.h", "curve_fn.h", "order_key.h", os.path.join("..", "..", "include", "gpbayes.h"),
            os.path.join("..", "..", "include", "gpbayes_debug.h")]
 
@@ -38,7 +41,7 @@ def build_native(force=False, verbose=False, debug_variants=False):
         # -fvisibility=hidden: the library exports the entry points of include/gpbayes.h (GPB_API) and, in the debug build,
         # include/gpbayes_debug.h — nothing of the C++ inside
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c",
-               os.path.join(CSRC, src), "-o", obj] + (["-DGPB_DEBUG_VARIANTS"] if debug_variants else [])
+               os.path.join(CSRC, src), "-o", obj] + SOURCE_FLAGS.get(src, []) + (["-DGPB_DEBUG_VARIANTS"] if debug_variants else [])
         if debug_variants:
             cmd += os.environ.get("GPB_DEBUG_EXTRA_DEFINES", "").split()      # A/B builds of the debug library only
         if verbose:

@@ -607,6 +607,59 @@ class GPEngine:
                                           nat.ptr(out.get("order")), nat.ptr(out.get("mixq")), nat.ptr(out.get("pit"))))
         return out
 
+    SENS_LDS_DOUBLES = 8064                       # GPB_SENS_LDS_DOUBLES
+    SENS_MAX_M, SENS_MAX_D, SENS_CHUNK = 2048, 64, 256
+
+    @classmethod
+    def sens_path(cls, M, d):
+        """"lds" when gpb_sens_accumulate keeps a row's Cw [M, M | 1] and L^-1 J [M, d] in LDS, "global" when it factorises the
+        row in place in its slab of C"""
+        M, d = int(M), int(d)
+        return "lds" if M * (M | 1) + M * d <= cls.SENS_LDS_DOUBLES else "global"
+
+    @staticmethod
+    def sens_acc_doubles(M, d):
+        """GPB_SENS_ACC_DOUBLES(M, d): sum wt | sum wt F [d, d] | sum wt R | sum wt R^2 | sum wt I [M, d] each"""
+        return 1 + int(d) * int(d) + 3 * int(M) * int(d)
+
+    def sens_accumulate(self, J, y, C, Cadd, x, wt, acc, cnt):
+        """Adds the rows' Fisher matrices, response matrices and single-observable informations to running sums
+        (gpb_sens_accumulate).  torch cuda tensors, contiguous: J [W, M, d], y [W, M], C [W, M, M] (DESTROYED), Cadd [M, M] or
+        None, x [W, d], wt [W] or None (= 1; non-negative), acc [sens_acc_doubles(M, d)] float64 and cnt [2] int64, both zeroed
+        by the caller before the first slab.  Every slab but the last must hold a multiple of 256 rows (GPBError otherwise); any
+        such split leaves the bits of one call.  The engine lends its device and stream only: M and d are the caller's."""
+        self._track_stream()
+        J = self._dev(J, (None, None, None), "J")
+        W, M, d = (int(v) for v in J.shape)
+        if M < 1 or d < 1 or M > self.SENS_MAX_M or d > self.SENS_MAX_D:
+            raise ValueError("sens_accumulate: need 1 <= M <= %d and 1 <= d <= %d" % (self.SENS_MAX_M, self.SENS_MAX_D))
+        self._dev(y, (W, M), "y")
+        self._dev(C, (W, M, M), "C")
+        self._dev(x, (W, d), "x")
+        if Cadd is not None:
+            self._dev(Cadd, (M, M), "Cadd")
+        if wt is not None:
+            self._dev(wt, (W,), "wt")
+        self._dev(acc, (self.sens_acc_doubles(M, d),), "acc")
+        self._dev(cnt, (2,), "cnt", dtype="torch.int64")
+        self._ck(self.lib.gpb_sens_accumulate(self.h, W, M, d, nat.ptr(J), nat.ptr(y), nat.ptr(C), nat.ptr(Cadd), nat.ptr(x),
+                                              nat.ptr(wt), nat.ptr(acc), nat.ptr(cnt)))
+
+    def sens_unpack(self, acc, cnt, M, d):
+        """The running sums of sens_accumulate as host arrays (sums, not means): "wsum", "fisher" [d, d], "response",
+        "response_sq", "obs_information" [M, d], "n_rows", "n_bad"."""
+        M, d = int(M), int(d)
+        a = acc.cpu().numpy() if _is_torch(acc) else np.asarray(acc, dtype=np.float64)
+        c = cnt.cpu().numpy() if _is_torch(cnt) else np.asarray(cnt)
+        if a.shape != (self.sens_acc_doubles(M, d),) or c.shape != (2,):
+            raise ValueError("sens_unpack: acc [%d] and cnt [2] expected" % self.sens_acc_doubles(M, d))
+        o = 1 + d * d
+        return {"wsum": float(a[0]), "fisher": a[1:o].reshape(d, d).copy(),
+                "response": a[o:o + M * d].reshape(M, d).copy(),
+                "response_sq": a[o + M * d:o + 2 * M * d].reshape(M, d).copy(),
+                "obs_information": a[o + 2 * M * d:o + 3 * M * d].reshape(M, d).copy(),
+                "n_rows": int(c[0]), "n_bad": int(c[1])}
+
     DIAG_NO_WINDOW = 1 << 30                      # GPB_DIAG_NO_WINDOW
 
     def mcmc_diag(self, x_dev, layout="steps", max_lag=None, c=5.0, on_device=False, outputs=None):
@@ -960,11 +1013,26 @@ class GPEngine:
         self._ck(self.lib.gpb_maxpro_run_order(self.h, nat.ptr(X), X.shape[0], X.shape[1], int(first), nat.ptr(order)))
         return order
 
-    def emu_predict_jac(self, Xs):
+    def emu_predict_jac(self, Xs, out=None):
         """Jacobian [W,M,d_in] of the observable-space mean (gpb_emu_predict_jac): through the transform and, when one is set,
-        the parameter map (Xs then holds the original parameters, d_in columns).  numpy in/out."""
+        the parameter map (Xs then holds the original parameters, d_in columns).  numpy in -> numpy out; torch(cuda) in -> torch
+        out (asynchronous), into `out` (a contiguous [W, M, d_in] device tensor) when it is given."""
         self._need_data()
         din = self.pmap_d_in if getattr(self, "pmap_d_in", -1) > 0 else self.d
+        if _is_torch(Xs):
+            import torch
+            self._track_stream()
+            Xs = self._dev(Xs, (None, din), "Xs", contiguous=False)
+            W = Xs.shape[0]
+            if out is None:
+                out = torch.empty((W, self.M, din), dtype=torch.float64, device=Xs.device)
+            else:
+                self._dev(out, (W, self.M, din), "out")
+            if W:
+                self._ck(self.lib.gpb_emu_predict_jac(self.h, nat.ptr(Xs), W, 1, nat.ptr(out)))
+            return out
+        if out is not None:
+            raise ValueError("emu_predict_jac: out= takes a device tensor, together with torch input")
         Xs = nat.f64(Xs).reshape(-1, din)
         W = Xs.shape[0]
         jac = nat.host_empty((W, self.M, din))

@@ -642,6 +642,39 @@ class Chain:
         names = list(self.pardict) if len(getattr(self, "pardict", ())) == xd.shape[-1] else None
         return trace_histogram(xd, bins=bins, range=range, layout="walkers", names=names, device=self.device or 0)
 
+    sens_slab_rows = None                        # most rows of one sensitivity slab (None: sensitivity.slab_rows' rule); same bits
+
+    def sensitivity(self, samples=None, discard=0, thin=1, weights=None):
+        """Which data constrain which parameter: PosteriorSensitivity (sensitivity.py) over ALL rows of `samples` — [S, ndim], or
+        a stored [nwalkers, nsteps, ndim] array without its first `discard` steps and thinned by `thin`; default self.chain, read
+        from mcmc_path when it is not in memory; `weights` [S] go with a flat set.  The observable-by-parameter response matrix of
+        examples/SensitivityAnalysis.ipynb (x_j / y_m dy_m / dx_j, there from 2 d finite-difference predictions at one design
+        point) with its mean and spread over the posterior, and per emulator the Fisher information J^T C^-1 J, C = the
+        emulator's predictive covariance plus its block of expdata_cov, the covariance of the likelihood.  Jacobian, covariance,
+        Cholesky solve and the sums run on the device (gpb_emu_predict, gpb_emu_predict_jac, gpb_sens_accumulate); equal inputs
+        give equal bits whatever the slab size.  fisher is the Gauss-Newton Hessian of the negative log-likelihood with the
+        covariance frozen at each sample, not the full Gaussian Fisher matrix (the 1/2 tr(C^-1 dC C^-1 dC) term is left out).
+        NotImplementedError for foreign emulators, a chain sharded over several ranks and an expdata_cov that couples
+        emulators; ValueError for wrong shapes, non-finite samples, negative or all-zero weights."""
+        from .sensitivity import posterior_sensitivity
+        if samples is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            samples = self.chain
+        x = np.asarray(samples, dtype=np.float64)
+        if x.ndim == 3:
+            if weights is not None:
+                raise ValueError("sensitivity: weights go with a flat [S, ndim] sample set")
+            discard, thin = int(discard), int(thin)
+            if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+                raise ValueError("sensitivity: discard >= 0, thin >= 1 and at least one step must remain")
+            x = x[:, discard::thin].reshape(-1, x.shape[-1])
+        elif x.ndim != 2:
+            raise ValueError("sensitivity: samples must be [S, %d] or [nwalkers, nsteps, %d], got %s"
+                             % (self.ndim, self.ndim, np.shape(samples)))
+        return posterior_sensitivity(self, x, weights=weights)
+
     def posterior_clusters(self, chain=None, discard=0, thin=1, n_clusters=10, n_init=10, **kw):
         """Representative parameter sets of the posterior: PosteriorClusters (clusters.py) of a stored [nwalkers, nsteps, ndim]
         array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first

@@ -303,6 +303,13 @@ class StretchSampler:
         x, _ = self._stored_view(discard, thin)
         return posterior_curves(x, layout="steps", **kw)
 
+    def sensitivity(self, discard=0, thin=1):
+        """PosteriorSensitivity of chain[discard::thin] (sensitivity.py): the response matrix of SensitivityAnalysis.ipynb
+        averaged over all stored samples, and the Fisher information J^T C^-1 J per emulator (gpb_sens_accumulate)."""
+        from .sensitivity import posterior_sensitivity
+        x, _ = self._stored_view(discard, thin)
+        return posterior_sensitivity(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy())
+
     def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
         """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
         chain object's prior box."""

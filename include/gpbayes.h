@@ -451,6 +451,42 @@ GPB_API int gpb_chain_trace_hist(gpb_ctx* ctx, const double* x_dev, int64_t nste
                          int64_t step_stride, int64_t walker_stride, const double* edges_host /*[d,B+1]*/, int B, int on_device,
                          int64_t* hist /*[d,nsteps,B] or NULL*/, int64_t* outside /*[d,nsteps] or NULL*/);
 
+/* ---- response matrix and Fisher information over a set of posterior rows ------------------------------------------------------ *
+ * gpb_sens_accumulate <- examples/SensitivityAnalysis.ipynb: the observable-by-parameter response matrix `(Y+ - Y-) / (2 h) * x /
+ *                        ((Y+ + Y-) / 2)` of 2 d finite-difference predictions at one design point — here in its analytic limit, from
+ *                        the Jacobian gpb_emu_predict_jac gives, summed over all rows of a chain — and the matrix that weighs the
+ *                        response by the uncertainties, J^T C^-1 J with the likelihood's covariance (src/mcmc.py:288-290).
+ *   The context gives the device, the stream and the buffer cache only; M and d are the caller's.  All arrays are device memory.
+ *   Per row w, with Cw = C[w] + Cadd = L L^T (C_dev IS DESTROYED: large rows are factorised in place):
+ *     F_w [d, d]   = J^T Cw^-1 J, formed as (L^-1 J)^T (L^-1 J); both triangles are stored and hold the same bits
+ *     R_w [M, d]   = (x_j J_mj) / y_m                 (a zero y_m gives IEEE inf / NaN in that entry's sums only)
+ *     I_w [M, d]   = (J_mj J_mj) / Cw_mm              (the information observable m alone carries)
+ *   A row whose Cw has a non-positive pivot is BAD: it contributes what a row of weight 0 contributes — nothing, no NaN — and
+ *   adds 1 to cnt[1].  A row with wt == 0 is skipped the same way and is not counted; nothing of it is read into a sum.
+ *   acc_dev [GPB_SENS_ACC_DOUBLES(M, d)], running sums the caller zeroes (with cnt_dev) before the first slab:
+ *     [0] sum wt | [GPB_SENS_ACC_F] sum wt F [d, d] | [GPB_SENS_ACC_R] sum wt R [M, d] | [GPB_SENS_ACC_R2] sum wt (R R) [M, d] |
+ *     [GPB_SENS_ACC_I] sum wt I [M, d];   cnt_dev [2]: rows seen so far (cnt[0] += W), bad rows so far.
+ *   Equal inputs give equal bits, however the rows are split into calls: no floating-point atomics; rows are summed in chunks
+ *   of 256 consecutive rows, each by one fixed tree (sixteen runs of sixteen rows), the chunk sums are added to acc in chunk
+ *   order by one thread per entry, and a call whose cnt[0] at entry is not a multiple of 256 is refused.  Any sequence of slabs
+ *   whose sizes are multiples of 256, except the last, leaves the bits of one call on all rows.  The call reads cnt[0] back
+ *   (one stream synchronisation); the kernels are asynchronous.
+ *   Cw and L^-1 J live in LDS while M (M | 1) + M d <= GPB_SENS_LDS_DOUBLES, in the row's slab of C_dev and a workspace above.
+ *   Errors: GPB_E_ARG for a null pointer (Cadd_dev and wt_dev may be NULL), W < 0 or above 2^31 - 1, M or d < 1, M > 2048,
+ *   d > 64; GPB_E_STATE for a call that does not start on a chunk boundary.  A refused call writes nothing.  W == 0 is a no-op. */
+#define GPB_SENS_MAX_M 2048
+#define GPB_SENS_MAX_D 64
+#define GPB_SENS_LDS_DOUBLES 8064
+#define GPB_SENS_ACC_F 1
+#define GPB_SENS_ACC_R(M, d) (1 + (int64_t)(d) * (d))
+#define GPB_SENS_ACC_R2(M, d) (1 + (int64_t)(d) * (d) + (int64_t)(M) * (d))
+#define GPB_SENS_ACC_I(M, d) (1 + (int64_t)(d) * (d) + 2 * (int64_t)(M) * (d))
+#define GPB_SENS_ACC_DOUBLES(M, d) (1 + (int64_t)(d) * (d) + 3 * (int64_t)(M) * (d))
+GPB_API int gpb_sens_accumulate(gpb_ctx* ctx, int64_t W, int64_t M, int64_t d, const double* J_dev /*[W,M,d]*/,
+                        const double* y_dev /*[W,M]*/, double* C_dev /*[W,M,M], destroyed*/, const double* Cadd_dev /*[M,M] or NULL*/,
+                        const double* x_dev /*[W,d]*/, const double* wt_dev /*[W] or NULL*/,
+                        double* acc_dev /*[GPB_SENS_ACC_DOUBLES(M,d)]*/, int64_t* cnt_dev /*[2]*/);
+
 /* ---- posterior clusters of a resident chain --------------------------------------------------------------------------------- *
  * gpb_chain_kmeans <- examples/generate_posterior_clusters.py: `StandardScaler().fit_transform(chain)`, `KMeans(n_clusters,
  *                     n_init=10).fit(...)`, `scaler.inverse_transform(kmeans.cluster_centers_)` — weighted k-means of the rows of a
