@@ -70,6 +70,9 @@ BOUNDARY = {
                                    c_i64]),
     "gpb_chain_trace_hist": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, VP, VP]),
     "gpb_sens_accumulate": (C.c_int, [VP, c_i64, c_i64, c_i64, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "gpb_gof_accumulate": (C.c_int, [VP, c_i64, c_i64, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "gpb_chi2_sf": (C.c_int, [VP, VP, c_i64, C.c_double, VP]),
+    "gpb_gof_influence": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, VP, c_i64, VP, VP]),
     "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_maxpro_lhd": (C.c_int, [VP, c_i64, c_i64, C.c_int, C.c_int, VP, c_u64, c_i64, c_i64, C.c_int, C.c_double, C.c_double,

@@ -159,6 +159,8 @@ struct gpb_ctx {
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
     gpb::DevBuf<int64_t> maxpro_ws;  // MaxPro Latin-hypercube designs (gpb_maxpro.hip): MaxproWs of ws_layout.h
     gpb::DevBuf<double> sens_ws;     // gpb_sens_accumulate (gpb_sens.hip): per-row F | diag Cw | L^-1 J (large rows) | chunk sums | flags
+    // goodness of fit (gpb_gof.hip): gpb_gof_accumulate's per-row z | pulls | p | chunk sums | flags, or gpb_gof_influence's minima | chunk sums
+    gpb::DevBuf<double> gof_ws;
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

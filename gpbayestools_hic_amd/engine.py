@@ -660,6 +660,100 @@ class GPEngine:
                 "obs_information": a[o + 2 * M * d:o + 3 * M * d].reshape(M, d).copy(),
                 "n_rows": int(c[0]), "n_bad": int(c[1])}
 
+    GOF_LDS_DOUBLES = 8064                        # GPB_GOF_LDS_DOUBLES
+    GOF_MAX_M, GOF_MAX_D, GOF_MAX_E, GOF_CHUNK = 2048, 512, 64, 256
+
+    @classmethod
+    def gof_path(cls, M):
+        """"lds" when gpb_gof_accumulate keeps a row's Cw and z ([M + 1, M | 1]) in LDS, "global" when it factorises the row in
+        place in its slab of C"""
+        M = int(M)
+        return "lds" if (M + 1) * (M | 1) <= cls.GOF_LDS_DOUBLES else "global"
+
+    @staticmethod
+    def gof_acc_doubles(M):
+        """GPB_GOF_ACC_DOUBLES(M): sum wt | sum wt p | sum wt z | sum wt z^2 | sum wt pull | sum wt pull^2 [M] each"""
+        return 2 + 4 * int(M)
+
+    def gof_accumulate(self, y, C, yexp, Cadd, wt, chi2_out, ll_out, acc, cnt):
+        """chi2 and log-likelihood of every row against one data set, and the running sums of the whitened residuals, the pulls
+        and the predictive p-value (gpb_gof_accumulate).  torch cuda tensors: y [W, M], C [W, M, M] (DESTROYED), yexp [M], Cadd
+        [M, M] or None, wt [W] or None (= 1; non-negative), chi2_out and ll_out [W] with unit stride (a slab of a row of an
+        [E, S] array), acc [gof_acc_doubles(M)] float64 and cnt [2] int64, both zeroed by the caller before the first slab.
+        Every slab but the last must hold a multiple of 256 rows (GPBError otherwise); any such split leaves the bits of one
+        call.  The engine lends its device and stream only: M is the caller's."""
+        self._track_stream()
+        y = self._dev(y, (None, None), "y")
+        W, M = (int(v) for v in y.shape)
+        if M < 1 or M > self.GOF_MAX_M:
+            raise ValueError("gof_accumulate: need 1 <= M <= %d" % self.GOF_MAX_M)
+        self._dev(C, (W, M, M), "C")
+        self._dev(yexp, (M,), "yexp")
+        if Cadd is not None:
+            self._dev(Cadd, (M, M), "Cadd")
+        if wt is not None:
+            self._dev(wt, (W,), "wt")
+        self._dev(chi2_out, (W,), "chi2_out")
+        self._dev(ll_out, (W,), "ll_out")
+        self._dev(acc, (self.gof_acc_doubles(M),), "acc")
+        self._dev(cnt, (2,), "cnt", dtype="torch.int64")
+        self._ck(self.lib.gpb_gof_accumulate(self.h, W, M, nat.ptr(y), nat.ptr(C), nat.ptr(yexp), nat.ptr(Cadd), nat.ptr(wt),
+                                             nat.ptr(chi2_out), nat.ptr(ll_out), nat.ptr(acc), nat.ptr(cnt)))
+
+    @staticmethod
+    def gof_unpack(acc, cnt, M):
+        """The running sums of gof_accumulate as host arrays (sums, not means): "wsum", "p", "z", "z_sq", "pull", "pull_sq" [M],
+        "n_rows", "n_bad"."""
+        M = int(M)
+        a = acc.cpu().numpy() if _is_torch(acc) else np.asarray(acc, dtype=np.float64)
+        c = cnt.cpu().numpy() if _is_torch(cnt) else np.asarray(cnt)
+        if a.shape != (2 + 4 * M,) or c.shape != (2,):
+            raise ValueError("gof_unpack: acc [%d] and cnt [2] expected" % (2 + 4 * M))
+        return {"wsum": float(a[0]), "p": float(a[1]), "z": a[2:2 + M].copy(), "z_sq": a[2 + M:2 + 2 * M].copy(),
+                "pull": a[2 + 2 * M:2 + 3 * M].copy(), "pull_sq": a[2 + 3 * M:2 + 4 * M].copy(),
+                "n_rows": int(c[0]), "n_bad": int(c[1])}
+
+    def chi2_sf(self, x, ndf, out=None):
+        """Q(ndf / 2, x / 2) per element of the torch cuda tensor x [n] (gpb_chi2_sf): the chi-square survival function; NaN in
+        gives NaN out, x <= 0 gives 1.  Returns a device tensor (out, when given).  Asynchronous."""
+        import torch
+        self._track_stream()
+        x = self._dev(x, (None,), "x", contiguous=False)
+        ndf = float(ndf)
+        if not (ndf > 0.0 and np.isfinite(ndf)):
+            raise ValueError("chi2_sf: ndf must be finite and positive")
+        if out is None:
+            out = torch.empty_like(x)
+        self._dev(out, (x.shape[0],), "out")
+        self._ck(self.lib.gpb_chi2_sf(self.h, nat.ptr(x), int(x.shape[0]), ndf, nat.ptr(out)))
+        return out
+
+    def gof_influence(self, ll_T, x, wt=None, S=None):
+        """The moments of the rows x [S, d] under the importance weights wt exp(-(ll_T[e] - min ll_T[e])) of the posterior
+        without data set e (gpb_gof_influence): ll_T a torch cuda view [E, >= S] with unit stride along the rows, wt [S] or
+        None.  Returns a device tensor [E, 2 + 2 d]: sum w | sum w^2 | sum w x_j | sum w x_j^2.  Rows with a NaN ll or wt == 0
+        are left out.  Asynchronous; equal inputs give equal bits, and a row of the result does not depend on the others."""
+        import torch
+        self._track_stream()
+        if not _is_torch(ll_T) or ll_T.dim() != 2:
+            raise ValueError("ll_T: expected a two-dimensional torch tensor")
+        E = int(ll_T.shape[0])
+        S = int(ll_T.shape[1]) if S is None else int(S)
+        if not ll_T.is_cuda or ll_T.device.index != self.device or str(ll_T.dtype) != "torch.float64":
+            raise ValueError("ll_T: expected a torch.float64 tensor on cuda:%d" % self.device)
+        if S < 1 or ll_T.shape[1] < S or (ll_T.shape[1] > 1 and ll_T.stride(1) != 1):
+            raise ValueError("ll_T: expected a [%d, >= %d] view with unit stride along the rows, S >= 1" % (E, S))
+        ld = int(ll_T.stride(0)) if E > 1 else max(int(ll_T.shape[1]), S)
+        x = self._dev(x, (S, None), "x")
+        d = int(x.shape[1])
+        if E < 1 or E > self.GOF_MAX_E or d < 1 or d > self.GOF_MAX_D or ld < S:
+            raise ValueError("gof_influence: need 1 <= E <= %d, 1 <= d <= %d and a row stride >= S" % (self.GOF_MAX_E, self.GOF_MAX_D))
+        if wt is not None:
+            self._dev(wt, (S,), "wt")
+        out = torch.empty((E, 2 + 2 * d), dtype=torch.float64, device=x.device)
+        self._ck(self.lib.gpb_gof_influence(self.h, nat.ptr(ll_T), E, S, ld, nat.ptr(x), d, nat.ptr(wt), nat.ptr(out)))
+        return out
+
     DIAG_NO_WINDOW = 1 << 30                      # GPB_DIAG_NO_WINDOW
 
     def mcmc_diag(self, x_dev, layout="steps", max_lag=None, c=5.0, on_device=False, outputs=None):

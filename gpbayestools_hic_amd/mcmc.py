@@ -675,6 +675,41 @@ class Chain:
                              % (self.ndim, self.ndim, np.shape(samples)))
         return posterior_sensitivity(self, x, weights=weights)
 
+    gof_slab_rows = None                         # most rows of one goodness-of-fit slab (None: gof.slab_rows' rule); same bits
+
+    def goodness_of_fit(self, samples=None, discard=0, thin=1, weights=None, **kw):
+        """Does the calibrated model describe the data, data set by data set: GoodnessOfFit (gof.py) over ALL rows of `samples` —
+        [S, ndim], or a stored [nwalkers, nsteps, ndim] array without its first `discard` steps and thinned by `thin`; default
+        self.chain, read from mcmc_path when it is not in memory; `weights` [S] go with a flat set.  Per emulator chi2 = dY^T C^-1
+        dY with C = the emulator's predictive covariance plus its block of expdata_cov — the covariance of the likelihood, the
+        two pieces mvn_loglike computes (src/mcmc.py:23-65) kept apart — its quantiles over the posterior, chi2 per degree of
+        freedom (ndf = the number of observables; no parameters are subtracted, the chi2 is the posterior's, not a minimum), the
+        closed-form posterior-predictive p-value, the whitened residuals and pulls per observable, the totals over the emulators
+        and what the posterior would be without each data set (importance reweighting; its ess says when that has collapsed).
+        Predict, Cholesky, p-values and sums run on the device (gpb_emu_predict, gpb_gof_accumulate, gpb_chi2_sf,
+        gpb_gof_influence); equal inputs give equal bits whatever the slab size.  kw: quantiles, influence, return_rows, profile
+        (gof.posterior_gof).  A coupled expdata_cov: per-emulator marginal checks, the total from the joint matrix, no influence.
+        NotImplementedError for foreign emulators and a chain sharded over several ranks; ValueError for wrong shapes,
+        non-finite samples, negative or all-zero weights, quantile levels outside [0, 1]."""
+        from .gof import posterior_gof
+        if samples is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            samples = self.chain
+        x = np.asarray(samples, dtype=np.float64)
+        if x.ndim == 3:
+            if weights is not None:
+                raise ValueError("goodness_of_fit: weights go with a flat [S, ndim] sample set")
+            discard, thin = int(discard), int(thin)
+            if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+                raise ValueError("goodness_of_fit: discard >= 0, thin >= 1 and at least one step must remain")
+            x = x[:, discard::thin].reshape(-1, x.shape[-1])
+        elif x.ndim != 2:
+            raise ValueError("goodness_of_fit: samples must be [S, %d] or [nwalkers, nsteps, %d], got %s"
+                             % (self.ndim, self.ndim, np.shape(samples)))
+        return posterior_gof(self, x, weights=weights, **kw)
+
     def posterior_clusters(self, chain=None, discard=0, thin=1, n_clusters=10, n_init=10, **kw):
         """Representative parameter sets of the posterior: PosteriorClusters (clusters.py) of a stored [nwalkers, nsteps, ndim]
         array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first

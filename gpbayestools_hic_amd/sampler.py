@@ -310,6 +310,14 @@ class StretchSampler:
         x, _ = self._stored_view(discard, thin)
         return posterior_sensitivity(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy())
 
+    def goodness_of_fit(self, discard=0, thin=1, **kw):
+        """GoodnessOfFit of chain[discard::thin] (gof.py): chi2 per data set and degree of freedom with the likelihood's
+        covariance over all stored samples, its predictive p-value, whitened residuals and the influence of each data set
+        (gpb_gof_accumulate, gpb_gof_influence).  kw as Chain.goodness_of_fit takes them."""
+        from .gof import posterior_gof
+        x, _ = self._stored_view(discard, thin)
+        return posterior_gof(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
+
     def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
         """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
         chain object's prior box."""

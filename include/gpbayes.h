@@ -487,6 +487,68 @@ GPB_API int gpb_sens_accumulate(gpb_ctx* ctx, int64_t W, int64_t M, int64_t d, c
                         const double* x_dev /*[W,d]*/, const double* wt_dev /*[W] or NULL*/,
                         double* acc_dev /*[GPB_SENS_ACC_DOUBLES(M,d)]*/, int64_t* cnt_dev /*[2]*/);
 
+/* ---- goodness of fit and data-set influence over a set of posterior rows -------------------------------------------------------- *
+ * gpb_gof_accumulate <- src/mcmc.py:23-65 (mvn_loglike): its two pieces, 1/2 dY^T C^-1 dY and sum ln L_ii, which the reference adds
+ *                       up over all emulators and returns as one number — here kept per row and emulator, with the whitened
+ *                       residuals and the closed-form predictive p-value, so that a calibration can be judged data set by data set
+ *                       (examples/ClosureTest.ipynb judges it by eye from fifteen predictive curves).
+ *   The context gives the device, the stream and the buffer cache only; M is the caller's.  All arrays are device memory.
+ *   Per row w, with dY = y[w] - yexp and Cw = C[w] + Cadd = L L^T (C_dev IS DESTROYED: large rows are factorised in place):
+ *     z [M]      = L^-1 dY, the whitened sequential residuals: z_m is the residual of observable m given observables 0 .. m - 1,
+ *                  each N(0, 1) if the model describes the data
+ *     chi2       = z^T z                          -> chi2_out[w]
+ *     ll         = -1/2 chi2 - sum ln L_ii        -> ll_out[w]   (mvn_loglike's value, without the 2 pi constant; log det Cw =
+ *                  -2 ll - chi2)
+ *     p          = Q(M / 2, chi2 / 2), gpb_chi2_sf's function: the posterior-predictive p-value of the chi2 discrepancy in closed
+ *                  form (for y_rep ~ N(mu_w, Cw) the replicate's chi2 is chi2_M exactly; nothing is sampled)
+ *     pull [M]   = dY_m / sqrt(Cw_mm), the marginal pulls
+ *   chi2_out and ll_out are written at stride 1, W entries each: a caller fills row e of an [E, ld] array slab by slab.
+ *   A row whose Cw has a non-positive pivot is BAD: NaN in chi2_out and ll_out, nothing in any sum, 1 added to cnt[1].  A row with
+ *   wt == 0 is not evaluated: NaN in chi2_out and ll_out, nothing of it is read into a sum, and it is not counted as bad.
+ *   acc_dev [GPB_GOF_ACC_DOUBLES(M)], running sums the caller zeroes (with cnt_dev) before the first slab:
+ *     [GPB_GOF_ACC_W] sum wt | [GPB_GOF_ACC_P] sum wt p | [GPB_GOF_ACC_Z] sum wt z [M] | [GPB_GOF_ACC_Z2] sum wt (z z) [M] |
+ *     [GPB_GOF_ACC_PULL] sum wt pull [M] | [GPB_GOF_ACC_PULL2] sum wt (pull pull) [M];   cnt_dev [2]: rows seen so far, bad rows so far.
+ *   Equal inputs give equal bits, however the rows are split into calls — gpb_sens_accumulate's rules: no floating-point atomics;
+ *   chunks of 256 consecutive rows, each summed by one fixed tree (sixteen runs of sixteen rows); the chunk sums added to acc in
+ *   chunk order by one thread per entry; a call whose cnt[0] at entry is not a multiple of 256 is refused.  Any sequence of slabs
+ *   whose sizes are multiples of 256, except the last, leaves the bits of one call on all rows.  The call reads cnt[0] back (one
+ *   stream synchronisation); the kernels are asynchronous.
+ *   Cw and z live in LDS while (M + 1) (M | 1) <= GPB_GOF_LDS_DOUBLES (M <= 89), in the row's slab of C_dev and a workspace above.
+ *   The dot products of the factorisation and of z are carried in two doubles, as gpb_sens_accumulate carries them.
+ *   Errors: GPB_E_ARG for a null pointer (Cadd_dev and wt_dev may be NULL), W < 0 or above 2^31 - 1, M < 1, M > 2048; GPB_E_STATE
+ *   for a call that does not start on a chunk boundary.  A refused call writes nothing.  W == 0 is a no-op.
+ * gpb_chi2_sf: out[i] = Q(ndf / 2, x[i] / 2), the survival function of the chi-square distribution with ndf degrees of freedom
+ *   (regularised upper incomplete gamma function; csrc/chi2_sf.h: the series below x / 2 < ndf / 2 + 1, a continued fraction above,
+ *   at most GPB_CHI2_SF_MAX_ITER steps of either).  NaN in gives NaN out; x <= 0 gives 1.  ndf finite and positive, not necessarily
+ *   an integer.  Relative error a few 1e-15 at small ndf, growing to ~1e-12 at ndf = 2048 (the prefactor exp(a ln t - t -
+ *   lgamma(a)) carries the rounding of terms of size ~1e4).  Errors (GPB_E_ARG): a null pointer, n < 0 or above 2^31 - 1, such an ndf.
+ * gpb_gof_influence: what the posterior would be WITHOUT data set e, by importance reweighting.  ll_T [E, ld]: row e holds the
+ *   ll of emulator e for the S rows (gpb_gof_accumulate's ll_out).  Per emulator the weights w_s = wt_s exp(-(ll_T[e, s] - min)),
+ *   min the minimum of ll_T[e, .] over the rows used, and
+ *     out_dev [E, 2 + 2 d]:  sum w | sum w w | sum w x_j [d] | sum w (x_j x_j) [d]
+ *   A row with a NaN ll or wt == 0 is skipped by a branch.  The minimum is exact and order free; the sums are the chunk trees above
+ *   over s, added in chunk order: equal inputs give equal bits, and a row of out depends neither on E nor on the other rows of ll_T.
+ *   An emulator without a usable row leaves zeros.  Errors (GPB_E_ARG): a null pointer (wt_dev may be NULL), E outside 1 .. 64,
+ *   d outside 1 .. 512, S < 1 or above 2^31 - 1, ld < S. */
+#define GPB_GOF_MAX_M 2048
+#define GPB_GOF_MAX_D 512
+#define GPB_GOF_MAX_E 64
+#define GPB_GOF_LDS_DOUBLES 8064
+#define GPB_GOF_ACC_W 0
+#define GPB_GOF_ACC_P 1
+#define GPB_GOF_ACC_Z 2
+#define GPB_GOF_ACC_Z2(M) (2 + (int64_t)(M))
+#define GPB_GOF_ACC_PULL(M) (2 + 2 * (int64_t)(M))
+#define GPB_GOF_ACC_PULL2(M) (2 + 3 * (int64_t)(M))
+#define GPB_GOF_ACC_DOUBLES(M) (2 + 4 * (int64_t)(M))
+GPB_API int gpb_gof_accumulate(gpb_ctx* ctx, int64_t W, int64_t M, const double* y_dev /*[W,M]*/, double* C_dev /*[W,M,M], destroyed*/,
+                       const double* yexp_dev /*[M]*/, const double* Cadd_dev /*[M,M] or NULL*/, const double* wt_dev /*[W] or NULL*/,
+                       double* chi2_out /*[W]*/, double* ll_out /*[W]*/, double* acc_dev /*[GPB_GOF_ACC_DOUBLES(M)]*/,
+                       int64_t* cnt_dev /*[2]*/);
+GPB_API int gpb_chi2_sf(gpb_ctx* ctx, const double* x_dev /*[n]*/, int64_t n, double ndf, double* out_dev /*[n]*/);
+GPB_API int gpb_gof_influence(gpb_ctx* ctx, const double* ll_T /*[E,ld]*/, int64_t E, int64_t S, int64_t ld, const double* x_dev /*[S,d]*/,
+                      int64_t d, const double* wt_dev /*[S] or NULL*/, double* out_dev /*[E,2+2d]*/);
+
 /* ---- posterior clusters of a resident chain --------------------------------------------------------------------------------- *
  * gpb_chain_kmeans <- examples/generate_posterior_clusters.py: `StandardScaler().fit_transform(chain)`, `KMeans(n_clusters,
  *                     n_init=10).fit(...)`, `scaler.inverse_transform(kmeans.cluster_centers_)` — weighted k-means of the rows of a
