@@ -97,6 +97,10 @@ BOUNDARY = {
     "gpb_chain_emcee_run": (C.c_int, [VP, C.c_int, VP, VP, c_i64, c_i64, c_u64, c_u64, C.c_double, C.c_int, VP, VP,
                                       C.c_double, C.c_double, VP, VP, VP]),
     "gpb_chain_emcee_prepare": (C.c_int, [VP, C.c_int, c_i64]),
+    "gpb_chain_like_sets": (C.c_int, [VP, C.c_int, c_i64, VP]),
+    "gpb_chain_logpost_sets": (C.c_int, [VP, C.c_int, VP, c_i64, c_i64, VP, VP, VP, C.c_double, C.c_double]),
+    "gpb_chain_emcee_sets_run": (C.c_int, [VP, C.c_int, VP, VP, c_i64, c_i64, c_i64, VP, c_u64, C.c_double, C.c_int, VP, VP,
+                                           C.c_double, C.c_double, VP, VP, VP]),
     "gpb_chain_logpost_grad": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, VP, C.c_double, C.c_double]),
     "gpb_chain_ptlmc_run": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_i64, c_u64, c_u64, c_i64, C.c_double, VP, VP, VP, VP,
                                       VP, VP, VP, VP, VP, VP, C.c_double, C.c_double, VP, c_i64, VP, VP]),
@@ -126,6 +130,7 @@ DEBUG = {
     "gpb_debug_tile_trace": (C.c_int, [VP, c_i64]),
     "gpb_debug_tile_trace_read": (C.c_int, [VP, VP, c_i64, VP]),
     "gpb_debug_pool_live": (C.c_int, [VP, VP]),
+    "gpb_debug_like_tables": (C.c_int, [VP, c_i64, VP, VP]),
     "gpb_probe_fp64": (C.c_int, [VP, C.c_int, VP]),
 }
 PROTOTYPES = dict(BOUNDARY, **DEBUG)

@@ -158,6 +158,7 @@ static int gp_set_impl(gpb_ctx* ctx, int64_t P, int64_t d, const int64_t* N_p, c
     // whatever was installed for the previous GPs (observable transform sized [old P][M], likelihood block, low-rank
     // factors, parameter map) does not describe the new ones: it has to be set again
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
+    ctx->lrs_K = 0;                                    // (the per-data-set tables of gpb_chain_like_sets go with the likelihood)
     ++ctx->like_epoch;                                 // (a coupled chain likelihood built on this context is stale)
     ctx->M = 0;
     ctx->A.release(); ctx->mu.release(); ctx->scale.release(); ctx->C0.release(); ctx->yexp.release();
@@ -602,6 +603,7 @@ extern "C" int gpb_emu_set_transform(gpb_ctx* ctx, int mode, int64_t M, const do
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t P = ctx->P;
     ctx->have_transform = ctx->have_like = ctx->lr_ok = false;
+    ctx->lrs_K = 0;                                    // (the per-data-set tables of gpb_chain_like_sets go with the likelihood)
     ++ctx->like_epoch;                                 // (a coupled chain likelihood built on this context is stale)
     int rc;
     if ((rc = ctx_replace(ctx, ctx->A, P * M))) return rc;
@@ -620,93 +622,24 @@ extern "C" int gpb_emu_set_transform(gpb_ctx* ctx, int mode, int64_t M, const do
     return 0;
 }
 
-// Low-rank form of the block likelihood (PCA mode, src/emulator.py:584-587 + src/mcmc.py:23-65): the covariance of
-// every walker is C = C0 + A^T D A with the SAME C0 = C_trunc + C_exp and a walker-dependent D = diag(var_p) of
-// rank P << M.  With C0 = L0 L0^T and the thin QR factorisation L0^-1 A^T = Q R (M x P, P x P):
-//     L0^-1 C L0^-T = I + Q (R D R^T) Q^T
-//     log det C = log det C0 + log det S,                 S = I_P + R D R^T
-//     y^T C^-1 y = |(I - Q Q^T) L0^-1 y|^2 + v^T S^-1 v,  v = Q^T L0^-1 y = R m + v0
-// because y = A^T m + (mu - yexp) and L0^-1 A^T m = Q R m lies in the span of Q: the first term is a constant of
-// the emulator.  No difference of large numbers anywhere (unlike the Woodbury identity); against 40-digit
-// arithmetic the form is as accurate as the dense Cholesky (1e-15 relative).  Per walker this is a P x P Cholesky
-// instead of an M x M one.  Returns false (dense kernels stay in charge) when C0 is not positive definite or A is
-// rank deficient.
+// Low-rank form of the block likelihood (lowrank_setup.h has the algebra and the arithmetic): the factorisation of
+// C0 = C_trunc + C_exp stays in the context on the host (long double, M^2 + P M values), so that further data vectors
+// against the same covariance (gpb_chain_like_sets) need no second Cholesky; then the data terms of yexp.  Returns false
+// (dense kernels stay in charge) when C0 is not positive definite or A is rank deficient.
 static bool lowrank_setup(gpb_ctx* ctx, const double* yexp, const double* cexp) {
     const int64_t M = ctx->M, P = ctx->P;
+    ctx->lr_fac.clear();
     if (ctx->mode != GPB_MODE_PCA || P > 16 || P > M) return false;
-    std::vector<long double> L((size_t)(M * M), 0.0L);
-    for (int64_t i = 0; i < M; ++i)
-        for (int64_t j = 0; j <= i; ++j) {                         // symmetrised lower triangle of C0
-            const double a = ctx->h_C0[i * M + j] + cexp[i * M + j], b = ctx->h_C0[j * M + i] + cexp[j * M + i];
-            L[i * M + j] = 0.5L * ((long double)a + (long double)b);
-        }
-    long double logdet = 0.0L;
-    for (int64_t j = 0; j < M; ++j) {                              // Cholesky, column by column
-        long double dsum = L[j * M + j];
-        for (int64_t k = 0; k < j; ++k) dsum -= L[j * M + k] * L[j * M + k];
-        if (!(dsum > 0.0L)) return false;
-        const long double ljj = sqrtl(dsum);
-        L[j * M + j] = ljj;
-        logdet += 2.0L * logl(ljj);
-        for (int64_t i = j + 1; i < M; ++i) {
-            long double v = L[i * M + j];
-            for (int64_t k = 0; k < j; ++k) v -= L[i * M + k] * L[j * M + k];
-            L[i * M + j] = v / ljj;
-        }
-    }
-    auto fwd = [&](std::vector<long double>& x) {                  // x <- L0^-1 x
-        for (int64_t i = 0; i < M; ++i) {
-            long double v = x[i];
-            for (int64_t k = 0; k < i; ++k) v -= L[i * M + k] * x[k];
-            x[i] = v / L[i * M + i];
-        }
-    };
-    std::vector<std::vector<long double>> Q((size_t)P, std::vector<long double>((size_t)M));
-    std::vector<long double> R((size_t)(P * P), 0.0L);
-    for (int64_t j = 0; j < P; ++j) {                              // column j of L0^-1 A^T, then Gram-Schmidt twice
-        std::vector<long double>& q = Q[j];
-        for (int64_t i = 0; i < M; ++i) q[i] = ctx->h_A[j * M + i];
-        fwd(q);
-        long double norm0 = 0.0L;
-        for (int64_t i = 0; i < M; ++i) norm0 += q[i] * q[i];
-        for (int pass = 0; pass < 2; ++pass)
-            for (int64_t i = 0; i < j; ++i) {
-                long double r = 0.0L;
-                for (int64_t k = 0; k < M; ++k) r += Q[i][k] * q[k];
-                for (int64_t k = 0; k < M; ++k) q[k] -= r * Q[i][k];
-                R[i * P + j] += r;
-            }
-        long double nrm = 0.0L;
-        for (int64_t i = 0; i < M; ++i) nrm += q[i] * q[i];
-        if (!(nrm > 1e-24L * norm0) || !(norm0 > 0.0L)) return false;      // A (numerically) rank deficient
-        nrm = sqrtl(nrm);
-        R[j * P + j] = nrm;
-        for (int64_t i = 0; i < M; ++i) q[i] /= nrm;
-    }
-    std::vector<long double> w((size_t)M);
-    for (int64_t i = 0; i < M; ++i) w[i] = (long double)ctx->h_mu[i] - (long double)yexp[i];
-    fwd(w);
-    std::vector<long double> v0((size_t)P, 0.0L);
-    for (int64_t j = 0; j < P; ++j)
-        for (int64_t k = 0; k < M; ++k) v0[j] += Q[j][k] * w[k];
-    long double cperp = 0.0L;
-    for (int64_t k = 0; k < M; ++k) {
-        long double t = w[k];
-        for (int64_t j = 0; j < P; ++j) t -= Q[j][k] * v0[j];
-        cperp += t * t;
-    }
-    double Rh[256], vh[16];
-    for (int i = 0; i < 256; ++i) Rh[i] = 0.0;
+    if (!lowrank_factor(M, P, ctx->h_A.data(), ctx->h_C0.data(), cexp, ctx->lr_fac)) return false;
+    double Rh[256], vh[16], cperp;
     for (int i = 0; i < 16; ++i) vh[i] = 0.0;
-    for (int64_t i = 0; i < P; ++i) {
-        vh[i] = (double)v0[i];
-        for (int64_t j = i; j < P; ++j) Rh[i * 16 + j] = (double)R[i * P + j];
-    }
+    lowrank_R16(ctx->lr_fac, Rh);
+    lowrank_data_terms(ctx->lr_fac, ctx->h_mu.data(), yexp, vh, &cperp);
     if (ctx_replace(ctx, ctx->lr_R, 256) || ctx_replace(ctx, ctx->lr_v0, 16)) return false;
     if (hipMemcpy(ctx->lr_R, Rh, sizeof(Rh), hipMemcpyHostToDevice) != hipSuccess) return false;
     if (hipMemcpy(ctx->lr_v0, vh, sizeof(vh), hipMemcpyHostToDevice) != hipSuccess) return false;
-    ctx->lr_cperp = (double)cperp;
-    ctx->lr_logdet0 = (double)logdet;
+    ctx->lr_cperp = cperp;
+    ctx->lr_logdet0 = (double)ctx->lr_fac.logdet0;
     return true;
 }
 
@@ -867,6 +800,7 @@ extern "C" int gpb_like_set(gpb_ctx* ctx, const double* yexp_host, const double*
     GPB_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t M = ctx->M;
     ctx->have_like = ctx->lr_ok = false;
+    ctx->lrs_K = 0;                                    // the per-data-set tables (gpb_chain_like_sets) are dropped
     ++ctx->like_epoch;
     int rc;
     if ((rc = ctx_replace(ctx, ctx->yexp, M))) return rc;

@@ -4,6 +4,7 @@
 //   the same parameter space (those with a parameter map, src/emulator.py:492-551, through gpb_param_map).
 //   chain_ctx_check   what every entry point that takes a list of contexts asks of it
 //   chain_rows        the compacted chain call: the rows inside the prior box only, the emulators' launches batched
+//   chain_rows_sets   chain_rows for rows that belong to different data sets (gpb_chain_like_sets; gpb_sets.hip)
 //   chain_eval        the chain call where it applies, else the per-emulator sequence
 #include "gpb_internal.h"
 
@@ -53,26 +54,10 @@ int chain_ctx_check(gpb_ctx* const* ctxs, int E, const char* who, bool need_like
 }
 int chain_check(gpb_ctx* const* ctxs, int E, const char* who) { return refuse(ctxs[0], who, chain_refusal(ctxs, E)); }
 
-// log-posterior of rows X[W][ndim] over all emulators, rows inside the box only (ctxs[0] owns the compaction)
-int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
-               const double* hi_dev, double outside, double inside_const, int premarked, const int* cmpv) {
+// Passes (1) and (2) of a compacted chain batch (chain_rows has the list), over the rows gathered in ctxs[0]->cmp_X
+static int chain_predict_passes(gpb_ctx* const* ctxs, int E, int64_t W, const int* cmpv) {
     gpb_ctx* c0 = ctxs[0];
     int rc;
-    if ((rc = coupling_check(ctxs, E, "gpb_chain_logpost"))) return rc;
-    for (int e = 0; e < E; ++e)
-        if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
-    if ((rc = ensure_lr_blocks(c0, E))) return rc;
-    if ((rc = launch_compact(c0, X_dev, W, sampler_ndim(c0), lo_dev, hi_dev, outside, ll_dev, premarked))) return rc;
-    if (!cmpv) cmpv = c0->cmp_idx;                     // (count, -, -, -, indices ...) of the rows inside the box
-    // Three passes over the emulators (each kernel sees what it would see in its own emulator's sequence: same bits):
-    // (1) parameter maps, then K*^T and the mean partials — ONE launch per run of emulators of equal padded size
-    //     (k_kcross_multi);
-    // (2) V = L^-1 K*^T with the fused sum of squares: ONE launch for each run of emulators whose designs pad to the same
-    //     Np (the reference's analyses: nine emulators on one design) instead of one partly filled launch per emulator;
-    // (3) the block log-likelihoods, added up in emuList order: one launch that walks the emulators (k_loglike_lowrank_multi)
-    //     when every block takes the low-rank kernel, else one launch per emulator.  A chain whose experimental covariance
-    //     couples its emulators (gpb_chain_like_set) has no blocks to add: the GPs' sums per emulator (k_finalize), then
-    //     one launch of the joint kernel (gpb_coupled.hip).
     const double* Xg[MAX_CHAIN_CTX];
     gpb_ctx* mapped[MAX_CHAIN_CTX];
     int nmapped = 0;
@@ -106,6 +91,30 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
         if ((rc = launch_vsq(ctxs + e, n, W, cmpv))) { c0->err = ctxs[e]->err; return rc; }
         e += n;
     }
+    return 0;
+}
+
+// log-posterior of rows X[W][ndim] over all emulators, rows inside the box only (ctxs[0] owns the compaction)
+int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
+               const double* hi_dev, double outside, double inside_const, int premarked, const int* cmpv) {
+    gpb_ctx* c0 = ctxs[0];
+    int rc;
+    if ((rc = coupling_check(ctxs, E, "gpb_chain_logpost"))) return rc;
+    for (int e = 0; e < E; ++e)
+        if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
+    if ((rc = ensure_lr_blocks(c0, E))) return rc;
+    if ((rc = launch_compact(c0, X_dev, W, sampler_ndim(c0), lo_dev, hi_dev, outside, ll_dev, premarked))) return rc;
+    if (!cmpv) cmpv = c0->cmp_idx;                     // (count, -, -, -, indices ...) of the rows inside the box
+    // Three passes over the emulators (each kernel sees what it would see in its own emulator's sequence: same bits):
+    // (1) parameter maps, then K*^T and the mean partials — ONE launch per run of emulators of equal padded size
+    //     (k_kcross_multi);
+    // (2) V = L^-1 K*^T with the fused sum of squares: ONE launch for each run of emulators whose designs pad to the same
+    //     Np (the reference's analyses: nine emulators on one design) instead of one partly filled launch per emulator;
+    // (3) the block log-likelihoods, added up in emuList order: one launch that walks the emulators (k_loglike_lowrank_multi)
+    //     when every block takes the low-rank kernel, else one launch per emulator.  A chain whose experimental covariance
+    //     couples its emulators (gpb_chain_like_set) has no blocks to add: the GPs' sums per emulator (k_finalize), then
+    //     one launch of the joint kernel (gpb_coupled.hip).
+    if ((rc = chain_predict_passes(ctxs, E, W, cmpv))) return rc;
     if (coupling_installed(c0)) {
         for (int e = 0; e < E; ++e)
             if ((rc = launch_finalize(ctxs[e], W, true))) { c0->err = ctxs[e]->err; return rc; }
@@ -123,6 +132,33 @@ int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, doub
             return rc;
         }
     }
+    return 0;
+}
+
+// chain_rows for rows that belong to different data sets (row w: set w / rows_per_set of gpb_chain_like_sets' tables): the
+// same compaction and passes (1)-(2) — the prediction does not depend on the data — then the sets' likelihood kernel
+int chain_rows_sets(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, int64_t rows_per_set, double* ll_dev,
+                    const double* lo_dev, const double* hi_dev, double outside, double inside_const, int premarked, const int* cmpv) {
+    gpb_ctx* c0 = ctxs[0];
+    int rc;
+    for (int e = 0; e < E; ++e)
+        if ((rc = ensure_wcap(ctxs[e], W))) { if (e) c0->err = ctxs[e]->err; return rc; }
+    if ((rc = ensure_lr_blocks(c0, E))) return rc;
+    if ((rc = launch_compact(c0, X_dev, W, sampler_ndim(c0), lo_dev, hi_dev, outside, ll_dev, premarked))) return rc;
+    if (!cmpv) cmpv = c0->cmp_idx;
+    if ((rc = chain_predict_passes(ctxs, E, W, cmpv))) return rc;
+    return launch_loglike_lowrank_sets(ctxs, E, W, rows_per_set, ll_dev, cmpv, inside_const);
+}
+
+int sets_check(gpb_ctx* const* ctxs, int E, int64_t nsets, const char* who) {
+    gpb_ctx* ctx = ctxs[0];
+    int rc = chain_check(ctxs, E, who);
+    if (rc) return rc;
+    if ((rc = lowrank_sets_check(ctxs, E, who))) return rc;
+    for (int e = 0; e < E; ++e)
+        if (ctxs[e]->lrs_K < 1 || ctxs[e]->lrs_K != ctx->lrs_K)
+            GPB_FAIL(GPB_E_STATE, std::string(who) + " before gpb_chain_like_sets (a new gpb_like_set drops its tables)");
+    if (nsets > ctx->lrs_K) GPB_FAIL(GPB_E_ARG, std::string(who) + ": more data sets than gpb_chain_like_sets installed");
     return 0;
 }
 

@@ -276,7 +276,8 @@ extern "C" int gpb_chain_like_set(gpb_ctx* const* ctxs, int E, const double* yex
         pca = pca && c->mode == GPB_MODE_PCA;
     }
     ctx->cpl.on = false;
-    if (!cov_exp_host) return 0;                       // the coupling is cleared, the blocks stay
+    for (int e = 0; e < E; ++e) ctxs[e]->lrs_K = 0;    // a new experiment: the per-data-set tables (gpb_chain_like_sets) go
+    if (!cov_exp_host) return 0;                      // the coupling is cleared, the blocks stay
     // every emulator's own diagonal block, as before: what reads yexp / Cexp per emulator keeps working
     std::vector<char> in_block((size_t)MT * (size_t)MT, 0);
     std::vector<double> blockv;

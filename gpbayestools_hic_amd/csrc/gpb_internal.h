@@ -10,6 +10,7 @@
 #include "../../include/gpbayes_debug.h"
 #include "dev_buf.h"
 #include "dispatch.h"
+#include "lowrank_setup.h"
 #include "ws_layout.h"
 
 namespace gpb {
@@ -195,6 +196,13 @@ struct gpb_ctx {
     int lowrank = 1;               // use it when it applies (tune key 23)
     int lr_split = 1;              // option key 49: a chain's block likelihoods as one workgroup per (walker tile, emulator) + an ordered sum
     gpb::DevBuf<double> lr_blocks;   // [E][Wcap] the emulators' blocks of a chain's batch (chain's first context)
+    // many data sets against the installed covariance (gpb_chain_like_sets): the factorisation of C0 kept on the host
+    // (lowrank_setup.h), and per data set k the row v0[k][16] (zero padded like lr_v0) and cperp[k].  lrs_K = 0: none.
+    gpb::LowrankFactor lr_fac;
+    gpb::DevBuf<double> lrs_v0;      // [lrs_K][16]
+    gpb::DevBuf<double> lrs_cperp;   // [lrs_K]
+    int64_t lrs_K = 0;
+    gpb::DevBuf<uint64_t> sets_seeds;  // gpb_chain_emcee_sets_run: the ensembles' generator keys [K]
     gpb::DevBuf<double> A;           // [P][M]
     gpb::DevBuf<double> mu;          // [M]
     gpb::DevBuf<double> scale;       // [M]
@@ -526,6 +534,14 @@ int launch_mvn(gpb_ctx* ctx, const double* dY_dev, const double* cov_dev, int64_
 int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double* ll_dev, const int* cmpv, double inside_const,
                                  bool* taken);
 int ensure_lr_blocks(gpb_ctx* ctx, int E);          // its per-emulator blocks [E][Wcap] in the chain's first context
+// ---- rows that belong to different data sets (gpb_chain_like_sets' tables; k_loglike_lowrank_sets) ---------------
+constexpr int64_t MAX_LIKE_SETS = 65536;
+// GPB_E_STATE (message on ctxs[0]) unless every emulator takes the low-rank kernel with the fused sums and the chain
+// holds no coupled likelihood: what gpb_chain_like_sets and the calls that read its tables ask
+int lowrank_sets_check(gpb_ctx* const* ctxs, int E, const char* who);
+// step (3) of chain_rows for such a batch: row w is judged against data set cmpv[4 + w] / rows_per_set (< K, the tables' K)
+int launch_loglike_lowrank_sets(gpb_ctx* const* ctxs, int E, int64_t W, int64_t rows_per_set, double* ll_dev, const int* cmpv,
+                                double inside_const);
 bool compaction_applies(const gpb_ctx* ctx);
 // ---- a chain of emulators (gpb_chain.hip) ----------------------------------------------------------------
 constexpr int MAX_CHAIN_CTX = 64;         // emulators of one chain: the context lists of the gpb_chain_* entry points
@@ -541,6 +557,14 @@ int chain_check(gpb_ctx* const* ctxs, int E, const char* who);
 // (1) and gathered the rows inside (2) into ctxs[0]->cmp_X, their count and indices at cmpv (gpb_chain_emcee_run)
 int chain_rows(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, double* ll_dev, const double* lo_dev,
                const double* hi_dev, double outside, double inside_const, int premarked = 0, const int* cmpv = nullptr);
+// chain_rows with the last stage replaced: row w belongs to data set w / rows_per_set of the tables of gpb_chain_like_sets
+// (checked by the caller: sets_check).  Same passes (1)-(2), then k_loglike_lowrank_sets.
+int chain_rows_sets(gpb_ctx* const* ctxs, int E, const double* X_dev, int64_t W, int64_t rows_per_set, double* ll_dev,
+                    const double* lo_dev, const double* hi_dev, double outside, double inside_const, int premarked = 0,
+                    const int* cmpv = nullptr);
+// what gpb_chain_logpost_sets and gpb_chain_emcee_sets_run ask before they launch: a chain (chain_check) whose every emulator
+// holds tables of the same K >= nsets (GPB_E_STATE without tables, GPB_E_ARG beyond them)
+int sets_check(gpb_ctx* const* ctxs, int E, int64_t nsets, const char* who);
 // The evaluation of the resident samplers and the gradient: lp of the rows X [W, ndim] of checked contexts on the selected
 // device, what Chain.log_prob_device writes: gpb_chain_logpost where gpb_chain_supported answers 1, else the per-emulator
 // sequence of gpb_param_map / gpb_loglike / gpb_box_finish / gpb_logpost

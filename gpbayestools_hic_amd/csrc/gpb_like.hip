@@ -547,7 +547,7 @@ static int launch_loglike_wg(gpb_ctx* ctx, int64_t W, double* ll_dev, bool accum
 }
 
 // ------------------------------------------------------------------ low-rank block log-likelihood, one lane per walker
-// C_w = C0 + A^T diag(var_w) A with the same C0 for every walker (gpb_api.hip: lowrank_setup has the algebra):
+// C_w = C0 + A^T diag(var_w) A with the same C0 for every walker (lowrank_setup.h has the algebra):
 //     loglike_w = -1/2 (c_perp + v^T S^-1 v) - 1/2 (log det C0 + log det S),   S = I + R diag(var_w) R^T,  v = R m_w + v0
 // a PP x PP Cholesky in one lane's registers instead of the M x M one (M = 64: 90 k flops and a 64-column
 // dependency chain per walker; here ~1 k flops).  R is upper triangular, so row i of R touches p >= i only.
@@ -853,6 +853,154 @@ int launch_loglike_lowrank_chain(gpb_ctx* const* ctxs, int E, int64_t W, double*
         hipLaunchKernelGGL(k_lowrank_sum, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, ctx->stream, blocks, E, ctx->Wld, W,
                            ll_dev, cmpv, inside_const);
     if (hipGetLastError() != hipSuccess) GPB_FAIL(GPB_E_HIP, "gpb: k_loglike_lowrank_multi launch failed");
+    return 0;
+}
+
+// ---- rows that belong to DIFFERENT data sets (a closure study: K ensembles, one per pseudo-experiment) ----------------------
+// The data enter the low-rank form through v0 and c_perp alone (lowrank_setup.h); R, log det C0 and the whole per-row S do
+// not depend on them.  k_loglike_lowrank_multi with a row's own v0[set][.] and cperp[set] from the tables of
+// gpb_chain_like_sets: set = (the row's ORIGINAL index, cmp[4 + w]) / rows_per_set.  The rows of a 64-row tile belong to
+// arbitrary sets (the gather order is arbitrary), so v0 is no per-workgroup vector: all waves stage the tile's 64 vectors in
+// LDS (sv0[i][lane], read back like smg: an LDS read where the twin has one, no table value is held in a register across
+// the algebra; all four forms build with zero scratch).  Given the same v0 every operation is the one the single-set kernels
+// do, in their order, so a row of set k gets the bits of gpb_chain_logpost with data set k installed; an emulator with fewer
+// than PP GPs runs with identity padding as in k_loglike_lowrank_multi (the tables are zero beyond P like lr_v0), which
+// also serves E = 1 (k_loglike_lowrank<P>: same products, sums and logarithms).
+struct LrSets {
+    const double* v0[MAX_LR_CTX];      // [K][16] per emulator
+    const double* cperp[MAX_LR_CTX];   // [K]
+    int rows_per_set, K;
+};
+
+template <int PP>
+__global__ __launch_bounds__(lr_threads<PP>()) void k_loglike_lowrank_sets(const LrTable tab, const LrSets sets, int64_t Wld,
+                                                             int64_t W, double* __restrict__ ll,
+                                                             const int* __restrict__ cmp, double inside_const,
+                                                             double* __restrict__ blocks) {
+    __shared__ double sR[PP][PP + 1];
+    __shared__ double sv0[PP][64];
+    __shared__ double smg[2][PP][64];
+    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const int64_t w = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = w < W && w < cmp[0];
+    // the set of this lane's row; a set index beyond the tables cannot happen (the host checks W / rows_per_set <= K): min
+    // keeps the read inside them whatever the index list holds
+    const int set = live ? max(min(cmp[4 + w] / sets.rows_per_set, sets.K - 1), 0) : 0;
+    double total = 0.0;
+    const int e_begin = blocks ? (int)blockIdx.y : 0, e_end = blocks ? (int)blockIdx.y + 1 : tab.E;
+    for (int e = e_begin; e < e_end; ++e) {
+        const LrCtx& c = tab.c[e];
+        const int P = c.P;
+        if (e > e_begin) __syncthreads();              // wave 0 is done with the previous emulator's tables
+        for (int i = threadIdx.x; i < PP * PP; i += lr_threads<PP>()) sR[i / PP][i % PP] = c.R[(i / PP) * 16 + (i % PP)];
+        if (live) {
+            const double* v0s = sets.v0[e] + (int64_t)set * 16;
+            for (int i = grp; i < PP; i += lr_threads<PP>() / 64) sv0[i][lane] = v0s[i];
+            partial_sums<PP>(smg, c.mpart, c.spart, c.amp, c.noise, P, c.nchunk, c.nI64, Wld, w, lane, grp);
+        }
+        __syncthreads();
+        if (grp != 0 || !live) continue;               // (uniform per wave; every wave still reaches the barriers above)
+        // From here to `bad` a copy of k_loglike_lowrank's algebra on purpose (see k_loglike_lowrank_multi)
+        double m[PP], g[PP];
+#pragma unroll
+        for (int p = 0; p < PP; ++p) {
+            m[p] = 0.0; g[p] = 0.0;
+            if (p < P) { m[p] = smg[0][p][lane]; g[p] = smg[1][p][lane]; }
+        }
+        double S[PP][PP], v[PP];
+#pragma unroll
+        for (int i = 0; i < PP; ++i) {
+            double vi = sv0[i][lane];
+#pragma unroll
+            for (int p = i; p < PP; ++p) vi = fma(sR[i][p], m[p], vi);
+            v[i] = vi;
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                double sij = (i == j) ? 1.0 : 0.0;
+#pragma unroll
+                for (int p = i; p < PP; ++p) sij = fma(sR[i][p] * g[p], sR[j][p], sij);
+                S[i][j] = sij;
+            }
+        }
+        double q = 0.0, prod = 1.0, logsum = 0.0;
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < PP; ++j) {
+            const double ajj = S[j][j];
+            bad = bad || !(ajj > 0.0);
+            const double rinv = rsqrt(ajj);
+            const double zj = v[j] * rinv;
+            q = fma(zj, zj, q);
+            prod *= ajj;
+            if ((j & 3) == 3 || j == PP - 1) { logsum += log(prod); prod = 1.0; }
+#pragma unroll
+            for (int i = j + 1; i < PP; ++i) {
+                const double lij = S[i][j] * rinv;
+                v[i] = fma(-lij, zj, v[i]);
+#pragma unroll
+                for (int k = j + 1; k <= i; ++k) S[i][k] = fma(-lij, S[k][j] * rinv, S[i][k]);
+            }
+        }
+        double r = -0.5 * (sets.cperp[e][set] + q) - 0.5 * (c.logdet0 + logsum);
+        bad = bad || !(logsum < INFINITY);
+        if (bad) {
+            r = nan("");
+            atomicAdd(c.notpd, 1);
+        }
+        if (blocks) { blocks[(int64_t)e * Wld + w] = r; return; }      // (grp 0, live: the ordered sum follows in k_lowrank_sum)
+        total = e ? (total + r) : r;                   // ll = r0; ll = ll + r1; ... as the separate launches accumulate
+    }
+    if (grp == 0 && live && !blocks) ll[cmp[4 + w]] = total + inside_const;
+}
+
+int lowrank_sets_check(gpb_ctx* const* ctxs, int E, const char* who) {
+    gpb_ctx* ctx = ctxs[0];
+    if (coupling_installed(ctx))
+        GPB_FAIL(GPB_E_STATE, std::string(who) + ": a coupled chain likelihood is installed (per-set tables are those of the "
+                                                 "emulators' own blocks)");
+    if (E > MAX_LR_CTX) GPB_FAIL(GPB_E_STATE, std::string(who) + ": more than 24 emulators");
+    for (int e = 0; e < E; ++e)
+        if (!lowrank_applies(ctxs[e]) || !ctxs[e]->fuse_finalize || !ctxs[e]->lr_fac.ok)
+            GPB_FAIL(GPB_E_STATE, std::string(who) + ": needs the low-rank likelihood kernel with its fused sums for every "
+                                                     "emulator (PCA mode, at most 16 GPs, C0 positive definite, option "
+                                                     "keys 11, 23 and 43 at their defaults)");
+    return 0;
+}
+
+int launch_loglike_lowrank_sets(gpb_ctx* const* ctxs, int E, int64_t W, int64_t rows_per_set, double* ll_dev, const int* cmpv,
+                                double inside_const) {
+    gpb_ctx* ctx = ctxs[0];
+    LrTable tab;
+    LrSets sets;
+    int64_t pmax = 0;
+    for (int e = 0; e < E; ++e) {
+        const gpb_ctx* c = ctxs[e];
+        if (c->Wld != ctx->Wld || c->lrs_K != ctx->lrs_K || c->lrs_K < 1)
+            GPB_FAIL(GPB_E_STATE, "gpb: internal: the emulators of a data-set batch disagree on its workspaces or tables");
+        pmax = c->P > pmax ? c->P : pmax;
+        tab.c[e] = LrCtx{c->mpart, c->spart, c->amp, c->noise, c->lr_R, c->lr_v0, c->notpd, c->lr_cperp, c->lr_logdet0,
+                         (int)c->P, (int)((c->Np + KX_CHUNK - 1) / KX_CHUNK), (int)(c->Np / 64)};
+        sets.v0[e] = c->lrs_v0;
+        sets.cperp[e] = c->lrs_cperp;
+    }
+    tab.E = E;
+    sets.rows_per_set = (int)rows_per_set;
+    sets.K = (int)ctx->lrs_K;
+    if (rows_per_set < 1 || rows_per_set >= (1ll << 31) || (W + rows_per_set - 1) / rows_per_set > ctx->lrs_K)
+        GPB_FAIL(GPB_E_STATE, "gpb: internal: a data-set batch beyond the tables");
+    double* blocks = (E > 1 && ctx->lr_split && ctx->lr_blocks.cap >= (int64_t)E * ctx->Wld) ? ctx->lr_blocks : nullptr;
+    const dim3 grid((unsigned)((W + 63) / 64), blocks ? (unsigned)E : 1u);
+    const int rc = with_int<4, 8, 12, 16>(round_up(pmax, 4), [&](auto N) {
+        constexpr int PP = decltype(N)::value;
+        hipLaunchKernelGGL(k_loglike_lowrank_sets<PP>, grid, dim3(lr_threads<PP>()), 0, ctx->stream, tab, sets, ctx->Wld, W, ll_dev,
+                           cmpv, inside_const, blocks);
+        return 0;
+    });
+    if (rc) return dispatched(ctx, rc, "k_loglike_lowrank_sets");
+    if (blocks)
+        hipLaunchKernelGGL(k_lowrank_sum, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, ctx->stream, blocks, E, ctx->Wld, W,
+                           ll_dev, cmpv, inside_const);
+    if (hipGetLastError() != hipSuccess) GPB_FAIL(GPB_E_HIP, "gpb: k_loglike_lowrank_sets launch failed");
     return 0;
 }
 

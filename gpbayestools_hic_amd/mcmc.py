@@ -957,6 +957,30 @@ class Chain:
             if failed:
                 raise RuntimeError("run_mcmc: rank 0 could not write %s (%s)" % (self.mcmc_path, failed))
 
+    def pseudo_data(self, truths, noise=False, seed=None):
+        """Closure-test data: the emulators' mean at truths [K, ndim] (_predict), [K, nobs] — the model's own output in the
+        experiment's place, examples/ClosureTest.ipynb.  noise=True adds one draw per set from expdata_cov
+        (np.random.default_rng(seed))."""
+        from .closure import pseudo_data
+        return pseudo_data(self, truths, noise=noise, seed=seed)
+
+    def run_closure(self, data, truths=None, nsteps=500, nburnsteps=None, nwalkers=None, nthin=10, seed=None):
+        """A closure study in one resident run: the chain calibrated against every row of data [K, nobs] (pseudo_data) with the
+        shared error model expdata_cov — K independent ensembles of `nwalkers` walkers whose proposals form one batch per
+        half-step (closure.ClosureSampler; gpb_chain_like_sets, gpb_chain_emcee_sets_run).  run_mcmc's recipe per set: half the
+        burn-in from random_pos, the walkers repositioned to the set's `nwalkers` most likely distinct points, the second half,
+        then `nsteps` of production thinned by `nthin`.  Set k's samples are, bit for bit, those of StretchSampler(seed =
+        result seeds[k]) on a chain whose experiment is data[k].  Returns a closure.ClosureResult — chain [K, nwalkers,
+        nsteps / nthin, ndim], lnprobability, acceptance, data and, with truths [K, ndim], the truth's rank in every posterior,
+        coverage(level), rank_histogram(bins), delta [K] and delta_per_parameter (closure_delta per set); save(path) and
+        write_chain(k, path) write pickles.  Nothing is written to mcmc_path, and the chain's own experiment stays installed.
+        NotImplementedError for foreign emulators, an emulator outside PCA mode or with more than 16 GPs, an expdata_cov that
+        couples emulators and a sharded chain; ValueError for a data width other than nobs, truths of another shape, odd
+        nwalkers, missing nburnsteps / nwalkers."""
+        from .closure import run_closure
+        return run_closure(self, data, truths=truths, nsteps=nsteps, nburnsteps=nburnsteps, nwalkers=nwalkers, nthin=nthin,
+                           seed=seed)
+
     def samplerPTLMC(self, logpostfunc, draw_func, theta0=None, numtemps=32, numchain=16, sampperchain=400, maxtemp=30,
                      nstartparameters=1000, seed=None):
         """Parallel-tempered Langevin Monte Carlo (surmise 0.2.1's PTLMC as the reference carries it, src/mcmc.py:431-676),

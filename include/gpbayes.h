@@ -750,6 +750,39 @@ GPB_API int gpb_chain_emcee_run(gpb_ctx* const* ctxs, int E, double* pos_dev, do
  *   contexts on different devices or streams.  Synchronises. */
 GPB_API int gpb_chain_like_set(gpb_ctx* const* ctxs, int E, const double* yexp_host /*[MT]*/,
                        const double* cov_exp_host /*[MT,MT], or NULL: clear the coupling*/, int* applies_host);
+/* Many data vectors against ONE experimental covariance in one resident run (Chain.run_closure: the closure study of
+ *   examples/ClosureTest.ipynb over a whole validation set).  The data enter the low-rank block likelihood only through a
+ *   P-vector v0 = Q^T L0^-1 (mu - yexp) and a scalar c_perp per emulator; the factorisation of C0 stays in the context.
+ * gpb_chain_like_sets: after gpb_chain_like_set, whose covariance all sets share: per emulator the device tables
+ *   v0[K][16] (zero padded beyond P) and cperp[K] of the rows of yexp_host [K][MT], MT = sum M_e in emuList order; O(M^2) host
+ *   work per set and emulator, no second Cholesky.  Row k of the tables is, bit for bit, what a single-set installation of
+ *   yexp_host[k] leaves.  K = 0 drops the tables, and so does any later gpb_like_set / gpb_chain_like_set /
+ *   gpb_emu_set_transform / gpb_gp_set of a member.  GPB_E_ARG: K < 0 or K > 65536, a null pointer or context.  GPB_E_STATE:
+ *   no likelihood installed, an emulator that does not take the low-rank likelihood kernel (PCA mode, at most 16 GPs, C0
+ *   positive definite, A of full rank, option keys 11 / 23 / 43 at their defaults), more than 24 emulators, or a coupled
+ *   chain likelihood installed.  A covariance PER set is not supported (a factorisation per set).  Synchronises.
+ * gpb_chain_logpost_sets: gpb_chain_logpost for rows that belong to different data sets: row w is judged against set
+ *   w / rows_per_set.  ll of a row of set k equals, bit for bit, gpb_chain_logpost of that row with data set k installed.
+ *   GPB_E_ARG: W no multiple of rows_per_set, W >= 2^31, or W / rows_per_set beyond the tables' K.  GPB_E_STATE: no tables
+ *   (or dropped), and what gpb_chain_logpost refuses.  Asynchronous, all pointers device memory.
+ * gpb_chain_emcee_sets_run: gpb_chain_emcee_run over K independent ensembles of nwalkers walkers each, ensemble s calibrated
+ *   against data set s: pos_dev [K][nwalkers][d], lp_dev [K][nwalkers] (the caller's initial values: gpb_chain_logpost_sets
+ *   with rows_per_set = nwalkers), naccept_dev [K][nwalkers], chain_dev [nsteps][K][nwalkers][d] and lpchain_dev
+ *   [nsteps][K][nwalkers] (either may be NULL).  The proposals of all ensembles form one batch of K nwalkers / 2 rows per
+ *   half-step.  Ensemble s takes exactly the draws of a stand-alone gpb_chain_emcee_run with seed = seeds_host[s], partners
+ *   from its own other half only: its walkers are that run's, bit for bit.  Unfused sequence (propose, evaluate, accept,
+ *   store), not sharded.  GPB_E_ARG: K outside 1 .. 65535, nwalkers odd or outside 2 .. 2^30, K nwalkers > 2^30, K beyond
+ *   the tables.  GPB_E_STATE: a communicator is installed, and what gpb_chain_logpost_sets refuses.  All checks and all
+ *   workspace growth precede the first launch.  NaN proposals are rejected and counted (gpb_stretch_nan_count).
+ *   Asynchronous. */
+GPB_API int gpb_chain_like_sets(gpb_ctx* const* ctxs, int E, int64_t K, const double* yexp_host /*[K,MT]*/);
+GPB_API int gpb_chain_logpost_sets(gpb_ctx* const* ctxs, int E, const double* Xs_dev /*[W,ndim]*/, int64_t W, int64_t rows_per_set,
+                           double* ll_dev /*[W]*/, const double* lo_dev, const double* hi_dev, double outside_value,
+                           double inside_const);
+GPB_API int gpb_chain_emcee_sets_run(gpb_ctx* const* ctxs, int E, double* pos_dev, double* lp_dev, int64_t K, int64_t nwalkers,
+                             int64_t nsteps, const uint64_t* seeds_host /*[K]*/, uint64_t step0, double a, int randomize_split,
+                             const double* lo_dev, const double* hi_dev, double outside_value, double inside_const,
+                             double* chain_dev, double* lpchain_dev, int64_t* naccept_dev);
 /* gpb_chain_logpost_grad <- Chain.log_posterior / log_likelihood together with the gradient in the chain's parameters,
  *   the (lp, grad) tuple the reference's PTLMC sampler takes from its logpostfunc (src/mcmc.py:446-453, 499-528, 545-569).
  *   ll_dev receives bit for bit what gpb_chain_logpost writes (or, for contexts it does not accept, what the per-emulator

@@ -40,6 +40,12 @@ GPB_API int gpb_test_ptlmc_draws(gpb_ctx* ctx, int64_t T, int64_t d, uint64_t se
 GPB_API int gpb_test_smc_draws(gpb_ctx* ctx, int64_t N, int64_t d, uint64_t seed, uint64_t stage, uint64_t step,
                        double* normals_dev /*[N,d]*/, double* logu_accept_dev /*[N]*/, double* u_resample_dev /*[1]*/);
 
+/* ---- likelihood tables (tests/test_gpu_closure.py) ---------------------------------- */
+/* test hook: the data terms of the low-rank likelihood as they lie on the device.  K = 0: the installed experiment's
+ * lr_v0 [16] and lr_cperp [1]; K >= 1: the tables of gpb_chain_like_sets, v0 [K][16] and cperp [K] (GPB_E_ARG unless K is the
+ * tables' K).  GPB_E_STATE when the context does not hold them.  Synchronises. */
+GPB_API int gpb_debug_like_tables(gpb_ctx* ctx, int64_t K, double* v0_host, double* cperp_host);
+
 /* ---- micro-benchmarks / self-tests (device) --------------------------------------- */
 /* C[M,N] = A*B through the f64 MFMA tile engine (K%16==0).  b_trans bits 0-1: 0 = A[M,K] B[K,N],
  * 1 = A[M,K] B[N,K]^T, 2 = A[K,M]^T B[K,N]; bit 2: 64x64 tiles instead of 128x128. */
