@@ -9,7 +9,8 @@ __version__ = "0.1.0"
 
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
            "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals", "PosteriorClusters",
-           "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof"]
+           "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof",
+           "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -38,6 +39,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("GoodnessOfFit", "posterior_gof"):
         from . import gof
         return getattr(gof, name)
+    if name in ("InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances"):
+        from . import divergence
+        return getattr(divergence, name)
     if name in ("Design", "generate_lhs", "MaxProDesign", "maxpro_design"):
         import importlib
         return getattr(importlib.import_module(".design", __name__), name)

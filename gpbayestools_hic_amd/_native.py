@@ -75,6 +75,8 @@ BOUNDARY = {
     "gpb_gof_influence": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, VP, c_i64, VP, VP]),
     "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "gpb_chain_knn": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int,
+                                C.c_int, VP, VP, VP, VP]),
     "gpb_maxpro_lhd": (C.c_int, [VP, c_i64, c_i64, C.c_int, C.c_int, VP, c_u64, c_i64, c_i64, C.c_int, C.c_double, C.c_double,
                                  VP, VP, VP, VP, VP, VP]),
     "gpb_maxpro_criterion": (C.c_int, [VP, VP, c_i64, c_i64, VP, VP]),

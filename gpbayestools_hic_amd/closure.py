@@ -266,6 +266,33 @@ class ClosureResult:
         """[K, ndim]"""
         return self._deltas()[1]
 
+    def _set_samples(self, k):
+        """set k's samples as [nwalkers, nstored, ndim]: a strided view of the resident chain, else the host array"""
+        return self._chain_dev[:, k].permute(1, 0, 2) if self._chain_dev is not None else self.chain[k]
+
+    def information_gain(self, k_set, discard=0, thin=1, **kw):
+        """InformationGain (divergence.py) of data set k_set's samples, without the first `discard` stored steps and thinned by
+        `thin`, against the uniform prior on prior_ranges; kw (k, bins, splits) as divergence.information_gain takes them"""
+        from .divergence import information_gain
+        if self.prior_ranges is None:
+            raise ValueError("information_gain needs prior_ranges [ndim, 2]")
+        kw.setdefault("names", self.names)
+        kw.setdefault("device", self.device or 0)
+        return information_gain(self._set_samples(int(k_set))[:, int(discard)::int(thin)], self.prior_ranges[:, 0],
+                                self.prior_ranges[:, 1], layout="walkers", **kw)
+
+    def divergence_between(self, k_a, k_b, discard=0, thin=1, **kw):
+        """PosteriorComparison (divergence.py) of data set k_a's samples against data set k_b's on prior_ranges: do the two
+        closure calibrations agree?"""
+        from .divergence import posterior_divergence
+        if self.prior_ranges is None:
+            raise ValueError("divergence_between needs prior_ranges [ndim, 2]")
+        kw.setdefault("names", self.names)
+        kw.setdefault("device", self.device or 0)
+        cut = (slice(None), slice(int(discard), None, int(thin)))
+        return posterior_divergence(self._set_samples(int(k_a))[cut], self._set_samples(int(k_b))[cut], self.prior_ranges[:, 0],
+                                    self.prior_ranges[:, 1], layout="walkers", layout_b="walkers", **kw)
+
     def _state(self):
         return dict(chain=self.chain, lnprobability=self.lnprobability, acceptance=self.acceptance, data=self.data,
                     truths=self.truths, prior_ranges=self.prior_ranges, names=self.names, rank=self.rank,

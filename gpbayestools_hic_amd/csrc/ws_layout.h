@@ -218,6 +218,29 @@ struct KmeansWs {
     }
 };
 
+// knn_ws (gpb_chain_knn), 8-byte units, the sizes from knn_plan.h: counters [2] | inv_scale [dp] | the scaled rows of B (of A
+// in self mode) [nZ][dp] | per slab of A: its scaled rows [slab][dp] (cross mode only) | the ranges' partial lists, r2 and idx
+// [splits][slab][kp] each and zeros [splits][slab] | with staged results (a caller that wants host memory) r2, idx [slab][kmax]
+// and zeros [slab]
+struct KnnWs {
+    int64_t* counters;
+    double *inv, *zb, *za, *pr2, *fr2;
+    int *pidx, *pzeros, *fidx, *fzeros;
+    void lay(Carver<int64_t>& c, int64_t nZ, int64_t slab, int64_t dp, int64_t kp, int64_t kmax, int64_t splits, int cross,
+             int staged) {
+        counters = c.take<int64_t>(2);
+        inv = c.take<double>(dp);
+        zb = c.take<double>(nZ * dp);
+        za = c.take<double>(cross ? slab * dp : 0);
+        pr2 = c.take<double>(splits * slab * kp);
+        pidx = c.take<int>(splits * slab * kp);
+        pzeros = c.take<int>(splits * slab);
+        fr2 = c.take<double>(staged ? slab * kmax : 0);
+        fidx = c.take<int>(staged ? slab * kmax : 0);
+        fzeros = c.take<int>(staged ? slab : 0);
+    }
+};
+
 // maxpro_ws (gpb_maxpro.hip), 8-byte units: the pair matrices T [R][n][n] | row sums [R][n] | per restart (sum, best sum, start
 // sum, sum of the best levels) [R][4] | (accepted, consumed) [R][2] | levels and best levels [R][d][n] each (int, a column
 // contiguous) | the trace [R][n_trace] (int; none without a trace) | for a real design (R == 1): x [d][n], the scores [n] and the

@@ -1029,7 +1029,56 @@ class GPEngine:
             out["labels"] = labels
         return out
 
-    MAXPRO_N, MAXPRO_D, MAXPRO_MAX_RESTARTS, MAXPRO_MAX_BLOCK = (4, 4096), (2, 64), 16, 64
+    KNN_MAX_K = 16
+
+    def chain_knn(self, a_dev, layout="steps", b_dev=None, layout_b=None, k=8, inv_scale=None, skip_zero=True, splits=0,
+                  on_device=False, return_index=True, return_zeros=True):
+        """For every row of a chain that lies on the device the k smallest squared distances to the rows of the chain itself
+        (b_dev None; the row itself excluded) or of another chain b_dev (gpb_chain_knn): a_dev, b_dev and their layouts as
+        chain_marginals takes them (a flat [S, ndim] set: x[:, None, :]; ndim <= 64), k <= 16.  Every coordinate is multiplied
+        by inv_scale [ndim] (default ones) first; the squared distance is acc = acc + t * t over the coordinates in order, no
+        fused multiply-add, which numpy reproduces bit for bit.  A row with a non-finite coordinate is skipped (r2 = inf, idx =
+        -1; never a candidate); a candidate at distance 0 is counted in "zeros" and, with skip_zero, not listed.  Returns a
+        dict: "r2" [nA, k] ascending, "idx" [nA, k] (int32 row numbers, outer axis of the memory layout first; equal distances
+        by ascending row number; -1 where fewer than k candidates exist), "zeros" [nA] (int32), "n_skipped" (skipped rows of A,
+        of B).  numpy out, or torch tensors with on_device.  splits (0: automatic) changes no output.  The engine lends its
+        device, stream and buffer cache only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        na, nwa, d, ssa, wsa = self._chain_view(a_dev, layout)
+        nA = na * nwa
+        if b_dev is not None:
+            nb, nwb, db, ssb, wsb = self._chain_view(b_dev, layout_b or layout)
+            if db != d:
+                raise ValueError("b_dev: %d parameters, a_dev has %d" % (db, d))
+        else:
+            nb = nwb = ssb = wsb = 0
+        inv = np.ones(d) if inv_scale is None else nat.f64(np.asarray(inv_scale, dtype=np.float64).reshape(-1))
+        if inv.shape[0] != d:
+            raise ValueError("inv_scale: expected [%d]" % d)
+        k = int(k)
+        kk = max(k, 0)
+        if on_device:
+            out = {"r2": torch.empty((nA, kk), dtype=torch.float64, device=dev)}
+            if return_index:
+                out["idx"] = torch.empty((nA, kk), dtype=torch.int32, device=dev)
+            if return_zeros:
+                out["zeros"] = torch.empty((nA,), dtype=torch.int32, device=dev)
+        else:
+            out = {"r2": np.empty((nA, kk))}
+            if return_index:
+                out["idx"] = np.empty((nA, kk), dtype=np.int32)
+            if return_zeros:
+                out["zeros"] = np.empty((nA,), dtype=np.int32)
+        nskip = np.zeros(2, dtype=np.int64)
+        self._ck(self.lib.gpb_chain_knn(self.h, nat.ptr(a_dev), na, nwa, ssa, wsa, nat.ptr(b_dev), nb, nwb, ssb, wsb, d, nat.ptr(inv), k,
+                                        1 if skip_zero else 0, int(splits), 1 if on_device else 0, nat.ptr(out["r2"]),
+                                        nat.ptr(out.get("idx")), nat.ptr(out.get("zeros")), nat.ptr(nskip)))
+        out["n_skipped"] = (int(nskip[0]), int(nskip[1]))
+        return out
+
+    MAXPRO_N, MAXPRO_D, MAXPRO_MAX_RESTARTS, MAXPRO_MAX_BLOCK =(4, 4096), (2, 64), 16, 64
 
     def _maxpro_shape(self, n, d):
         if not self.MAXPRO_N[0] <= n <= self.MAXPRO_N[1]:

@@ -14,6 +14,7 @@ variances (gpb_chain_like_set).  Foreign emulators (anything with the reference'
 """
 import logging
 import math
+import os
 import pickle
 from pathlib import Path
 
@@ -737,6 +738,63 @@ class Chain:
         import torch
         xd = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", kw["device"]))
         return posterior_clusters(xd[:, discard::thin], n_clusters, n_init, layout="walkers", **kw)
+
+    def _stored_for_knn(self, who, chain, discard, thin):
+        """the chain argument of information_gain / posterior_divergence — None (self.chain, read from mcmc_path when it is not
+        in memory), an array, a tensor or a chain pickle's path — as (samples, layout): a flat [S, ndim] set as it is, a stored
+        [nwalkers, nsteps, ndim] array as the device view without its first `discard` steps, thinned by `thin`"""
+        import torch
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        elif isinstance(chain, (str, os.PathLike)):
+            with open(chain, "rb") as f:
+                chain = pickle.load(f)["chain"]
+        x = chain if hasattr(chain, "data_ptr") else np.asarray(chain, dtype=np.float64)
+        if x.ndim == 2:
+            return x, "steps"
+        if x.ndim != 3:
+            raise ValueError("%s: chain must be [nwalkers, nsteps, ndim] or [S, ndim], got %s" % (who, tuple(x.shape)))
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+            raise ValueError("%s: discard >= 0, thin >= 1 and at least one step must remain" % who)
+        if not hasattr(x, "data_ptr"):
+            x = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
+        return x[:, discard::thin], "walkers"
+
+    def information_gain(self, chain=None, discard=0, thin=1, k=8, **kw):
+        """How much did the data teach us?  InformationGain (divergence.py) of a stored [nwalkers, nsteps, ndim] array —
+        self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first `discard`
+        steps and thinned by `thin`, or of a flat [S, ndim] set, against the uniform prior on the box self.min / self.max: the
+        Kullback-Leibler divergence from prior to posterior in the whole parameter space (nearest-neighbour entropy for every k
+        up to `k`, brute force on the device: gpb_chain_knn) and per parameter (histograms).  Thin by about the autocorrelation
+        time: repeated rows distort the estimate (duplicate_fraction).  kw (bins, weights, splits) as
+        divergence.information_gain takes them."""
+        from .divergence import information_gain
+        x, layout = self._stored_for_knn("information_gain", chain, discard, thin)
+        if len(self.min) != x.shape[-1]:
+            raise ValueError("information_gain: the chain has %d parameters, the prior box %d" % (x.shape[-1], len(self.min)))
+        kw.setdefault("names", list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[-1] else None)
+        kw.setdefault("device", self.device or 0)
+        return information_gain(x, self.min, self.max, k=k, layout=layout, **kw)
+
+    def posterior_divergence(self, other, chain=None, discard=0, thin=1, **kw):
+        """Do two calibrations agree?  PosteriorComparison (divergence.py) of this object's chain (`chain`, discard, thin as
+        information_gain takes them) against `other` — an array, a tensor or a chain pickle's path, [nwalkers, nsteps, ndim]
+        (cut by the same discard and thin) or flat [S, ndim] — on the prior box self.min / self.max: D(A || B) and D(B || A) in
+        the whole parameter space (gpb_chain_knn), per parameter and pair the Jensen-Shannon divergence of the histograms and the
+        shift of the medians.  kw (k, bins, pairs, splits) as divergence.posterior_divergence takes them."""
+        from .divergence import posterior_divergence
+        xa, la = self._stored_for_knn("posterior_divergence", chain, discard, thin)
+        xb, lb = self._stored_for_knn("posterior_divergence", other, discard, thin)
+        if len(self.min) != xa.shape[-1] or xb.shape[-1] != xa.shape[-1]:
+            raise ValueError("posterior_divergence: the chains have %d and %d parameters, the prior box %d"
+                             % (xa.shape[-1], xb.shape[-1], len(self.min)))
+        kw.setdefault("names", list(self.pardict) if len(getattr(self, "pardict", ())) == xa.shape[-1] else None)
+        kw.setdefault("device", self.device or 0)
+        return posterior_divergence(xa, xb, self.min, self.max, layout=la, layout_b=lb, **kw)
 
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of

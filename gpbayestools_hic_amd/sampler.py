@@ -338,6 +338,39 @@ class StretchSampler:
         kw.setdefault("names", list(names) if names else None)
         return trace_histogram(x, layout="steps", **kw)
 
+    def _prior_box(self):
+        lo, hi = getattr(self.chain_obj, "min", None), getattr(self.chain_obj, "max", None)
+        if lo is None or hi is None:
+            raise ValueError("the sampler's log-probability has no prior box: pass lo= and hi=")
+        return lo, hi
+
+    def information_gain(self, discard=0, thin=1, **kw):
+        """InformationGain of chain[discard::thin] (divergence.py) against the uniform prior on the chain object's box (or kw
+        lo=, hi=): the Kullback-Leibler divergence from prior to posterior in the whole parameter space, nearest neighbours
+        found on the stored chain where it lies on the device, through its strides (gpb_chain_knn), and per parameter.  Thin
+        by about the autocorrelation time.  kw (k, bins, splits) as divergence.information_gain takes them."""
+        from .divergence import information_gain
+        x, _ = self._stored_view(discard, thin)
+        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return information_gain(x, lo, hi, layout="steps", **kw)
+
+    def divergence_from(self, other, discard=0, thin=1, **kw):
+        """PosteriorComparison of chain[discard::thin] (A) against `other` (B: another sampler — its stored chain, cut the same
+        way —, a torch tensor or an array, [nsteps, nwalkers, ndim] with kw layout_b="steps", [nwalkers, nsteps, ndim] with
+        "walkers", or flat [S, ndim]) on the chain object's prior box (or kw lo=, hi=): D(A || B), D(B || A), Jensen-Shannon
+        divergences and median shifts (divergence.posterior_divergence; gpb_chain_knn)."""
+        from .divergence import posterior_divergence
+        x, _ = self._stored_view(discard, thin)
+        if hasattr(other, "_stored_view"):
+            other = other._stored_view(discard, thin)[0]
+            kw["layout_b"] = "steps"
+        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return posterior_divergence(x, other, lo, hi, layout="steps", **kw)
+
 
 class _HostLogProb:
     """minimal chain-like object around a host callable f(X[w, ndim]) -> lp[w]"""

@@ -144,6 +144,22 @@ class SMCSampler:
                 return np.array(betas), np.array(rates)
         raise RuntimeError("SMC: beta = %.6g after %d stages (max_stages)" % (betas[-1] if betas else 0.0, int(max_stages)))
 
+    def information_gain(self, **kw):
+        """InformationGain of the resident particles (divergence.py) against the uniform prior on the chain's box — after a
+        resampling the particles carry equal weights; kw (k, bins, splits) as divergence.information_gain takes them"""
+        from .divergence import information_gain
+        kw.setdefault("names", list(getattr(self.chain, "pardict", ())) or None)
+        return information_gain(self.x[:self.N], self.chain.min, self.chain.max, **kw)
+
+    def divergence_from(self, other, **kw):
+        """PosteriorComparison of the resident particles (A) against `other` (B: another SMCSampler's particles, a tensor or an
+        array as divergence.posterior_divergence takes xb) on the chain's prior box"""
+        from .divergence import posterior_divergence
+        if isinstance(other, SMCSampler):
+            other = other.x[:other.N]
+        kw.setdefault("names", list(getattr(self.chain, "pardict", ())) or None)
+        return posterior_divergence(self.x[:self.N], other, self.chain.min, self.chain.max, **kw)
+
 
 def run_smc(chain, n_particles=4096, ess_fraction=0.5, nmcmc=20, max_stages=200, seed=None):
     """Chain.run_SMC (see there)"""

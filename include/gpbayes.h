@@ -600,6 +600,43 @@ GPB_API int gpb_chain_kmeans(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, 
                      double* mean /*[d]*/, double* scale /*[d]*/, int64_t* seed_index /*[R,k]*/, int32_t* best,
                      int64_t* n_skipped, int32_t* labels_dev /*[S], device, or NULL*/);
 
+/* ---- nearest-neighbour distances of resident chains -------------------------------------------------------------------------- *
+ * gpb_chain_knn <- examples/PlotMCMC.ipynb overlays posterior and prior, and two or three posteriors (plot_corner_compare_datasets,
+ *                  plot_compare_posteriors_3datasets), and leaves the comparison to the eye.  The numbers for it — the
+ *                  Kozachenko-Leonenko entropy, the Wang-Kulkarni-Verdu divergence (gpbayestools_hic_amd/divergence.py) — need,
+ *                  for every row of a set A, the distances to its nearest rows in A itself or in another set B: nA nB d coordinate
+ *                  pairs of fp64 arithmetic, brute force, for chains that already lie in device memory.
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  a_dev and b_dev with their sizes
+ *   and strides exactly as gpb_chain_marginals and gpb_chain_kmeans read a chain (the same aliasing rule; a flat [S, d] set is
+ *   nsteps = S, nwalkers = 1); the rows are numbered outer axis first, as in gpb_chain_kmeans.  b_dev == NULL: SELF mode, the
+ *   neighbours of every row of A are sought in A, the row itself excluded by its number (the b_ sizes are ignored).  Otherwise
+ *   CROSS mode: the candidates of every row of A are all rows of B.
+ *   THE RULE, which a numpy model reproduces bit for bit (tests/knn_reference.py):
+ *     z = x * inv_scale[j]                                       every coordinate of A and of B, one rounding
+ *     acc = 0;  for j = 0 .. d - 1:  t = za_j - zb_j;  acc = acc + t * t        in that order, no fused multiply-add
+ *   A row with a scaled coordinate that is not finite is skipped: as a query it gets r2 = +inf, idx = -1, zeros = 0, and it is
+ *   never a candidate; n_skipped[0] counts such rows of A, n_skipped[1] those of B (0 in self mode).  A candidate at distance
+ *   exactly 0 — a repeated row, which every MCMC chain has after a rejected move — is counted in zeros[i]; with skip_zero = 1 it
+ *   is not listed, with skip_zero = 0 it is listed like any other.
+ *   r2[i] holds the kmax smallest squared distances in ascending order, idx[i] their row numbers; equal distances are ordered by
+ *   ascending row number; with fewer than kmax candidates the tail is +inf / -1.  The difference form is deliberate: the
+ *   neighbours are the pairs where |a|^2 + |b|^2 - 2 a.b cancels worst.
+ *   No output depends on splits (the number of ranges B is cut into so that a small A still fills the device; 0: chosen from the
+ *   sizes), on the memory layout, on on_device, on which optional outputs are requested or on the slabs A goes through: the lists
+ *   of the ranges are merged in (distance, row number) order.  Workspace, from the context's buffer cache: the scaled copy of B
+ *   (of A in self mode), written once per call, and per slab of A its scaled rows, the ranges' partial lists and the staged
+ *   results; the slabs keep what grows with them under GPB_KNN_WS_MB megabytes.
+ *   Outputs in host memory when on_device = 0 or device memory when 1; n_skipped always in host memory; the call synchronises.
+ *   Errors (GPB_E_ARG): sizes below 1; more than 2^31 - 1 rows; d outside 1 .. 64; kmax outside 1 .. 16; inv_scale_host not finite
+ *   and positive; strides that let two elements alias; splits < 0; skip_zero or on_device not 0 / 1; r2 or n_skipped NULL. */
+#define GPB_KNN_WS_MB 256
+GPB_API int gpb_chain_knn(gpb_ctx* ctx, const double* a_dev, int64_t a_nsteps, int64_t a_nwalkers, int64_t a_step_stride,
+                  int64_t a_walker_stride, const double* b_dev /*NULL: the neighbours are sought in A itself*/, int64_t b_nsteps,
+                  int64_t b_nwalkers, int64_t b_step_stride, int64_t b_walker_stride, int64_t d,
+                  const double* inv_scale_host /*[d]*/, int kmax, int skip_zero, int splits /*0: automatic*/, int on_device,
+                  double* r2 /*[nA,kmax]*/, int32_t* idx /*[nA,kmax] or NULL*/, int32_t* zeros /*[nA] or NULL*/,
+                  int64_t* n_skipped /*host, [2]*/);
+
 /* ---- maximum-projection Latin-hypercube designs -------------------------------------------------------------------------------- *
  * gpb_maxpro_lhd, gpb_maxpro_run_order <- src/design.py:64-74, R's `MaxProRunOrder(MaxProLHD(npoints, ndim)$Design)`;
  * gpb_maxpro_criterion: the criterion that generator minimises, for any design.
