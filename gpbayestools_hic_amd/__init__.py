@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "LoggingEnsembleSampler",
            "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals", "PosteriorClusters",
            "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof",
-           "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances"]
+           "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances",
+           "HMCSampler"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -29,6 +30,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("StretchSampler", "LoggingEnsembleSampler"):
         from . import sampler
         return getattr(sampler, name)
+    if name == "HMCSampler":
+        from .hmc import HMCSampler
+        return HMCSampler
     if name in ("PosteriorMarginals", "marginals"):       # (`marginals` is the submodule; the function is marginals.marginals)
         import importlib
         mod = importlib.import_module(".marginals", __name__)

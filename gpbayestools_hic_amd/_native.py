@@ -26,6 +26,12 @@ c_i64 = C.c_int64
 c_u64 = C.c_uint64
 VP = C.c_void_p
 
+
+class HMCDiag(C.Structure):
+    """gpb_hmc_diag of include/gpbayes.h: the device outputs of one step of gpb_chain_hmc_run (each may be NULL)"""
+    _fields_ = [(n, VP) for n in ("p0_dev", "logu_dev", "dh_dev", "a_dev", "traj_dev", "eps_dev")]
+
+
 # name -> (restype, argtypes); BOUNDARY mirrors include/gpbayes.h one to one (the drop-in C ABI), DEBUG mirrors
 # include/gpbayes_debug.h (test / tuning / measurement hooks)
 BOUNDARY = {
@@ -106,6 +112,8 @@ BOUNDARY = {
     "gpb_chain_logpost_grad": (C.c_int, [VP, C.c_int, VP, c_i64, VP, VP, VP, VP, C.c_double, C.c_double]),
     "gpb_chain_ptlmc_run": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_i64, c_u64, c_u64, c_i64, C.c_double, VP, VP, VP, VP,
                                       VP, VP, VP, VP, VP, VP, C.c_double, C.c_double, VP, c_i64, VP, VP]),
+    "gpb_chain_hmc_run": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_u64, c_u64, c_i64, C.c_double, C.c_int, C.c_double, VP, VP, VP,
+                                    VP, VP, VP, VP, VP, C.c_double, C.c_double, VP, VP, c_i64, c_u64, c_i64, VP, VP]),
     "gpb_chain_smc_reweight": (C.c_int, [VP, C.c_int, c_i64, c_u64, c_u64, C.c_double, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_smc_move": (C.c_int, [VP, C.c_int, c_i64, c_i64, c_u64, c_u64, c_u64, VP, VP, VP, VP, VP, VP, C.c_double,
                                      C.c_double]),

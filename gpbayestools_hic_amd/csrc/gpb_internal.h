@@ -215,6 +215,7 @@ struct gpb_ctx {
     gpb::DevBuf<long long> n_nan;    // device counter: NaN log-probabilities seen by the stretch move's accept step
     gpb::DevBuf<double> mc_ws;       // gpb_emcee_run: proposals q[nh][d], factor[nh], log-probabilities lpq[nh]
     gpb::DevBuf<double> ptl_ws;      // gpb_chain_ptlmc_run: draws, proposals, their lp / gradient, the other state buffers
+    gpb::DevBuf<double> hmc_ws;      // gpb_chain_hmc_run: the trajectory (momenta, positions, gradient, lp), H0, step size, escape flags
     gpb::DevBuf<double> smc_ws;      // gpb_chain_smc_*: weights, their scan, the gathered / proposed particles, moments
     int sim_ranks = 0;             // measurement hook: gpb_emcee_run evaluates 1/sim_ranks of every batch (one rank's share)
     int num_cu = 256;               // multiprocessor count of the device

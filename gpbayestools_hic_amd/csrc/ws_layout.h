@@ -58,6 +58,22 @@ struct PtlWs {
     }
 };
 
+// hmc_ws (gpb_chain_hmc_run): the trajectory's momenta, positions and gradient [C][nd] each; its lp and the start's energy H0
+// [C] each; the step size of the step (eps, eps / 2); the escape flags [C] (int)
+struct HmcWs {
+    double *p, *xt, *gt, *lpt, *h0, *eps;
+    int* esc;
+    void lay(Carver<double>& c, int64_t C, int64_t nd) {
+        p = c.take<double>(C * nd);
+        xt = c.take<double>(C * nd);
+        gt = c.take<double>(C * nd);
+        lpt = c.take<double>(C);
+        h0 = c.take<double>(C);
+        eps = c.take<double>(2);
+        esc = c.take<int>(C);
+    }
+};
+
 // smc_ws (gpb_chain_smc_*): weights, their scan, log-probabilities [N] each; one particle buffer [N][nd] (the gathered rows of
 // a reweighting — with their log-likelihoods in lp —, the proposals of a move step); cov [nd][nd]; mean [nd]
 struct SmcWs {

@@ -1053,6 +1053,26 @@ class Chain:
         return sampler_ptlmc(self, logpostfunc, draw_func, theta0=theta0, numtemps=numtemps, numchain=numchain,
                              sampperchain=sampperchain, maxtemp=maxtemp, nstartparameters=nstartparameters, seed=seed)
 
+    def run_HMC(self, nsteps=500, nwarmup=200, nchains=1024, nleapfrog=8, nthin=1, seed=None, *, reseed=True):
+        """Hamiltonian Monte Carlo over `nchains` independent chains, resident on the device (hmc.HMCSampler,
+        gpb_chain_hmc_run, `DESIGN.md` §30): a diagonal metric, `nleapfrog` leapfrog steps per trajectory, the prior box as
+        reflecting walls, one batched gradient of the log-posterior per leapfrog.  Resumes from the last column of an existing
+        `{'chain': ...}` pickle as run_mcmc does (with the step size and metric of this object's previous run_HMC where there
+        was one, after a warm-up from the resumed positions otherwise); else the chains start at random_pos (drawn from
+        np.random.default_rng when a seed is given) and `nwarmup` steps adapt the step size and the metric, with the chains
+        re-seeded at the most likely eighth of them half way (hmc.warm_start: independent chains do not pull each other out
+        of a local maximum, and run_mcmc re-seeds its walkers for the same reason).  That discards chains that sit in genuine
+        minor modes: `reseed=False` (keyword only) warms up without it, and a warm-up that would leave fewer than 10 steps
+        behind the re-seeding is not re-seeded (a warning says so).  `nsteps`
+        production steps thinned by `nthin` are appended to `{'chain': [nchains, nsteps / nthin, ndim]}`; sets self.chain,
+        self.acceptance_fraction and self.hmc_sampler (the sampler: step_size, inv_metric, n_divergent, n_escaped, diagnostics()
+        and the other shortcuts of the stretch-move sampler) and returns the sampler.  NotImplementedError for foreign emulators
+        and for a sharded chain; ValueError for nchains outside 1 .. 1048576, nleapfrog outside 1 .. 1024, more than 256
+        parameters, nsteps < 1, nwarmup < 0, nthin < 1 and a pickle whose chain has another shape."""
+        from .hmc import run_hmc
+        return run_hmc(self, nsteps=nsteps, nwarmup=nwarmup, nchains=nchains, nleapfrog=nleapfrog, nthin=nthin, seed=seed,
+                       reseed=reseed)
+
     def tempexchange(self, lpostf, temps, iters=1):
         """The temperature exchange of surmise's PTLMC (src/mcmc.py:679-692) on the host with numpy's global generator: iters
         sweeps of len(lpostf) random neighbour picks rt in [1, T), each swapping rungs rt - 1 and rt by the parallel-tempering

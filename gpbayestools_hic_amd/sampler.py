@@ -23,7 +23,158 @@ from . import _native as nat
 log = logging.getLogger(__name__)
 
 
-class StretchSampler:
+class StoredChainAccessors:
+    """The emcee-style accessors and the analysis shortcuts of a sampler that stores its chain on the device as
+    [nsteps, nwalkers, ndim]: StretchSampler and hmc.HMCSampler.  The class that mixes it in provides `_chain_dev` and `_lp_dev`
+    (torch tensors, None before the first stored run), `naccept` [nwalkers] (int64, device), `iterations`, `ndim` and
+    `chain_obj` (the mcmc.Chain, or any object with .min / .max / .pardict where a shortcut needs them)."""
+
+    # ------------------------------------------------------------------ emcee-style accessors
+    @property
+    def acceptance_fraction(self):
+        return self.naccept.cpu().numpy() / max(self.iterations, 1)
+
+    @property
+    def chain(self):
+        """[nwalkers, nsteps, ndim] like emcee's `sampler.chain`."""
+        return self._chain_dev.permute(1, 0, 2).contiguous().cpu().numpy()
+
+    @property
+    def lnprobability(self):
+        """[nwalkers, nsteps]."""
+        return self._lp_dev.permute(1, 0).contiguous().cpu().numpy()
+
+    @property
+    def flatchain(self):
+        return self._chain_dev.reshape(-1, self.ndim).cpu().numpy()
+
+    @property
+    def flatlnprobability(self):
+        return self._lp_dev.reshape(-1).cpu().numpy()
+
+    # ------------------------------------------------------------------ convergence
+    def _stored_view(self, discard, thin):
+        if self._chain_dev is None:
+            raise AttributeError("no stored chain: run the sampler (store=True) first")
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1:
+            raise ValueError("discard >= 0 and thin >= 1")
+        return self._chain_dev[discard::thin], thin
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """emcee's EnsembleSampler.get_autocorr_time: the integrated autocorrelation time [ndim] of chain[discard::thin],
+        multiplied by thin; kwargs (c, tol, quiet) as diagnostics.integrated_time takes them.  Computed on the stored chain
+        where it lies on the device, through its strides (gpb_mcmc_diag)."""
+        from .diagnostics import integrated_time
+        x, thin = self._stored_view(discard, thin)
+        return thin * integrated_time(x, **kwargs)
+
+    def diagnostics(self, discard=0, thin=1, c=5, tol=50):
+        """ChainDiagnostics of chain[discard::thin] (diagnostics.py): tau, window, effective sample size, split-R-hat, mean, std
+        and Monte-Carlo standard error per parameter; never raises for a short chain (converged=False instead)."""
+        from .diagnostics import diagnose
+        x, thin = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        return diagnose(x, c=c, tol=tol, thin=thin, names=list(names) if names else None)
+
+    def marginals(self, discard=0, thin=1, **kw):
+        """PosteriorMarginals of chain[discard::thin] (marginals.py): histograms of every parameter and pair, percentiles and
+        credible intervals, computed on the stored chain where it lies on the device, through its strides
+        (gpb_chain_marginals); kw (bins, range, pairs, quantiles) as marginals.marginals takes them."""
+        from .marginals import marginals
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return marginals(x, layout="steps", **kw)
+
+    def clusters(self, discard=0, thin=1, **kw):
+        """PosteriorClusters of chain[discard::thin] (clusters.py): k-means of the standardised samples, computed on the stored
+        chain where it lies on the device, through its strides (gpb_chain_kmeans); kw (n_clusters, n_init, init, seed,
+        max_iter, tol, standardize, return_labels) as clusters.posterior_clusters takes them."""
+        from .clusters import posterior_clusters
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return posterior_clusters(x, layout="steps", **kw)
+
+    def curves(self, discard=0, thin=1, **kw):
+        """PosteriorCurves of chain[discard::thin] (curves.py): median and credible bands of zeta/s (T), eta/s (mu_B) and
+        <y_loss> (y_init) over all stored samples, selected on the device without forming the per-sample curves
+        (gpb_chain_curves); kw (curves, columns, grid, levels, truth, return_values) as curves.posterior_curves takes them."""
+        from .curves import posterior_curves
+        x, _ = self._stored_view(discard, thin)
+        return posterior_curves(x, layout="steps", **kw)
+
+    def sensitivity(self, discard=0, thin=1):
+        """PosteriorSensitivity of chain[discard::thin] (sensitivity.py): the response matrix of SensitivityAnalysis.ipynb
+        averaged over all stored samples, and the Fisher information J^T C^-1 J per emulator (gpb_sens_accumulate)."""
+        from .sensitivity import posterior_sensitivity
+        x, _ = self._stored_view(discard, thin)
+        return posterior_sensitivity(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy())
+
+    def goodness_of_fit(self, discard=0, thin=1, **kw):
+        """GoodnessOfFit of chain[discard::thin] (gof.py): chi2 per data set and degree of freedom with the likelihood's
+        covariance over all stored samples, its predictive p-value, whitened residuals and the influence of each data set
+        (gpb_gof_accumulate, gpb_gof_influence).  kw as Chain.goodness_of_fit takes them."""
+        from .gof import posterior_gof
+        x, _ = self._stored_view(discard, thin)
+        return posterior_gof(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
+
+    def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
+        """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
+        chain object's prior box."""
+        from .curves import closure_delta
+        x, _ = self._stored_view(discard, thin)
+        if prior_ranges is None:
+            prior_ranges = np.stack([self.chain_obj.min, self.chain_obj.max], axis=1)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return closure_delta(x, truth, prior_ranges, layout="steps", **kw)
+
+    def trace_histogram(self, discard=0, thin=1, **kw):
+        """TraceHistogram of chain[discard::thin] (curves.py): the walkers' distribution step by step, counted on the device
+        (gpb_chain_trace_hist); kw (bins, range) as curves.trace_histogram takes them."""
+        from .curves import trace_histogram
+        x, _ = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return trace_histogram(x, layout="steps", **kw)
+
+    def _prior_box(self):
+        lo, hi = getattr(self.chain_obj, "min", None), getattr(self.chain_obj, "max", None)
+        if lo is None or hi is None:
+            raise ValueError("the sampler's log-probability has no prior box: pass lo= and hi=")
+        return lo, hi
+
+    def information_gain(self, discard=0, thin=1, **kw):
+        """InformationGain of chain[discard::thin] (divergence.py) against the uniform prior on the chain object's box (or kw
+        lo=, hi=): the Kullback-Leibler divergence from prior to posterior in the whole parameter space, nearest neighbours
+        found on the stored chain where it lies on the device, through its strides (gpb_chain_knn), and per parameter.  Thin
+        by about the autocorrelation time.  kw (k, bins, splits) as divergence.information_gain takes them."""
+        from .divergence import information_gain
+        x, _ = self._stored_view(discard, thin)
+        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return information_gain(x, lo, hi, layout="steps", **kw)
+
+    def divergence_from(self, other, discard=0, thin=1, **kw):
+        """PosteriorComparison of chain[discard::thin] (A) against `other` (B: another sampler — its stored chain, cut the same
+        way —, a torch tensor or an array, [nsteps, nwalkers, ndim] with kw layout_b="steps", [nwalkers, nsteps, ndim] with
+        "walkers", or flat [S, ndim]) on the chain object's prior box (or kw lo=, hi=): D(A || B), D(B || A), Jensen-Shannon
+        divergences and median shifts (divergence.posterior_divergence; gpb_chain_knn)."""
+        from .divergence import posterior_divergence
+        x, _ = self._stored_view(discard, thin)
+        if hasattr(other, "_stored_view"):
+            other = other._stored_view(discard, thin)[0]
+            kw["layout_b"] = "steps"
+        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return posterior_divergence(x, other, lo, hi, layout="steps", **kw)
+
+
+class StretchSampler(StoredChainAccessors):
     def __init__(self, chain, nwalkers, seed=None, a=2.0, logprob_device=None, sharding=None,
                  device=None, randomize_split=True):
         """chain: object with .min/.max/.ndim and log_prob_device(X_dev, out) (mcmc.Chain).
@@ -226,150 +377,6 @@ class StretchSampler:
             self._chain_dev = cd if self._chain_dev is None else torch.cat([self._chain_dev, cd], 0)
             self._lp_dev = ld if self._lp_dev is None else torch.cat([self._lp_dev, ld], 0)
         return self.pos.cpu().numpy()
-
-    # ------------------------------------------------------------------ emcee-style accessors
-    @property
-    def acceptance_fraction(self):
-        return self.naccept.cpu().numpy() / max(self.iterations, 1)
-
-    @property
-    def chain(self):
-        """[nwalkers, nsteps, ndim] like emcee's `sampler.chain`."""
-        return self._chain_dev.permute(1, 0, 2).contiguous().cpu().numpy()
-
-    @property
-    def lnprobability(self):
-        """[nwalkers, nsteps]."""
-        return self._lp_dev.permute(1, 0).contiguous().cpu().numpy()
-
-    @property
-    def flatchain(self):
-        return self._chain_dev.reshape(-1, self.ndim).cpu().numpy()
-
-    @property
-    def flatlnprobability(self):
-        return self._lp_dev.reshape(-1).cpu().numpy()
-
-    # ------------------------------------------------------------------ convergence
-    def _stored_view(self, discard, thin):
-        if self._chain_dev is None:
-            raise AttributeError("no stored chain: run the sampler (store=True) first")
-        discard, thin = int(discard), int(thin)
-        if discard < 0 or thin < 1:
-            raise ValueError("discard >= 0 and thin >= 1")
-        return self._chain_dev[discard::thin], thin
-
-    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
-        """emcee's EnsembleSampler.get_autocorr_time: the integrated autocorrelation time [ndim] of chain[discard::thin],
-        multiplied by thin; kwargs (c, tol, quiet) as diagnostics.integrated_time takes them.  Computed on the stored chain
-        where it lies on the device, through its strides (gpb_mcmc_diag)."""
-        from .diagnostics import integrated_time
-        x, thin = self._stored_view(discard, thin)
-        return thin * integrated_time(x, **kwargs)
-
-    def diagnostics(self, discard=0, thin=1, c=5, tol=50):
-        """ChainDiagnostics of chain[discard::thin] (diagnostics.py): tau, window, effective sample size, split-R-hat, mean, std
-        and Monte-Carlo standard error per parameter; never raises for a short chain (converged=False instead)."""
-        from .diagnostics import diagnose
-        x, thin = self._stored_view(discard, thin)
-        names = getattr(self.chain_obj, "pardict", None)
-        return diagnose(x, c=c, tol=tol, thin=thin, names=list(names) if names else None)
-
-    def marginals(self, discard=0, thin=1, **kw):
-        """PosteriorMarginals of chain[discard::thin] (marginals.py): histograms of every parameter and pair, percentiles and
-        credible intervals, computed on the stored chain where it lies on the device, through its strides
-        (gpb_chain_marginals); kw (bins, range, pairs, quantiles) as marginals.marginals takes them."""
-        from .marginals import marginals
-        x, _ = self._stored_view(discard, thin)
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return marginals(x, layout="steps", **kw)
-
-    def clusters(self, discard=0, thin=1, **kw):
-        """PosteriorClusters of chain[discard::thin] (clusters.py): k-means of the standardised samples, computed on the stored
-        chain where it lies on the device, through its strides (gpb_chain_kmeans); kw (n_clusters, n_init, init, seed,
-        max_iter, tol, standardize, return_labels) as clusters.posterior_clusters takes them."""
-        from .clusters import posterior_clusters
-        x, _ = self._stored_view(discard, thin)
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return posterior_clusters(x, layout="steps", **kw)
-
-    def curves(self, discard=0, thin=1, **kw):
-        """PosteriorCurves of chain[discard::thin] (curves.py): median and credible bands of zeta/s (T), eta/s (mu_B) and
-        <y_loss> (y_init) over all stored samples, selected on the device without forming the per-sample curves
-        (gpb_chain_curves); kw (curves, columns, grid, levels, truth, return_values) as curves.posterior_curves takes them."""
-        from .curves import posterior_curves
-        x, _ = self._stored_view(discard, thin)
-        return posterior_curves(x, layout="steps", **kw)
-
-    def sensitivity(self, discard=0, thin=1):
-        """PosteriorSensitivity of chain[discard::thin] (sensitivity.py): the response matrix of SensitivityAnalysis.ipynb
-        averaged over all stored samples, and the Fisher information J^T C^-1 J per emulator (gpb_sens_accumulate)."""
-        from .sensitivity import posterior_sensitivity
-        x, _ = self._stored_view(discard, thin)
-        return posterior_sensitivity(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy())
-
-    def goodness_of_fit(self, discard=0, thin=1, **kw):
-        """GoodnessOfFit of chain[discard::thin] (gof.py): chi2 per data set and degree of freedom with the likelihood's
-        covariance over all stored samples, its predictive p-value, whitened residuals and the influence of each data set
-        (gpb_gof_accumulate, gpb_gof_influence).  kw as Chain.goodness_of_fit takes them."""
-        from .gof import posterior_gof
-        x, _ = self._stored_view(discard, thin)
-        return posterior_gof(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
-
-    def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
-        """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
-        chain object's prior box."""
-        from .curves import closure_delta
-        x, _ = self._stored_view(discard, thin)
-        if prior_ranges is None:
-            prior_ranges = np.stack([self.chain_obj.min, self.chain_obj.max], axis=1)
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return closure_delta(x, truth, prior_ranges, layout="steps", **kw)
-
-    def trace_histogram(self, discard=0, thin=1, **kw):
-        """TraceHistogram of chain[discard::thin] (curves.py): the walkers' distribution step by step, counted on the device
-        (gpb_chain_trace_hist); kw (bins, range) as curves.trace_histogram takes them."""
-        from .curves import trace_histogram
-        x, _ = self._stored_view(discard, thin)
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return trace_histogram(x, layout="steps", **kw)
-
-    def _prior_box(self):
-        lo, hi = getattr(self.chain_obj, "min", None), getattr(self.chain_obj, "max", None)
-        if lo is None or hi is None:
-            raise ValueError("the sampler's log-probability has no prior box: pass lo= and hi=")
-        return lo, hi
-
-    def information_gain(self, discard=0, thin=1, **kw):
-        """InformationGain of chain[discard::thin] (divergence.py) against the uniform prior on the chain object's box (or kw
-        lo=, hi=): the Kullback-Leibler divergence from prior to posterior in the whole parameter space, nearest neighbours
-        found on the stored chain where it lies on the device, through its strides (gpb_chain_knn), and per parameter.  Thin
-        by about the autocorrelation time.  kw (k, bins, splits) as divergence.information_gain takes them."""
-        from .divergence import information_gain
-        x, _ = self._stored_view(discard, thin)
-        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return information_gain(x, lo, hi, layout="steps", **kw)
-
-    def divergence_from(self, other, discard=0, thin=1, **kw):
-        """PosteriorComparison of chain[discard::thin] (A) against `other` (B: another sampler — its stored chain, cut the same
-        way —, a torch tensor or an array, [nsteps, nwalkers, ndim] with kw layout_b="steps", [nwalkers, nsteps, ndim] with
-        "walkers", or flat [S, ndim]) on the chain object's prior box (or kw lo=, hi=): D(A || B), D(B || A), Jensen-Shannon
-        divergences and median shifts (divergence.posterior_divergence; gpb_chain_knn)."""
-        from .divergence import posterior_divergence
-        x, _ = self._stored_view(discard, thin)
-        if hasattr(other, "_stored_view"):
-            other = other._stored_view(discard, thin)[0]
-            kw["layout_b"] = "steps"
-        lo, hi = (kw.pop("lo"), kw.pop("hi")) if "lo" in kw and "hi" in kw else self._prior_box()
-        names = getattr(self.chain_obj, "pardict", None)
-        kw.setdefault("names", list(names) if names else None)
-        return posterior_divergence(x, other, lo, hi, layout="steps", **kw)
 
 
 class _HostLogProb:

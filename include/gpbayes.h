@@ -851,6 +851,43 @@ GPB_API int gpb_chain_ptlmc_run(gpb_ctx* const* ctxs, int E, int64_t numtemps, i
                         const double* hc_dev, const double* covmat0_dev, const double* lo_dev, const double* hi_dev,
                         double outside_value, double inside_const, double* save_dev, int64_t nsave, int64_t* naccept_dev,
                         int64_t* nswap_dev);
+/* gpb_chain_hmc_run <- Chain.run_HMC's step loop (hmc.HMCSampler): Hamiltonian Monte Carlo over C independent chains of the
+ *   chain of ctxs (the contexts gpb_chain_logpost_grad accepts), a diagonal metric, L leapfrog steps per trajectory, the prior
+ *   box as reflecting walls.  nsteps steps numbered step0, step0 + 1, ... (global step k, below 2^32), enqueued back to back on
+ *   the contexts' stream, no host synchronisation, no graph capture; one call of n steps gives the bits of n calls of one
+ *   step, and a chain's bits do not depend on C (with adapt = 0).  State, device memory in and out: x [C, d], lp [C] and grad
+ *   [C, d] (gpb_chain_logpost_grad at x), state [10] 8-byte slots: the doubles ln eps, ln eps-bar, H-bar, mu and the update
+ *   count of the dual averaging, then the 64-bit counts of accepted, divergent and escaped trajectories and of NaN rows, and
+ *   one slot the loop keeps for itself (zero between calls).  minv_dev [d] the inverse masses, msqrt_dev [d] = 1 / sqrt(minv).
+ *   One step of chain c: momenta p_j = z_j msqrt_j with z ~ N(0, 1) from Philox counters (c, k, pair, 12); H0 = -lp + K0,
+ *   K = 1/2 sum_j (p_j p_j) minv_j in index order; the step size eps_k = exp(state[0]) (1 + jitter (2 u - 1)), u from (0, k, 0,
+ *   13), the same for all chains; L times: p += (eps_k / 2) g, x_j += eps_k (minv_j p_j), then per coordinate at most 8
+ *   reflections (x_j < lo_j: x_j = lo_j + (lo_j - x_j), p_j = -p_j; x_j > hi_j: x_j = hi_j - (x_j - hi_j), p_j = -p_j; still
+ *   outside after that: the trajectory has escaped), one gpb_chain_logpost_grad at the C rows, p += (eps_k / 2) g'; the
+ *   proposal is taken where ln u < -(H1 - H0), u from (c, k, 0, 14), and the trajectory has not escaped (NaN rejects; a row
+ *   exactly on a wall evaluates to outside_value and rejects): x, lp and grad are replaced in place, lp bit for bit what
+ *   gpb_chain_logpost gives at that row.  A trajectory is divergent where H1 - H0 > 1000 or is NaN.  adapt != 0: after each step
+ *   one dual-averaging update (Hoffman & Gelman 2014, algorithm 5: gamma 0.05, t0 10, kappa 0.75) of the state towards
+ *   target_accept with the mean over the chains of a_c = min(1, exp(-(H1 - H0))) (0 for NaN or escaped), summed as integers of
+ *   2^-32: reproducible whatever the grid.  save_dev [nsave, C, d] and lpsave_dev [nsave, C] (either NULL) receive the state
+ *   after step save0 + i thin at slot i < nsave; naccept_dev [C] (may be NULL) is incremented.
+ *   diag (may be NULL; GPB_E_ARG unless nsteps == 1): device outputs of the step, each may be NULL.
+ *   Errors (GPB_E_ARG): C outside 1 .. 1048576, d outside 1 .. 256, L outside 1 .. 1024, jitter outside [0, 1), with adapt a
+ *   target_accept outside (0, 1), a step number of 2^32 or above, a null pointer, nsave or thin below 1 with save_dev; and what
+ *   gpb_chain_logpost_grad refuses, before anything is enqueued.  Asynchronous. */
+typedef struct gpb_hmc_diag {
+    double* p0_dev;     /* [C, d] the initial momenta */
+    double* logu_dev;   /* [C] ln u of the accept test */
+    double* dh_dev;     /* [C] H1 - H0 */
+    double* a_dev;      /* [C] the accept probabilities a_c */
+    double* traj_dev;   /* [L, C, d] the positions after each drift (walls applied) */
+    double* eps_dev;    /* [1] the step's step size eps_k */
+} gpb_hmc_diag;
+GPB_API int gpb_chain_hmc_run(gpb_ctx* const* ctxs, int E, int64_t C, int64_t nsteps, uint64_t step0, uint64_t seed, int64_t L,
+                      double jitter, int adapt, double target_accept, double* x_dev, double* lp_dev, double* grad_dev,
+                      double* state_dev, const double* minv_dev, const double* msqrt_dev, const double* lo_dev,
+                      const double* hi_dev, double outside_value, double inside_const, double* save_dev, double* lpsave_dev,
+                      int64_t nsave, uint64_t save0, int64_t thin, int64_t* naccept_dev, const gpb_hmc_diag* diag);
 /* gpb_chain_smc_reweight / gpb_chain_smc_move <- Chain.run_SMC (smc.SMCSampler): a tempered sequential Monte Carlo sampler
  *   over the chain of ctxs — pocoMC's outer algorithm (adaptive tempering from the prior box to the posterior, resampling,
  *   MCMC moves, a running evidence) with the particle covariance as the preconditioner; there is no normalizing flow.
