@@ -281,6 +281,14 @@ class ClosureResult:
         return information_gain(self._set_samples(int(k_set))[:, int(discard)::int(thin)], self.prior_ranges[:, 0],
                                 self.prior_ranges[:, 1], layout="walkers", **kw)
 
+    def expected_information_gain(self, chain, k_set, discard=0, thin=1, **kw):
+        """EIGResult (eig.py) over data set k_set's samples, without the first `discard` stored steps and thinned by `thin`: what a
+        planned measurement is expected to add to that set's posterior.  `chain`: the Chain the sets were calibrated with (a
+        result holds arrays only); kw (planned_error, groups, n_outer, seed) as Chain.expected_information_gain takes them"""
+        x = self._set_samples(int(k_set))[:, int(discard)::int(thin)]
+        x = x.cpu().numpy() if hasattr(x, "data_ptr") else np.asarray(x)
+        return chain.expected_information_gain(np.ascontiguousarray(x).reshape(-1, x.shape[-1]), **kw)
+
     def divergence_between(self, k_a, k_b, discard=0, thin=1, **kw):
         """PosteriorComparison (divergence.py) of data set k_a's samples against data set k_b's on prior_ranges: do the two
         closure calibrations agree?"""

@@ -2,7 +2,8 @@
 // Philox4x32-10 (Salmon et al., SC'11) keyed by a 64-bit seed; oracle/stretch_oracle.py restates it.  The fourth counter
 // word is a tag that keeps the draws of different purposes apart: 0, 1, 7 stretch move; 2, 3, 4 PTLMC; 8, 9, 10 SMC
 // (gpb_smc.hip); 11 the swap proposals of the MaxPro design generator (gpb_maxpro.hip, MP_TAG of maxpro_index.h); 12, 13, 14
-// HMC's momenta, step-size jitter and accept draws (gpb_hmc.hip).
+// HMC's momenta, step-size jitter and accept draws (gpb_hmc.hip); 15 the simulated measurements of the expected information gain
+// (gpb_eig.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -257,6 +257,27 @@ struct KnnWs {
     }
 };
 
+// eig_ws (gpb_eig_lse), doubles, every piece an even count (the panels are read two doubles at a time), the sizes from eig_plan.h:
+// the centres c [M] | the inner panel (t, u) [2M][sin_p] | the outer panel (q, l) [2M][sout_p] | the bias [G][sin_p] | the ranges'
+// partial maxima and sums [G][splits][sout_p] each | the groups' table [G][4] (int) | the count of bad outer indices (int) | with
+// staged results (a caller that wants host memory) lse_excl and self [G][S_out] each
+struct EigWs {
+    double *cen, *bop, *aop, *bias, *pm, *ps, *flse, *fself;
+    int *ranges, *bad;
+    void lay(Carver<double>& c, int64_t M, int64_t S_out, int64_t sin_p, int64_t sout_p, int64_t G, int64_t splits, int staged) {
+        cen = c.take<double>(M, 2);
+        bop = c.take<double>(2 * M * sin_p, 2);
+        aop = c.take<double>(2 * M * sout_p, 2);
+        bias = c.take<double>(G * sin_p, 2);
+        pm = c.take<double>(G * splits * sout_p, 2);
+        ps = c.take<double>(G * splits * sout_p, 2);
+        ranges = c.take<int>(4 * G, 2);
+        bad = c.take<int>(2, 2);
+        flse = c.take<double>(staged ? G * S_out : 0, 2);
+        fself = c.take<double>(staged ? G * S_out : 0, 2);
+    }
+};
+
 // maxpro_ws (gpb_maxpro.hip), 8-byte units: the pair matrices T [R][n][n] | row sums [R][n] | per restart (sum, best sum, start
 // sum, sum of the best levels) [R][4] | (accepted, consumed) [R][2] | levels and best levels [R][d][n] each (int, a column
 // contiguous) | the trace [R][n_trace] (int; none without a trace) | for a real design (R == 1): x [d][n], the scores [n] and the

@@ -1078,6 +1078,88 @@ class GPEngine:
         out["n_skipped"] = (int(nskip[0]), int(nskip[1]))
         return out
 
+    EIG_MAX_M, EIG_MAX_GROUPS, EIG_MAX_SPLITS = 4096, 64, 64
+
+    def _eig_inputs(self, mu_T, var_T, vadd, outer_idx):
+        """the shared arguments of eig_simulate / eig_lse: observable-major float64 cuda tensors [M, S_in] whose rows are
+        contiguous (a column slice of a wider array is fine: its stride is ld_in), vadd [M] and outer_idx [S_out] uploaded when
+        they come as numpy"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for name, a in (("mu_T", mu_T), ("var_T", var_T)):
+            if a is None and name == "var_T":
+                continue
+            if not (hasattr(a, "data_ptr") and a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.stride(1) == 1):
+                raise ValueError("%s: a float64 cuda tensor [M, S_in] with contiguous rows" % name)
+        M, S_in = int(mu_T.shape[0]), int(mu_T.shape[1])
+        ld_in = int(mu_T.stride(0)) if M > 1 else max(int(mu_T.stride(0)), S_in)
+        if var_T is not None and (tuple(var_T.shape) != (M, S_in) or (M > 1 and int(var_T.stride(0)) != ld_in)):
+            raise ValueError("var_T: the shape and row stride of mu_T")
+        if vadd is not None:
+            vadd = torch.as_tensor(np.ascontiguousarray(vadd, dtype=np.float64) if not hasattr(vadd, "data_ptr") else vadd,
+                                   device=dev).contiguous()
+            if tuple(vadd.shape) != (M,) or vadd.dtype != torch.float64:
+                raise ValueError("vadd: float64 [%d]" % M)
+        if not hasattr(outer_idx, "data_ptr"):
+            outer_idx = torch.as_tensor(np.ascontiguousarray(outer_idx, dtype=np.int32), device=dev)
+        outer_idx = outer_idx.contiguous()
+        if outer_idx.dtype != torch.int32 or outer_idx.dim() != 1 or not outer_idx.is_cuda:
+            raise ValueError("outer_idx: int32 [S_out]")
+        return dev, M, S_in, ld_in, vadd, outer_idx
+
+    def eig_simulate(self, mu_T, var_T, vadd, outer_idx, seed, out=None, return_z=False):
+        """Simulated measurements for the expected information gain (gpb_eig_simulate): y[m, i] = mu[m, o_i] + sqrt(var[m, o_i] +
+        vadd[m]) z[m, i] with o = outer_idx [S_out] (int32) and z ~ N(0, 1) from the Philox counter (i, m // 2, 0, tag 15) —
+        keyed by the position i, so repeated indices get different noise.  mu_T, var_T: observable-major float64 cuda tensors
+        [M, S_in] (var_T or vadd may be None: zeros).  Returns y_T [M, S_out] (cuda; `out`: a tensor whose first S_out columns are
+        written, the others left alone), with return_z also z_T."""
+        import torch
+        self._track_stream()
+        dev, M, S_in, ld_in, vadd, outer_idx = self._eig_inputs(mu_T, var_T, vadd, outer_idx)
+        S_out = int(outer_idx.shape[0])
+        y = torch.empty((M, S_out), dtype=torch.float64, device=dev) if out is None else out
+        if not (y.is_cuda and y.dtype == torch.float64 and y.dim() == 2 and y.shape[0] == M and y.stride(1) == 1):
+            raise ValueError("out: a float64 cuda tensor [M, >= S_out] with contiguous rows")
+        ld_out = int(y.stride(0)) if M > 1 else max(int(y.stride(0)), int(y.shape[1]))
+        z = torch.empty_strided(tuple(y.shape), tuple(y.stride()), dtype=torch.float64, device=dev) if return_z else None
+        if z is not None:
+            z.zero_()                                  # (the columns behind S_out are not written)
+        self._ck(self.lib.gpb_eig_simulate(self.h, nat.ptr(mu_T), nat.ptr(var_T), nat.ptr(vadd), M, S_in, ld_in, nat.ptr(outer_idx),
+                                           S_out, int(seed) & 0xFFFFFFFFFFFFFFFF, nat.ptr(y), nat.ptr(z), ld_out))
+        return (y, z) if return_z else y
+
+    def eig_lse(self, mu_T, var_T, vadd, logw, y_T, outer_idx, ranges, splits=0, on_device=False):
+        """For every simulated data vector y_i (column i of y_T [M, >= S_out]) and every group g of observables
+        [ranges[g, 0], ranges[g, 1]): lse_excl[g, i] = ln sum_{j != o_i} exp l_ij(g) over the inner samples and self[g, i] =
+        l_{i, o_i}(g), with l_ij(g) = logw_j - sum_{m in g} [(y_im - mu_jm)^2 / s_jm + ln s_jm] / 2 and s = var_T + vadd
+        (gpb_eig_lse: a matrix product on the fp64 matrix pipe with an online log-sum-exp; no S_out x S_in array exists).  mu_T,
+        var_T, y_T: observable-major float64 cuda tensors; var_T, vadd, logw may be None.  Inputs must be finite with s > 0: the
+        caller checks (eig.py does).  Returns (lse_excl, self), [G, S_out] each, numpy or, with on_device, torch.  splits (0:
+        automatic) changes the values only within the rounding of the sum."""
+        import torch
+        self._track_stream()
+        dev, M, S_in, ld_in, vadd, outer_idx = self._eig_inputs(mu_T, var_T, vadd, outer_idx)
+        S_out = int(outer_idx.shape[0])
+        if not (hasattr(y_T, "data_ptr") and y_T.is_cuda and y_T.dtype == torch.float64 and y_T.dim() == 2 and y_T.shape[0] == M
+                and y_T.stride(1) == 1):
+            raise ValueError("y_T: a float64 cuda tensor [M, >= S_out] with contiguous rows")
+        ld_out = int(y_T.stride(0)) if M > 1 else max(int(y_T.stride(0)), int(y_T.shape[1]))
+        if logw is not None:
+            logw = torch.as_tensor(np.ascontiguousarray(logw, dtype=np.float64) if not hasattr(logw, "data_ptr") else logw,
+                                   device=dev).contiguous()
+            if tuple(logw.shape) != (S_in,) or logw.dtype != torch.float64:
+                raise ValueError("logw: float64 [%d]" % S_in)
+        rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 2))
+        G = int(rg.shape[0])
+        if on_device:
+            lse, slf = (torch.empty((G, S_out), dtype=torch.float64, device=dev) for _ in range(2))
+        else:
+            lse, slf = np.empty((G, S_out)), np.empty((G, S_out))
+        self._ck(self.lib.gpb_eig_lse(self.h, nat.ptr(mu_T), nat.ptr(var_T), nat.ptr(vadd), nat.ptr(logw), M, S_in, ld_in, nat.ptr(y_T),
+                                      nat.ptr(outer_idx), S_out, ld_out, nat.ptr(rg), G, int(splits), 1 if on_device else 0,
+                                      nat.ptr(lse), nat.ptr(slf)))
+        return lse, slf
+
     MAXPRO_N, MAXPRO_D, MAXPRO_MAX_RESTARTS, MAXPRO_MAX_BLOCK =(4, 4096), (2, 64), 16, 64
 
     def _maxpro_shape(self, n, d):

@@ -796,6 +796,29 @@ class Chain:
         kw.setdefault("device", self.device or 0)
         return posterior_divergence(xa, xb, self.min, self.max, layout=la, layout_b=lb, **kw)
 
+    def expected_information_gain(self, samples=None, discard=0, thin=1, weights=None, planned_error=None, groups=None,
+                                  n_outer=8192, seed=None, **kw):
+        """Which data set, measured to which precision, is expected to constrain the parameters most?  EIGResult (eig.py): the
+        expected information gain — the mutual information between the parameters and a planned measurement, in nats — of
+        every emulator's observables alone and of all together, over `samples`: [S, ndim], or a stored [nwalkers, nsteps, ndim]
+        array without its first `discard` steps and thinned by `thin`; default self.chain, read from mcmc_path when it is not in
+        memory; `weights` [S] go with a flat set.  The stored chain gives the gain expected on top of the present posterior;
+        self.random_pos(n) gives the prior's, to set beside information_gain (what the data at hand realised).
+        Identical rows are collapsed into one sample with their summed weight first.  One predict pass writes means and
+        predictive variances observable-major (gpb_emu_predict_diag); n_outer measurements are simulated from samples drawn by
+        weight (np.random.default_rng(seed)) with the variance var + planned_error^2 (planned_error [nobs]: default
+        sqrt(diag(expdata_cov)), the errors of the data at hand), and the log-likelihood of every one under every sample goes
+        through the fp64 matrix pipe with an online log-sum-exp (gpb_eig_simulate, gpb_eig_lse).  groups: default the emulators
+        in emuList order ("emulator0", ...), then "all"; else a dict name -> (c0, c1) of contiguous observable ranges.
+        `lower` (prior-contrastive, biased low, saturates at ln S: a warning when within 1 nat) and `upper` (leave-one-out
+        nested Monte Carlo, biased high) bracket the value in expectation.  NOT solved here: the covariance is diagonal — the
+        PCA truncation term and an expdata_cov that couples observables are ignored —, and the number is the gain under the
+        emulator's own model of its error.
+        NotImplementedError for foreign emulators and a chain sharded over several ranks; ValueError for wrong shapes,
+        non-finite samples, bad weights and fewer than 2 distinct samples."""
+        from .eig import chain_expected_information_gain
+        return chain_expected_information_gain(self, samples, discard, thin, weights, planned_error, groups, n_outer, seed, **kw)
+
     def propose_design(self, n_new, candidates, reference=None, weights=None, return_scores=False, candidate_error=None):
         """Where should the next n_new model runs go, for this calibration?  Emulator.propose_design over all emulators of
         emuList at once (gpb_chain_design_run): one run yields every observable, so the pick is common — the score of a

@@ -158,6 +158,13 @@ class StoredChainAccessors:
         kw.setdefault("names", list(names) if names else None)
         return information_gain(x, lo, hi, layout="steps", **kw)
 
+    def expected_information_gain(self, discard=0, thin=1, **kw):
+        """EIGResult of chain[discard::thin] (eig.py): the information a planned measurement of every emulator's observables, and
+        of all together, is expected to add to this posterior (gpb_eig_simulate, gpb_eig_lse).  kw (planned_error, groups,
+        n_outer, seed) as Chain.expected_information_gain takes them."""
+        x, _ = self._stored_view(discard, thin)
+        return self.chain_obj.expected_information_gain(x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
+
     def divergence_from(self, other, discard=0, thin=1, **kw):
         """PosteriorComparison of chain[discard::thin] (A) against `other` (B: another sampler — its stored chain, cut the same
         way —, a torch tensor or an array, [nsteps, nwalkers, ndim] with kw layout_b="steps", [nwalkers, nsteps, ndim] with

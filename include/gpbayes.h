@@ -637,6 +637,45 @@ GPB_API int gpb_chain_knn(gpb_ctx* ctx, const double* a_dev, int64_t a_nsteps, i
                   double* r2 /*[nA,kmax]*/, int32_t* idx /*[nA,kmax] or NULL*/, int32_t* zeros /*[nA] or NULL*/,
                   int64_t* n_skipped /*host, [2]*/);
 
+/* ---- expected information gain of planned measurements ------------------------------------------------------------------------ *
+ * gpb_eig_simulate, gpb_eig_lse <- nothing in the reference project: it reports what the data taught (the posterior) and never asks
+ *                  what a planned measurement is expected to teach.  The nested Monte Carlo estimator of the mutual information
+ *                  between parameters and data (gpbayestools_hic_amd/eig.py) needs the diagonal Gaussian log-likelihood of every
+ *                  simulated data vector under every sample: S_out S_in M terms and a log-sum-exp per row and group of observables.
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  All arrays are OBSERVABLE-MAJOR,
+ *   as gpb_emu_predict_diag writes them: mu_T, var_T [M][ld_in] (sample j of observable m at [m ld_in + j]), y_T, z_T [M][ld_out].
+ *   INNER SET: samples j < S_in with means mu_jm, variances s_jm = var_jm + vadd_m (var_T == NULL: 0; vadd_dev == NULL: 0; every s
+ *   must be finite and > 0 and every input finite — the CALLER checks that, the library does not) and log-weights logw_j (NULL: 0).
+ *   OUTER SET: positions i < S_out, each with an index o_i = outer_idx_dev[i] (int32, device) into the inner set.  THE LIBRARY checks
+ *   the indices, on the device, before any kernel reads through one: an index outside [0, S_in) is GPB_E_ARG.
+ *   gpb_eig_simulate: y_im = mu_{o_i,m} + sqrt(s_{o_i,m}) z_im, no fused multiply-add, z from normal_pair (csrc/philox.h) of the
+ *   counter (i, p, 0, tag 15) for the observables 2p and 2p + 1: the key is the POSITION i, so repeated indices get different
+ *   noise.  z_T (optional) receives the draws.  Columns >= S_out of y_T and z_T are not touched.
+ *   gpb_eig_lse: for the groups g < G of observables [ranges_host[2g], ranges_host[2g + 1]) (host, int32) and
+ *     l_ij(g) = logw_j - sum_{m in g} [ (y_im - mu_jm)^2 / s_jm + ln s_jm ] / 2           (the (M_g / 2) ln 2 pi term is left out)
+ *     lse_excl[g, i] = ln sum_{j != o_i} exp l_ij(g)          (-inf when S_in == 1)
+ *     self[g, i]     = l_{i, o_i}(g), summed term by term in the order of m
+ *   lse_excl is evaluated as a matrix product on the fp64 matrix pipe: with c_m = mean_j mu_jm, t = 1 / s, u = (mu - c) t,
+ *   q = -(y - c)^2 / 2, l = y - c and b_gj = logw_j - sum_{m in g} [(mu_jm - c_m)^2 t_jm + ln s_jm] / 2,
+ *     l_ij(g) = sum_{m in g} (q_im t_jm + l_im u_jm) + b_gj,
+ *   followed by an online log-sum-exp (running maximum and sum of exponentials) over the inner samples; no S_out x S_in array exists.
+ *   Its error is that of a dot product of 2 M_g terms: |lse_excl - exact| <= (2 M_g + 64) 2^-52 (max_j (sum_k |a_ik b_jk| + |b_gj|)
+ *   + |lse_excl| + 1) (tests/test_gpu_eig.py).  The inner axis is cut into `splits` ranges (0: chosen from the sizes, 1 .. 64: at
+ *   most that many) so that few outer rows still fill the device; the ranges are merged in range order, no floating-point
+ *   atomics: the same call gives the same bits, another `splits` the same value within the rounding above.
+ *   Workspace, from the context's buffer cache: the two operand panels, 16 M (S_in + S_out) bytes rounded up to whole tiles.
+ *   Outputs lse_excl, self [G, S_out] in host memory when on_device = 0 or device memory when 1; both calls synchronise.
+ *   Errors (GPB_E_ARG): M outside 1 .. 4096; S_in or S_out below 1 or above 2^31 - 65; ld_in < S_in or ld_out < S_out; an outer index
+ *   outside [0, S_in); G outside 1 .. 64; a group that is empty or not inside [0, M); splits outside 0 .. 64; on_device not 0 / 1;
+ *   a NULL mu_T, outer_idx_dev, y_T, ranges_host, lse_excl or self. */
+GPB_API int gpb_eig_simulate(gpb_ctx* ctx, const double* mu_T, const double* var_T /*or NULL*/, const double* vadd_dev /*[M] or NULL*/,
+                     int64_t M, int64_t S_in, int64_t ld_in, const int32_t* outer_idx_dev /*[S_out]*/, int64_t S_out, uint64_t seed,
+                     double* y_T /*[M,ld_out]*/, double* z_T /*[M,ld_out] or NULL*/, int64_t ld_out);
+GPB_API int gpb_eig_lse(gpb_ctx* ctx, const double* mu_T, const double* var_T /*or NULL*/, const double* vadd_dev /*[M] or NULL*/,
+                const double* logw_dev /*[S_in] or NULL*/, int64_t M, int64_t S_in, int64_t ld_in, const double* y_T,
+                const int32_t* outer_idx_dev /*[S_out]*/, int64_t S_out, int64_t ld_out, const int32_t* ranges_host /*[G,2]*/, int G,
+                int splits /*0: automatic*/, int on_device, double* lse_excl /*[G,S_out]*/, double* self /*[G,S_out]*/);
+
 /* ---- maximum-projection Latin-hypercube designs -------------------------------------------------------------------------------- *
  * gpb_maxpro_lhd, gpb_maxpro_run_order <- src/design.py:64-74, R's `MaxProRunOrder(MaxProLHD(npoints, ndim)$Design)`;
  * gpb_maxpro_criterion: the criterion that generator minimises, for any design.
