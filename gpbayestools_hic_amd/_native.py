@@ -70,6 +70,7 @@ BOUNDARY = {
     "gpb_emu_predict_diag": (C.c_int, [VP, VP, c_i64, C.c_int, VP, VP, VP, c_i64]),
     "gpb_ppd_summary": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_i64, VP, C.c_int, VP, VP, C.c_int, VP, VP, VP, VP]),
     "gpb_mcmc_diag": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_double, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "gpb_chain_rank_diag": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, c_i64, C.c_int, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_marginals": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, VP, c_i64, VP, C.c_double, C.c_int,
                                       VP, VP, VP]),
     "gpb_chain_curves": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int, VP, VP,

@@ -1108,7 +1108,8 @@ extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
 #ifndef GPB_DEBUG_VARIANTS
     // the measurement hooks (26, 32: one rank's share of a sharded step on a single GPU) exist in the debug build
     // (libgpbayes_debug.so, -DGPB_DEBUG_VARIANTS) and are refused here
-    if ((key == 26 && value != 0) || (key == 32 && value != 0) || (key == 52 && value != 0))
+    if ((key == 26 && value != 0) || (key == 32 && value != 0) || (key == 52 && value != 0) ||
+        (key == 53 && value != 0))
         GPB_FAIL(GPB_E_ARG, "gpb_ctx_option: this value selects a hook of the debug build only");
 #endif
     switch (key) {
@@ -1164,6 +1165,10 @@ extern "C" int gpb_ctx_option(gpb_ctx* ctx, int key, int value) {
         case 52:        // gpb_chain_marginals: bytes of codes and integer weights per sample group (0: GPB_MARG_WS_MB megabytes); same counts
             if (value < 0) return GPB_E_ARG;
             ctx->marg_ws_bytes = value > 0 ? (int64_t)value : (int64_t)GPB_MARG_WS_MB << 20;
+            break;
+        case 53:        // gpb_chain_rank_diag: bytes of its workspace (0: GPB_RANK_WS_MB megabytes); the parameter groups change no bit
+            if (value < 0) return GPB_E_ARG;
+            ctx->rank_ws_bytes = value > 0 ? (int64_t)value : (int64_t)GPB_RANK_WS_MB << 20;
             break;
         default: return GPB_E_ARG;
     }

@@ -155,6 +155,10 @@ struct gpb_ctx {
     // chain marginals (gpb_marg.hip): edges | h1 | outside | h2 | pairs | integer weights | one code byte per (sample, parameter)
     // of a sample group; marg_ws_bytes caps the last two (option key 52 lowers it, in the debug build only: the grouping's test)
     gpb::DevBuf<int64_t> marg_ws;
+    // rank-normalised diagnostics (gpb_rank.hip): RankWs of ws_layout.h; rank_ws_bytes caps it (option key 53 lowers it, in the
+    // debug build only: the grouping's test)
+    gpb::DevBuf<int64_t> rank_ws;
+    int64_t rank_ws_bytes = (int64_t)GPB_RANK_WS_MB << 20;
     int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
     gpb::DevBuf<int64_t> curves_ws;  // posterior curves and trace histograms (gpb_curves.hip): CurvesWs of ws_layout.h
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h

@@ -153,6 +153,53 @@ struct DiagWs {
     }
 };
 
+// gpb_chain_rank_diag's results in out_stage, 8-byte units: median [d] | quant [d][nq] | rhat [d][2] | ess [d][K] | sd [d] | stop
+// [d][K] (int) | rank2 [d][n] (int64; n_rank2 = 0 unless asked for)
+struct RankStage {
+    double *median, *quant, *rhat, *ess, *sd;
+    int* stop;
+    int64_t* rank2;
+    void lay(Carver<double>& c, int64_t d, int64_t nq, int64_t n_rank2) {
+        const int64_t K = 2 + nq;
+        median = c.take<double>(d);
+        quant = c.take<double>(d * nq);
+        rhat = c.take<double>(2 * d);
+        ess = c.take<double>(d * K);
+        sd = c.take<double>(d);
+        stop = c.take<int>(d * K);
+        rank2 = c.take<int64_t>(n_rank2);
+    }
+};
+
+// rank_ws (launch_rank_diag), 8-byte units.  One parameter's sort: keys [2][n] (u64) and positions [2][n] (u32), ping and pong |
+// per sort block the digit counts, then offsets [nsb][256] (u32) | the digits' bases [256] (u32) | the plan of the eight passes
+// [32] (u32: the OR of key differences in [0..1], skipped [8 + p], source buffer [16 + p]) | 2 r of the values and of the folded
+// values in (step, walker) order [n] each (u32).  Then G parameters at a time: Y [G][K][hp][mp] | lag partials [G][K][nband][128]
+// | A(t) [G][K][L + 1] | the scan's R [G][K][L + 3] | per split chain (mean, variance) [G][K + 1][mp][2] | per series (W, variance
+// of the chain means) [G][K + 1][2]
+struct RankWs {
+    uint64_t* keys[2];
+    unsigned *pos[2], *counts, *base, *plan, *r2b, *r2f;
+    double *Y, *part, *acov, *R, *cstat, *mom;
+    int64_t n_sort;                 // units of the sort's pieces in front of Y
+    void lay(Carver<int64_t>& c, int64_t n, int64_t nsb, int64_t G, int64_t K, int64_t hp, int64_t mp, int64_t nband, int64_t L) {
+        for (int b = 0; b < 2; ++b) keys[b] = c.take<uint64_t>(n);
+        for (int b = 0; b < 2; ++b) pos[b] = c.take<unsigned>(n);
+        counts = c.take<unsigned>(nsb * 256);
+        base = c.take<unsigned>(256);
+        plan = c.take<unsigned>(32);
+        r2b = c.take<unsigned>(n);
+        r2f = c.take<unsigned>(n);
+        n_sort = c.total();
+        Y = c.take<double>(G * K * hp * mp);
+        part = c.take<double>(G * K * nband * 128);
+        acov = c.take<double>(G * K * (L + 1));
+        R = c.take<double>(G * K * (L + 3));
+        cstat = c.take<double>(G * (K + 1) * mp * 2);
+        mom = c.take<double>(G * (K + 1) * 2);
+    }
+};
+
 // marg_ws (launch_chain_marginals), 8-byte units: edges | h1 | outside [d] | h2 | pairs [n_pairs][2] (int) | integer weights |
 // one code byte per (sample, parameter) of a sample group.  h1 | outside | h2 are zeroed and copied out as one run of counts.
 struct MargWs {

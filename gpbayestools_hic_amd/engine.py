@@ -802,6 +802,41 @@ class GPEngine:
                                         nat.ptr(out.get("moments")), nat.ptr(out.get("rhat")), nat.ptr(out.get("nconst"))))
         return out
 
+    RANK_NO_BAND = 1 << 30                        # GPB_RANK_NO_BAND
+    RANK_MAX_Q = 8                                # GPB_RANK_MAX_Q
+
+    def rank_diag(self, x_dev, layout="steps", probs=(0.05, 0.95), max_lag=None, on_device=False, outputs=None):
+        """Rank-normalised diagnostics of a chain that lies on the device (gpb_chain_rank_diag; include/gpbayes.h has the
+        statistic): x_dev and layout as mcmc_diag takes them; probs: the levels of the quantile indicators (1 to 8, inside (0, 1));
+        max_lag: the largest lag formed (default nsteps // 2 - 1, all).  Returns a dict of numpy arrays (torch tensors,
+        asynchronously, with on_device), n = 2 (nsteps // 2) nwalkers, K = 2 + len(probs): "rank2" [ndim, n] int64 (twice the
+        average rank of the kept draws, in (step, walker) order), "median" [ndim], "quant" [ndim, nq], "rhat" [ndim, 2] (bulk,
+        folded), "ess" [ndim, K] (bulk, mean, the indicators), "stop" [ndim, K] int32 (bit 30, RANK_NO_BAND: the estimator needs
+        lags beyond max_lag and ess is NaN; -1: the series never varies), "sd" [ndim].  outputs: the names to compute (default
+        all but "rank2").  The engine lends its device, stream and buffer cache only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        n, nw, d, ss, ws = self._chain_view(x_dev, layout)
+        h = n // 2
+        probs = nat.f64(np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1))
+        nq = int(probs.shape[0])
+        max_lag = h - 1 if max_lag is None else int(max_lag)
+        names = ("rank2", "median", "quant", "rhat", "ess", "stop", "sd")
+        outputs = names[1:] if outputs is None else tuple(outputs)
+        if any(k not in names for k in outputs):
+            raise ValueError("outputs: names among %s" % (names,))
+        K = 2 + nq
+        shapes = {"rank2": (d, 2 * h * nw), "median": (d,), "quant": (d, nq), "rhat": (d, 2), "ess": (d, K), "stop": (d, K), "sd": (d,)}
+        types = {"rank2": "int64", "stop": "int32"}
+        if on_device:
+            out = {k: torch.empty(shapes[k], dtype=getattr(torch, types.get(k, "float64")), device=dev) for k in outputs}
+        else:
+            out = {k: np.empty(shapes[k], dtype=getattr(np, types.get(k, "float64"))) for k in outputs}
+        self._ck(self.lib.gpb_chain_rank_diag(self.h, nat.ptr(x_dev), n, nw, d, ss, ws, nat.ptr(probs), nq, max_lag,
+                                              1 if on_device else 0, *[nat.ptr(out.get(k)) for k in names]))
+        return out
+
     MARG_MAX_BINS = 64
 
     def chain_marginals(self, x_dev, layout="steps", edges=None, pairs=None, weights=None, on_device=False, outputs=None):
@@ -1451,7 +1486,8 @@ class GPEngine:
              "kcross_chunks": 19, "kcross_wpl": 20, "mid_switch": 22, "lowrank": 23, "chol_lookahead": 25, "sim_ranks": 26,
              "compact": 27, "tile_by_live": 28, "premark": 29, "fuse_accept_propose": 30, "sim_rank": 32, "tile_switch_c": 33,
              "mid_switch_c": 34, "narrow_switch_c": 35, "balance_shards": 36, "chain_batch": 40, "force_tile": 42, "generic_mvn": 43,
-             "tile_switch": 44, "chol_pair": 47, "lr_split": 49, "kinv_tile": 50, "predict_sliced": 51, "marg_ws_bytes": 52}[key]
+             "tile_switch": 44, "chol_pair": 47, "lr_split": 49, "kinv_tile": 50, "predict_sliced": 51, "marg_ws_bytes": 52,
+             "rank_ws_bytes": 53}[key]
         self._ck(self.lib.gpb_ctx_option(self.h, k, int(value)))
         if k == 51:
             self.predict_sliced = int(value)         # (what Emulator.state_digest folds in)

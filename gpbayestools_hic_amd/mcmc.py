@@ -545,6 +545,32 @@ class Chain:
         names = list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[2] else None
         return diagnose(x[:, discard:], c=c, tol=tol, layout="walkers", names=names, device=self.device or 0)
 
+    def rank_convergence(self, chain=None, discard=0, thin=1, **kw):
+        """Are the chains mixed, and are the bulk and the tails resolved?  RankDiagnostics (diagnostics.py) of a stored [nwalkers,
+        nsteps, ndim] array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's, run_HMC's or
+        run_MCMC_PTLMC's output — without its first `discard` steps and thinned by `thin`: rank-normalised split-R-hat (the larger
+        of bulk and folded) with bulk-, tail-, mean- and quantile-ESS per parameter (Vehtari et al. 2021), computed on the device
+        (gpb_chain_rank_diag; the array is uploaded in its own layout and read through its strides).  kw (probs, min_ess,
+        rhat_max) as diagnostics.rank_diagnose takes them.  A weighted particle set (run_SMC's, pocoMC's) is refused."""
+        from .diagnostics import rank_diagnose
+        if kw.get("weights") is not None:
+            raise ValueError("rank_convergence: ranks of weighted draws are out of scope; resample the particle set to equal weights")
+        if chain is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            chain = self.chain
+        x = np.asarray(chain, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError("rank_convergence: chain must be [nwalkers, nsteps, ndim], got %s (a flat particle set has no chains to "
+                             "compare)" % (np.shape(chain),))
+        discard, thin = int(discard), int(thin)
+        if discard < 0 or thin < 1 or (x.shape[1] - discard + thin - 1) // thin < 4:
+            raise ValueError("rank_convergence: at least 4 steps must remain after discard and thin")
+        names = list(self.pardict) if len(getattr(self, "pardict", ())) == x.shape[2] else None
+        kw.setdefault("names", names)
+        return rank_diagnose(x[:, discard::thin], thin=thin, layout="walkers", device=self.device or 0, **kw)
+
     def posterior_marginals(self, chain=None, discard=0, thin=1, bins=20, range=None, weights=None,
                             quantiles=(0.05, 0.16, 0.5, 0.84, 0.95), pairs=None):
         """The posterior in parameter space: PosteriorMarginals (marginals.py) of a stored [nwalkers, nsteps, ndim] array —

@@ -77,6 +77,16 @@ class StoredChainAccessors:
         names = getattr(self.chain_obj, "pardict", None)
         return diagnose(x, c=c, tol=tol, thin=thin, names=list(names) if names else None)
 
+    def rank_diagnostics(self, discard=0, thin=1, **kw):
+        """RankDiagnostics of chain[discard::thin] (diagnostics.py): rank-normalised split-R-hat (the larger of bulk and folded),
+        bulk, tail, mean and quantile effective sample sizes per parameter, computed on the stored chain where it lies on the
+        device, through its strides (gpb_chain_rank_diag); kw (probs, min_ess, rhat_max) as diagnostics.rank_diagnose takes them."""
+        from .diagnostics import rank_diagnose
+        x, thin = self._stored_view(discard, thin)
+        names = getattr(self.chain_obj, "pardict", None)
+        kw.setdefault("names", list(names) if names else None)
+        return rank_diagnose(x, thin=thin, layout="steps", **kw)
+
     def marginals(self, discard=0, thin=1, **kw):
         """PosteriorMarginals of chain[discard::thin] (marginals.py): histograms of every parameter and pair, percentiles and
         credible intervals, computed on the stored chain where it lies on the device, through its strides

@@ -366,6 +366,66 @@ GPB_API int gpb_mcmc_diag(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int
                   double* rho /*[d,max_lag+1] or NULL*/, double* tau /*[d] or NULL*/, int32_t* window /*[d] or NULL*/,
                   double* moments /*[d,3] or NULL*/, double* rhat /*[d] or NULL*/, int32_t* nconst /*[d] or NULL*/);
 
+/* ---- rank-normalised convergence diagnostics of a resident chain -------------------------------------------------------------- *
+ * gpb_chain_rank_diag <- Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021, Bayesian Analysis 16): rank-normalised split-R-hat
+ *                        (bulk and folded) and the effective sample sizes of the bulk, the mean and the quantile indicators, per
+ *                        parameter j < d, for a chain that already lies in device memory — what Stan, `posterior` and ArviZ report;
+ *                        the reference has no convergence check at all.  This comment is the specification (tests/rank_reference.py
+ *                        restates it in numpy / scipy); where it differs from ArviZ it says DEVIATION.
+ *   The context gives the device, the stream and the buffer cache only, as for gpb_mcmc_diag; x_dev, the strides and the two layouts
+ *   as gpb_mcmc_diag reads them.  Outputs (NULL: skipped, with the work only it needs) in host memory when on_device = 0 (the call
+ *   synchronises) or device memory (asynchronous).  Values must be finite (the caller checks).
+ *   Kept draws: h = nsteps / 2; split chain c = w holds steps t < h of walker w, c = nwalkers + w steps t >= nsteps - h.  The middle
+ *   step of an odd nsteps enters nothing below (DEVIATION: ArviZ takes its quantiles before the split).  m = 2 nwalkers split chains
+ *   of h draws, n = m h.  -0.0 counts as +0.0.
+ *   Ranks: r = the average rank (1-based; ties share the mean of their positions: scipy.stats.rankdata(method="average")) of a value
+ *   among all n kept values of its parameter; z = Phi^-1((r - 3/8) / (n + 1/4)) (csrc/ndtri.h: AS 241).
+ *   Series per parameter, K = 2 + nq: (a) z; (b) x; (c) per level p = probs[k] the 0 / 1 series I(x <= q_p), q_p = np.quantile(kept,
+ *   p) bit for bit (the order statistics at floor(p (n - 1)) and the next, numpy's interpolation).  For R-hat only: (d) z of the ranks
+ *   of |x - med|, med = np.median(kept) = the mean of the two middle order statistics.
+ *   R-hat of a series as [m, h]: W = the mean of the chains' sample variances (divisor h - 1), B = h times the sample variance
+ *   (divisor m - 1) of their means, sqrt(((h - 1) / h W + B / h) / W); NaN when the numerator is 0.
+ *   ESS of a series: acov_c(t) = (1 / h) sum_s y_c(s) y_c(s + t), y_c centred by the chain's own mean (biased, no wrap-around), A(t) =
+ *   its mean over the chains — the t-th diagonal sum of Y^T Y, Y[s, c] = y_c(s), over m h; mean_var = A(0) h / (h - 1); var_plus =
+ *   mean_var (h - 1) / h + the sample variance of the chain means; rho(t) = 1 - (mean_var - A(t)) / var_plus, rho(0) = 1.  Then Stan's
+ *   estimator (Geyer's initial positive sequence, then the initial monotone sequence), every sum sequential in t:
+ *       re = 1; ro = rho(1); R[0] = 1; R[1] = ro; t = 1
+ *       while t < h - 3 and re + ro > 0:  re = rho(t + 1); ro = rho(t + 2); if re + ro >= 0: R[t + 1] = re, R[t + 2] = ro;  t += 2
+ *       max_t = t - 2;  if re > 0: R[max_t + 1] = re
+ *       for t = 1, 3, ... <= max_t - 2:  if R[t + 1] + R[t + 2] > R[t - 1] + R[t]: R[t + 1] = R[t + 2] = (R[t - 1] + R[t]) / 2
+ *       tau = -1 + 2 sum(R[0 .. max_t]) + R[max_t + 1];  tau = max(tau, 1 / log10(n));  ess = n / tau
+ *   (entries of R never set are 0).  A chain all of whose values are equal has its value as its mean and variance 0, and chain means
+ *   that are all equal have variance 0, both exactly; a series with var_plus == 0 (a parameter that never varies, an indicator that
+ *   is all 0 or all 1) has ess = NaN and stop = -1 (DEVIATION: ArviZ returns n).  Only lags <= max_lag <= h - 1 are formed: when the
+ *   first loop needs rho beyond max_lag, stop = max_lag with bit 30 set (GPB_RANK_NO_BAND) and ess = NaN — the caller widens the
+ *   band.  rho(k) has the same bits for every band that holds k, so no result depends on where such a search started.
+ *     rank2 [d, n] (int64)  2 r of the kept draws in (step, walker) order: draw (kept step tk < 2 h, walker w) at tk nwalkers + w
+ *                           (written straight into device memory with on_device = 1; for host memory it is staged on the device
+ *                           first, 8 d n bytes that stay in the context's buffer cache: ask for it where it is wanted)
+ *     median [d]            med
+ *     quant [d, nq]         q_p
+ *     rhat [d, 2]           R-hat of (a) — bulk — and of (d) — folded
+ *     ess [d, K]            of (a), (b), (c) in the order of probs
+ *     stop [d, K] (int32)   max_t, or max_lag | GPB_RANK_NO_BAND, or -1
+ *     sd [d]                sqrt(var_plus) of (b)
+ *   The rank transform is a device radix sort (eight-bit digits, least significant first, every pass stable; a digit all keys share
+ *   is skipped) of the order-preserving keys of one parameter's kept draws, twice when rhat is asked for.  No floating-point
+ *   atomics; every sum runs in an order fixed by the padded shapes (h to 64, m to 16) alone.  A parameter's bits do not depend on d,
+ *   on the other parameters, on the layout, on on_device, on the levels other than its own, or on which outputs share the call.
+ *   Workspace: the sort's buffers of one parameter (24 n bytes and the ranks, 8 n), and Y with its lag partials for a group of
+ *   parameters, from the context's buffer cache; the groups keep it under GPB_RANK_WS_MB megabytes (one parameter at a time where a
+ *   single one needs more).  The grouping changes no bit.
+ *   Errors (GPB_E_ARG): nsteps < 4; nwalkers < 1 or d < 1; nsteps, nwalkers or d above 2^31 - 1; n above 2^31 - 1; nq outside 1 ... 8;
+ *   a level outside (0, 1); max_lag outside [0, h - 1]; strides that let two elements alias (gpb_mcmc_diag's rule). */
+#define GPB_RANK_NO_BAND (1 << 30)
+#define GPB_RANK_MAX_Q 8
+#define GPB_RANK_WS_MB 1024
+GPB_API int gpb_chain_rank_diag(gpb_ctx* ctx, const double* x_dev, int64_t nsteps, int64_t nwalkers, int64_t d,
+                  int64_t step_stride, int64_t walker_stride, const double* probs_host /*[nq]*/, int nq, int64_t max_lag,
+                  int on_device, int64_t* rank2 /*[d,n] or NULL*/, double* median /*[d] or NULL*/, double* quant /*[d,nq] or NULL*/,
+                  double* rhat /*[d,2] or NULL*/, double* ess /*[d,2+nq] or NULL*/, int32_t* stop /*[d,2+nq] or NULL*/,
+                  double* sd /*[d] or NULL*/);
+
 /* ---- corner-plot marginals of a resident chain ------------------------------------------------------------------------------ *
  * gpb_chain_marginals <- examples/PlotMCMC.ipynb (plot_corner_1dataset): `ax.hist(samples[:, i], bins=20)` per parameter and
  *                        `ax.hist2d(samples[:, j], samples[:, i], bins=20)` per pair — np.histogram and np.histogram2d of every column
@@ -1015,7 +1075,8 @@ GPB_API int gpb_dist_finalize(gpb_ctx* ctx);
  *   time, D = 6 in ~0.5.
  *   Keys 26 / 32 (one rank's share of a sharded step on a single GPU: a measurement hook) take non-zero values in the debug build
  *   only (libgpbayes_debug.so: include/gpbayes_debug.h) and return GPB_E_ARG here.  So does key 52, the bytes of gpb_chain_marginals'
- *   per-group workspace (0: GPB_MARG_WS_MB megabytes): a test hook for the sample groups, which change no count.
+ *   per-group workspace (0: GPB_MARG_WS_MB megabytes): a test hook for the sample groups, which change no count; and key 53, the
+ *   bytes of gpb_chain_rank_diag's workspace (0: GPB_RANK_WS_MB megabytes): a test hook for the parameter groups, which change no bit.
  * gpb_debug_has_variants: 1 when the loaded library is that debug build (-DGPB_DEBUG_VARIANTS), 0 for the product library.
  * gpb_profile_enable / _read: HIP-event timing of the dominant kernel (k_predict: V = L^-1 K*^T + sum of squares) on the
  *   context's stream — number of timed launches, their summed duration, the (GP, walker) pairs they processed; read resets.
