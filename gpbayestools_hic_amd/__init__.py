@@ -11,7 +11,7 @@ __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "Lo
            "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals", "PosteriorClusters",
            "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof",
            "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances",
-           "HMCSampler", "EIGResult", "expected_information_gain"]
+           "HMCSampler", "EIGResult", "expected_information_gain", "LooResult", "PsisResult", "posterior_loo", "psis"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -46,6 +46,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances"):
         from . import divergence
         return getattr(divergence, name)
+    if name in ("LooResult", "PsisResult", "posterior_loo", "psis"):
+        from . import loo
+        return getattr(loo, name)
     if name in ("EIGResult", "expected_information_gain"):
         from . import eig
         return getattr(eig, name)

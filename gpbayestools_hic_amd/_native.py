@@ -80,6 +80,9 @@ BOUNDARY = {
     "gpb_gof_accumulate": (C.c_int, [VP, c_i64, c_i64, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_chi2_sf": (C.c_int, [VP, VP, c_i64, C.c_double, VP]),
     "gpb_gof_influence": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, VP, c_i64, VP, VP]),
+    "gpb_loo_pointwise": (C.c_int, [VP, c_i64, c_i64, VP, VP, VP, VP, VP, VP, c_i64, VP]),
+    "gpb_psis": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, C.c_int, VP, VP, VP, VP]),
+    "gpb_psis_loo": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_i64, C.c_int, VP]),
     "gpb_chain_kmeans": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_knn": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int,

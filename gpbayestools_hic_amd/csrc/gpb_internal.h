@@ -168,6 +168,9 @@ struct gpb_ctx {
     gpb::DevBuf<double> sens_ws;     // gpb_sens_accumulate (gpb_sens.hip): per-row F | diag Cw | L^-1 J (large rows) | chunk sums | flags
     // goodness of fit (gpb_gof.hip): gpb_gof_accumulate's per-row z | pulls | p | chunk sums | flags, or gpb_gof_influence's minima | chunk sums
     gpb::DevBuf<double> gof_ws;
+    // leave-one-out (gpb_loo.hip, gpb_psis.hip): gpb_loo_pointwise's z | row copy of the rows worked in place, or gpb_psis's gathered
+    // tails x | sample index | index by rank | rank and, for host callers, the staged rows and results
+    gpb::DevBuf<double> loo_ws;
     // cross-validation (gpb_cv.hip): the folds of the planned call (idx [n] | fold_ptr [nf + 1], host copy h_cv), then the
     // leave-one-out path's sum-of-squares partials [P][Np/64][Np]
     gpb::DevBuf<int> cv_ws;

@@ -754,6 +754,121 @@ class GPEngine:
         self._ck(self.lib.gpb_gof_influence(self.h, nat.ptr(ll_T), E, S, ld, nat.ptr(x), d, nat.ptr(wt), nat.ptr(out)))
         return out
 
+    PSIS_MAX_S = 1 << 24                          # GPB_PSIS_MAX_S
+    LOO_COLUMNS = ("elpd_loo", "lppd", "p_waic", "khat", "ess", "n_tail", "loo_pit", "min_ll")     # GPB_LOO_*
+
+    def loo_pointwise(self, y, C, yexp, Cadd, ll_T, zc_T, flag):
+        """The leave-one-out conditionals of every observable of every row (gpb_loo_pointwise; include/gpbayes.h has the
+        formulas).  torch cuda tensors: y [W, M], C [W, M, M] (DESTROYED), yexp [M], Cadd [M, M] or None; ll_T and zc_T (or None)
+        views [M, W] with unit stride along the rows and one row stride (a slab of columns of an [nobs, S] array); flag [W] uint8,
+        1 where the row's covariance had a non-positive pivot (its column is NaN).  Asynchronous.  The engine lends its device
+        and stream only: M is the caller's."""
+        self._track_stream()
+        y = self._dev(y, (None, None), "y")
+        W, M = (int(v) for v in y.shape)
+        if M < 1 or M > self.GOF_MAX_M:
+            raise ValueError("loo_pointwise: need 1 <= M <= %d" % self.GOF_MAX_M)
+        self._dev(C, (W, M, M), "C")
+        self._dev(yexp, (M,), "yexp")
+        if Cadd is not None:
+            self._dev(Cadd, (M, M), "Cadd")
+        self._dev(flag, (W,), "flag", dtype="torch.uint8")
+        ld = None
+        for name, a in (("ll_T", ll_T), ("zc_T", zc_T)):
+            if a is None:
+                if name == "ll_T":
+                    raise ValueError("ll_T: expected a torch tensor")
+                continue
+            if not _is_torch(a) or not a.is_cuda or a.device.index != self.device or str(a.dtype) != "torch.float64":
+                raise ValueError("%s: expected a torch.float64 tensor on cuda:%d" % (name, self.device))
+            if a.dim() != 2 or tuple(a.shape) != (M, W) or (W > 1 and a.stride(1) != 1):
+                raise ValueError("%s: expected a [%d, %d] view with unit stride along the rows" % (name, M, W))
+            a_ld = int(a.stride(0)) if M > 1 else W
+            if a_ld < W or (ld is not None and a_ld != ld):
+                raise ValueError("ll_T and zc_T need the same row stride, at least W")
+            ld = a_ld
+        self._ck(self.lib.gpb_loo_pointwise(self.h, W, M, nat.ptr(y), nat.ptr(C), nat.ptr(yexp), nat.ptr(Cadd), nat.ptr(ll_T),
+                                            nat.ptr(zc_T), ld, nat.ptr(flag)))
+
+    def _rows_view(self, a, name, S=None):
+        """(R, S, ld) of a [R, >= S] float64 array of rows: a torch cuda view with unit stride along the samples, or a numpy array
+        (made C-contiguous by the caller)"""
+        if _is_torch(a):
+            if a.dim() != 2 or not a.is_cuda or a.device.index != self.device or str(a.dtype) != "torch.float64":
+                raise ValueError("%s: expected a two-dimensional torch.float64 tensor on cuda:%d" % (name, self.device))
+            R = int(a.shape[0])
+            S = int(a.shape[1]) if S is None else int(S)
+            if S < 1 or a.shape[1] < S or (a.shape[1] > 1 and a.stride(1) != 1):
+                raise ValueError("%s: expected a [%d, >= %d] view with unit stride along the samples, S >= 1" % (name, R, S))
+            ld = int(a.stride(0)) if R > 1 else max(int(a.shape[1]), S)
+            if ld < S:
+                raise ValueError("%s: the row stride must be at least S" % name)
+            return R, S, ld
+        if a.ndim != 2 or a.shape[1] < 1:
+            raise ValueError("%s: expected a [R, S] array, S >= 1" % name)
+        S = int(a.shape[1]) if S is None else int(S)
+        if S < 1 or S > a.shape[1]:
+            raise ValueError("%s: S outside 1 .. %d" % (name, a.shape[1]))
+        return int(a.shape[0]), S, int(a.shape[1])
+
+    def psis(self, lr_T, S=None, outputs=None):
+        """Pareto-smoothed importance sampling of every row of log ratios (gpb_psis; include/gpbayes.h has the procedure): lr_T
+        [R, >= S], finite (the caller checks), a torch cuda view with unit stride along the samples — the results are then device
+        tensors and the call is asynchronous — or a numpy array — numpy results.  Returns a dict: "khat" [R], "n_tail" [R] int64,
+        "ess" [R], "log_weights" [R, S] (normalised: logsumexp of a row is 0).  outputs: the names to compute (default all).
+        A row's bits depend on neither R, the row stride, the other rows nor the outputs asked for."""
+        import torch
+        names = ("khat", "n_tail", "ess", "log_weights")
+        outputs = names if outputs is None else tuple(outputs)
+        if any(k not in names for k in outputs):
+            raise ValueError("outputs: names among %s" % (names,))
+        on_device = _is_torch(lr_T)
+        if on_device:
+            self._track_stream()
+        else:
+            self._check_pid()
+            lr_T = nat.f64(lr_T)
+        R, S, ld = self._rows_view(lr_T, "lr_T", S)
+        if R < 1 or S > self.PSIS_MAX_S:
+            raise ValueError("psis: need R >= 1 and S <= 2^24")
+        shapes = {"khat": (R,), "n_tail": (R,), "ess": (R,), "log_weights": (R, ld)}
+        if on_device:
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.empty(shapes[k], dtype=torch.int64 if k == "n_tail" else torch.float64, device=dev) for k in outputs}
+        else:
+            out = {k: np.empty(shapes[k], dtype=np.int64 if k == "n_tail" else np.float64) for k in outputs}
+        self._ck(self.lib.gpb_psis(self.h, nat.ptr(lr_T), R, S, ld, 1 if on_device else 0, nat.ptr(out.get("khat")),
+                                   nat.ptr(out.get("n_tail")), nat.ptr(out.get("ess")), nat.ptr(out.get("log_weights"))))
+        if "log_weights" in out:
+            out["log_weights"] = out["log_weights"][:, :S]
+        return out
+
+    def psis_loo(self, ll_T, zc_T=None, S=None):
+        """PSIS-LOO and WAIC of R units from their pointwise log-likelihoods (gpb_psis_loo): ll_T [R, >= S] finite, zc_T the
+        standardised conditional residuals of the same shape and row stride or None; torch cuda views (device result,
+        asynchronous) or numpy arrays.  Returns [R, 8] in the order of LOO_COLUMNS."""
+        import torch
+        on_device = _is_torch(ll_T)
+        if zc_T is not None and _is_torch(zc_T) != on_device:
+            raise ValueError("ll_T and zc_T: both torch cuda tensors or both numpy arrays")
+        if on_device:
+            self._track_stream()
+        else:
+            self._check_pid()
+            ll_T = nat.f64(ll_T)
+            zc_T = None if zc_T is None else nat.f64(zc_T)
+        R, S, ld = self._rows_view(ll_T, "ll_T", S)
+        if zc_T is not None and self._rows_view(zc_T, "zc_T", S) != (R, S, ld):
+            raise ValueError("zc_T: expected the shape and the row stride of ll_T")
+        if R < 1 or S > self.PSIS_MAX_S:
+            raise ValueError("psis_loo: need R >= 1 and S <= 2^24")
+        if on_device:
+            out = torch.empty((R, len(self.LOO_COLUMNS)), dtype=torch.float64, device=torch.device("cuda", self.device))
+        else:
+            out = np.empty((R, len(self.LOO_COLUMNS)))
+        self._ck(self.lib.gpb_psis_loo(self.h, nat.ptr(ll_T), nat.ptr(zc_T), R, S, ld, 1 if on_device else 0, nat.ptr(out)))
+        return out
+
     DIAG_NO_WINDOW = 1 << 30                      # GPB_DIAG_NO_WINDOW
 
     def mcmc_diag(self, x_dev, layout="steps", max_lag=None, c=5.0, on_device=False, outputs=None):

@@ -737,6 +737,32 @@ class Chain:
                              % (self.ndim, self.ndim, np.shape(samples)))
         return posterior_gof(self, x, weights=weights, **kw)
 
+    def loo(self, samples=None, discard=0, thin=1, **kw):
+        """Leave-one-out predictive accuracy of the calibration: LooResult (loo.py) over ALL rows of `samples` — [S, ndim], or a
+        stored [nwalkers, nsteps, ndim] array without its first `discard` steps and thinned by `thin`; default self.chain, read
+        from mcmc_path when it is not in memory.  PSIS-LOO and WAIC per observable (its density given all other observables,
+        from the covariance the likelihood factorises) or per data set (kw unit="dataset"), the Pareto khat that says whether
+        each estimate can be trusted, the leave-one-out PIT; loo.compare(a, b) ranks two calibrations of the same data.  The
+        conditionals, the Pareto fit and the sums run on the device (gpb_loo_pointwise, gpb_psis_loo); equal inputs give equal
+        bits whatever the slab size (gof_slab_rows).  kw: unit, pit, return_pointwise, profile (loo.posterior_loo).  Unweighted
+        draws only: weights= raises ValueError (resample the particle set).  NotImplementedError for foreign emulators, a chain
+        sharded over several ranks, unit="dataset" with a coupled expdata_cov."""
+        from .loo import posterior_loo
+        if samples is None:
+            if self.chain is False:
+                with open(self.mcmc_path, "rb") as f:
+                    self.chain = pickle.load(f)["chain"]
+            samples = self.chain
+        x = np.asarray(samples, dtype=np.float64)
+        if x.ndim == 3:
+            discard, thin = int(discard), int(thin)
+            if discard < 0 or thin < 1 or x.shape[1] - discard < 1:
+                raise ValueError("loo: discard >= 0, thin >= 1 and at least one step must remain")
+            x = x[:, discard::thin].reshape(-1, x.shape[-1])
+        elif x.ndim != 2:
+            raise ValueError("loo: samples must be [S, %d] or [nwalkers, nsteps, %d], got %s" % (self.ndim, self.ndim, np.shape(samples)))
+        return posterior_loo(self, x, **kw)
+
     def posterior_clusters(self, chain=None, discard=0, thin=1, n_clusters=10, n_init=10, **kw):
         """Representative parameter sets of the posterior: PosteriorClusters (clusters.py) of a stored [nwalkers, nsteps, ndim]
         array — self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first

@@ -130,6 +130,14 @@ class StoredChainAccessors:
         x, _ = self._stored_view(discard, thin)
         return posterior_gof(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
 
+    def loo(self, discard=0, thin=1, **kw):
+        """LooResult of chain[discard::thin] (loo.py): PSIS-LOO and WAIC per observable or data set over all stored samples, with
+        the Pareto khat of every estimate and the leave-one-out PIT (gpb_loo_pointwise, gpb_psis_loo).  kw as Chain.loo takes
+        them."""
+        from .loo import posterior_loo
+        x, _ = self._stored_view(discard, thin)
+        return posterior_loo(self.chain_obj, x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
+
     def closure_delta(self, truth, prior_ranges=None, discard=0, thin=1, **kw):
         """ClosureDelta of chain[discard::thin] against the true parameters (curves.py); prior_ranges [ndim, 2]: default the
         chain object's prior box."""

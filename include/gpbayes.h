@@ -609,6 +609,60 @@ GPB_API int gpb_chi2_sf(gpb_ctx* ctx, const double* x_dev /*[n]*/, int64_t n, do
 GPB_API int gpb_gof_influence(gpb_ctx* ctx, const double* ll_T /*[E,ld]*/, int64_t E, int64_t S, int64_t ld, const double* x_dev /*[S,d]*/,
                       int64_t d, const double* wt_dev /*[S] or NULL*/, double* out_dev /*[E,2+2d]*/);
 
+/* ---- leave-one-out predictive accuracy: pointwise conditionals, Pareto-smoothed importance sampling, WAIC ------------------------- *
+ * The reference has no model comparison; the specification is this comment and the numpy model tests/psis_reference.py.
+ * gpb_loo_pointwise: per row w, with dY = y[w] - yexp, Cw = C[w] + Cadd = L L^T, P = Cw^-1 and g = P dY, for every observable m
+ *     ll_T[m, w] = -1/2 ln(2 pi / P_mm) - 1/2 g_m^2 / P_mm  =  ln p(y_m | y_-m, theta_w)     (with the 2 pi constant)
+ *     zc_T[m, w] = g_m / sqrt(P_mm)      the standardised conditional residual; zc_T may be NULL
+ *   the leave-one-out conditionals of a Gaussian that does not factorise (Buerkner, Gabry, Vehtari 2021).  Both outputs are
+ *   observable-major, element (m, w) at m * ld + w, as gpb_emu_predict_diag writes.  flag_dev [W] bytes: 1 for a row whose Cw has a
+ *   non-positive pivot (its column of both outputs is NaN), else 0.  C_dev IS DESTROYED (rows with M > 89 are worked in place).
+ *   One workgroup per row: gpb_gof_accumulate's left-looking Cholesky with z = L^-1 dY as row M of the factor, its dot products in
+ *   two doubles; then L is inverted in place row by row, and P_mm = sum_{k >= m} (L^-1)_km^2, g_m = sum_{k >= m} (L^-1)_km z_k in
+ *   ascending k.  In LDS while (M + 1) (M | 1) <= GPB_GOF_LDS_DOUBLES.  A row's bits depend on the row alone.
+ *   Errors (GPB_E_ARG): a null pointer (Cadd_dev and zc_T may be NULL), W < 0 or above 2^31 - 1, M < 1, M > 2048, ld < W.
+ * gpb_psis: Pareto-smoothed importance sampling (Vehtari, Simpson, Gelman, Yao, Gabry, JMLR 2024, as ArviZ's _psislw computes it)
+ *   of every row of lr_T [R, ld], S finite log ratios each (the caller checks):
+ *     1  x = lr - max(lr)
+ *     2  M = min(S // 5, ceil(3 sqrt(S))); cutoff = max((M + 1)-th largest x, ln DBL_MIN) by an exact radix select;
+ *        the tail is {x > cutoff}, n_tail its size
+ *     3  n_tail <= 4: khat = +inf, nothing is smoothed
+ *     4  the tail sorted ascending, ties by sample index; t_j = exp(x_j) - exp(cutoff); the Zhang-Stephens fit of csrc/psis_fit.h:
+ *        m_est = 30 + floor(sqrt(n_tail)) candidates b_i = (1 - sqrt(m_est / (i - 1/2))) / (3 t_[floor(n / 4 + 1/2)]) + 1 / t_[n],
+ *        k_i = mean log1p(-b_i t), profile weights from n (ln(-b_i / k_i) - k_i - 1), those below 10 eps dropped and the rest
+ *        renormalised, bhat = sum w_i b_i, k = mean log1p(-bhat t), sigma = -k / bhat, khat = (n k + 5) / (n + 10)
+ *     5  the j-th smallest tail value becomes ln(sigma expm1(-khat log1p(-p_j)) / khat + exp(cutoff)), p_j = (j - 1/2) / n
+ *        (-sigma log1p(-p_j) for the fraction at khat == 0); a khat that is not finite smooths nothing
+ *     6  values above 0 become 0; lw = x - logsumexp(x); ess = 1 / sum exp(2 lw)
+ *   khat [R], n_tail [R], ess [R], lw_T [R, ld]: each may be NULL.  on_device != 0: lr_T and the outputs are device memory and the
+ *   call is asynchronous; 0: host memory, staged.  Every sum runs in a tree fixed by S, n_tail and m_est alone, there is no
+ *   floating-point atomic, and a row's bits depend on neither R, ld, the other rows, on_device nor the outputs asked for.
+ *   Errors (GPB_E_ARG): a null lr_T, R < 1 or above 2^31 - 1, S < 1, ld < S, S > GPB_PSIS_MAX_S = 2^24 (the tail, at most 12288
+ *   values, is sorted in LDS).
+ * gpb_psis_loo: the same steps on lr = -ll_T [R, ld] (pointwise log-likelihoods of unit r for the S samples) and, in the same
+ *   passes, out [R, GPB_LOO_NOUT]:
+ *     [GPB_LOO_ELPD] logsumexp(lw + ll) | [GPB_LOO_LPPD] logsumexp(ll) - ln S | [GPB_LOO_PWAIC] the variance of ll, ddof 1, about
+ *     the mean of a first pass | [GPB_LOO_KHAT] | [GPB_LOO_ESS] | [GPB_LOO_NTAIL] | [GPB_LOO_PIT] sum exp(lw) Phi(zc_T), Phi from
+ *     erfc, NaN when zc_T is NULL | [GPB_LOO_MINLL] min ll.
+ *   Errors: those of gpb_psis, and a null out. */
+#define GPB_PSIS_MAX_S (1 << 24)
+#define GPB_LOO_ELPD 0
+#define GPB_LOO_LPPD 1
+#define GPB_LOO_PWAIC 2
+#define GPB_LOO_KHAT 3
+#define GPB_LOO_ESS 4
+#define GPB_LOO_NTAIL 5
+#define GPB_LOO_PIT 6
+#define GPB_LOO_MINLL 7
+#define GPB_LOO_NOUT 8
+GPB_API int gpb_loo_pointwise(gpb_ctx* ctx, int64_t W, int64_t M, const double* y_dev /*[W,M]*/, double* C_dev /*[W,M,M], destroyed*/,
+                      const double* yexp_dev /*[M]*/, const double* Cadd_dev /*[M,M] or NULL*/, double* ll_T /*[M,ld]*/,
+                      double* zc_T /*[M,ld] or NULL*/, int64_t ld, unsigned char* flag_dev /*[W]*/);
+GPB_API int gpb_psis(gpb_ctx* ctx, const double* lr_T /*[R,ld]*/, int64_t R, int64_t S, int64_t ld, int on_device, double* khat /*[R]*/,
+             int64_t* n_tail /*[R]*/, double* ess /*[R]*/, double* lw_T /*[R,ld] or NULL*/);
+GPB_API int gpb_psis_loo(gpb_ctx* ctx, const double* ll_T /*[R,ld]*/, const double* zc_T /*[R,ld] or NULL*/, int64_t R, int64_t S,
+                 int64_t ld, int on_device, double* out /*[R,GPB_LOO_NOUT]*/);
+
 /* ---- posterior clusters of a resident chain --------------------------------------------------------------------------------- *
  * gpb_chain_kmeans <- examples/generate_posterior_clusters.py: `StandardScaler().fit_transform(chain)`, `KMeans(n_clusters,
  *                     n_init=10).fit(...)`, `scaler.inverse_transform(kmeans.cluster_centers_)` — weighted k-means of the rows of a
