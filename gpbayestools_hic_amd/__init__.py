@@ -11,7 +11,8 @@ __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "Lo
            "WalkerSharding", "rms_relative_error", "honesty", "DesignProposal", "PosteriorMarginals", "PosteriorClusters",
            "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof",
            "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances",
-           "HMCSampler", "EIGResult", "expected_information_gain", "LooResult", "PsisResult", "posterior_loo", "psis"]
+           "HMCSampler", "EIGResult", "expected_information_gain", "LooResult", "PsisResult", "posterior_loo", "psis",
+           "HistoryMatch", "implausibility", "implausibility_maps"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -49,6 +50,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("LooResult", "PsisResult", "posterior_loo", "psis"):
         from . import loo
         return getattr(loo, name)
+    if name in ("HistoryMatch", "implausibility", "implausibility_maps"):
+        from . import history
+        return getattr(history, name)
     if name in ("EIGResult", "expected_information_gain"):
         from . import eig
         return getattr(eig, name)

@@ -89,6 +89,9 @@ BOUNDARY = {
                                 C.c_int, VP, VP, VP, VP]),
     "gpb_eig_simulate": (C.c_int, [VP, VP, VP, VP, c_i64, c_i64, c_i64, VP, c_i64, c_u64, VP, VP, c_i64]),
     "gpb_eig_lse": (C.c_int, [VP, VP, VP, VP, VP, c_i64, c_i64, c_i64, VP, VP, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, VP, VP]),
+    "gpb_hm_uniform": (C.c_int, [VP, VP, VP, c_i64, c_u64, c_i64, c_u64, VP, c_i64]),
+    "gpb_hm_implausibility": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_i64, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, c_i64, VP]),
+    "gpb_hm_maps": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, VP, C.c_double, VP, C.c_int, VP, c_i64, C.c_int, VP, VP, VP, VP, VP, VP]),
     "gpb_maxpro_lhd": (C.c_int, [VP, c_i64, c_i64, C.c_int, C.c_int, VP, c_u64, c_i64, c_i64, C.c_int, C.c_double, C.c_double,
                                  VP, VP, VP, VP, VP, VP]),
     "gpb_maxpro_criterion": (C.c_int, [VP, VP, c_i64, c_i64, VP, VP]),

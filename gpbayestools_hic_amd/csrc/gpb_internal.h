@@ -160,6 +160,7 @@ struct gpb_ctx {
     gpb::DevBuf<int64_t> rank_ws;
     int64_t rank_ws_bytes = (int64_t)GPB_RANK_WS_MB << 20;
     int64_t marg_ws_bytes = (int64_t)GPB_MARG_WS_MB << 20;
+    gpb::DevBuf<int64_t> hm_ws;      // history matching (gpb_hm.hip): HmWs of ws_layout.h; marg_ws_bytes caps the codes of a sample group
     gpb::DevBuf<int64_t> curves_ws;  // posterior curves and trace histograms (gpb_curves.hip): CurvesWs of ws_layout.h
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
     gpb::DevBuf<int64_t> knn_ws;     // nearest-neighbour distances (gpb_knn.hip): KnnWs of ws_layout.h
@@ -526,6 +527,13 @@ struct PpdLevels {
 };
 int launch_ppd(gpb_ctx* ctx, const double* mu_T, const double* var_T, int64_t M, int64_t S, int64_t ld, const PpdLevels& lv,
                const double* vadd, const double* yobs, double* moments, double* order, double* mixq, double* pit);
+// history matching (gpb_hm.hip), checked arguments, everything on the context's stream: candidate rows in a box; the maps of a
+// per-row score over the parameters, minima and counts taken onto the caller's device arrays
+int launch_hm_uniform(gpb_ctx* ctx, const double* lo_host, const double* hi_host, int d, uint64_t row0, int64_t S, uint64_t seed,
+                      double* X, int64_t ld);
+int launch_hm_maps(gpb_ctx* ctx, const double* x, int64_t S, int64_t d, int64_t row_stride, const double* score, double cutoff,
+                   const double* edges_host, int B, const int32_t* pairs_host, int64_t npairs, int init, double* min1, int64_t* cnt1,
+                   int64_t* nroy1, double* min2, int64_t* cnt2, int64_t* nroy2);
 // true when launch_loglike will take the block log-likelihood kernels that sum the partials themselves
 bool loglike_fuses_finalize(const gpb_ctx* ctx, int64_t W);
 // cmp_dev (optional): the batch was compacted by launch_compact: row w of the workspace is row cmp_dev[4 + w] of ll_dev

@@ -3,7 +3,7 @@
 // word is a tag that keeps the draws of different purposes apart: 0, 1, 7 stretch move; 2, 3, 4 PTLMC; 8, 9, 10 SMC
 // (gpb_smc.hip); 11 the swap proposals of the MaxPro design generator (gpb_maxpro.hip, MP_TAG of maxpro_index.h); 12, 13, 14
 // HMC's momenta, step-size jitter and accept draws (gpb_hmc.hip); 15 the simulated measurements of the expected information gain
-// (gpb_eig.hip).
+// (gpb_eig.hip); 16 the candidate rows of history matching (gpb_hm.hip, keyed by the absolute row).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

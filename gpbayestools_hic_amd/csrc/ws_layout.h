@@ -219,6 +219,20 @@ struct MargWs {
     }
 };
 
+// hm_ws (gpb_hm.hip), 8-byte units: the box lo [d] | hi [d] of gpb_hm_uniform, or gpb_hm_maps' edges [d][B + 1] | pairs
+// [npairs][2] (int) | one code byte per (sample, parameter) of a sample group
+struct HmWs {
+    double *box, *edges;
+    int* pairs;
+    unsigned char* codes;
+    void lay(Carver<int64_t>& c, int64_t n_box, int64_t n_edges, int64_t n_pairs, int64_t n_code_bytes) {
+        box = c.take<double>(n_box);
+        edges = c.take<double>(n_edges);
+        pairs = c.take<int>(2 * n_pairs);
+        codes = c.take<unsigned char>(n_code_bytes);
+    }
+};
+
 // curves_ws (gpb_chain_curves), 8-byte units, R = ncurves G rows and nr = 2 nq ranks per row: grid [R] | aux [2 d] | per
 // (row, rank) the digits found so far, the rank among the keys that share them and the distinct prefixes of the row's ranks
 // [R][nr] each | the digit histograms [R][nr][256] (u32) | curve descriptors [ncurves][5], every rank's group [R][nr] and the

@@ -1310,6 +1310,130 @@ class GPEngine:
                                       nat.ptr(lse), nat.ptr(slf)))
         return lse, slf
 
+    HM_MAX_D, HM_MAX_K, HM_MAX_GROUPS = 512, 4, 64
+
+    def _hm_rows(self, t, name, rows=None, dtype="torch.float64"):
+        """a cuda view [rows, >= 1] with unit stride along its columns, as the history-matching calls read and write them; returns
+        its leading dimension"""
+        if not _is_torch(t) or not t.is_cuda or t.device.index != self.device or str(t.dtype) != dtype:
+            raise ValueError("%s: expected a %s tensor on cuda:%d" % (name, dtype, self.device))
+        if t.dim() != 2 or (rows is not None and t.shape[0] != rows) or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1) \
+                or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError("%s: expected a [%s, n] view with unit stride along its columns" % (name, "rows" if rows is None else rows))
+        return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+    def hm_uniform(self, lo, hi, S, seed=0, row0=0, out=None):
+        """Candidate rows drawn uniformly in the box [lo, hi) on the device (gpb_hm_uniform): x[r, j] = lo_j + (hi_j - lo_j) u with u
+        the 53-bit uniform of the Philox counter (row0 + r, j, tag 16) — keyed by the ABSOLUTE row, so a row's bits do not depend
+        on how the rows are cut into calls.  Returns a cuda tensor [S, d] (`out`: a [S, >= d] view whose first d columns are
+        written)."""
+        import torch
+        self._track_stream()
+        lo, hi = nat.f64(lo).reshape(-1), nat.f64(hi).reshape(-1)
+        d, S = int(lo.shape[0]), int(S)
+        if hi.shape[0] != d:
+            raise ValueError("hm_uniform: lo and hi differ in length")
+        if out is None:
+            out = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
+        ld = self._hm_rows(out, "out", S)
+        if out.shape[1] < d:
+            raise ValueError("out: expected [%d, >= %d]" % (S, d))
+        self._ck(self.lib.gpb_hm_uniform(self.h, nat.ptr(lo), nat.ptr(hi), d, int(row0) & 0xFFFFFFFFFFFFFFFF, S,
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, nat.ptr(out), ld))
+        return out
+
+    def hm_implausibility(self, mu_T, var_T, yexp, vadd=None, ranges=None, K=1, S=None, want_arg=True, bad=None, on_device=False):
+        """The univariate implausibility of every sample under every observable (gpb_hm_implausibility): mu_T, var_T (None = 0)
+        observable-major cuda views [M, >= S] as emu_predict_diag writes them, yexp, vadd (None = 0; +inf masks an observable) [M],
+        numpy or torch cuda; I = |yexp - mu| / sqrt(var + vadd), 0 / +inf where the variance is not positive.  Returns a dict:
+        "top" [K, S] the K (<= 4) largest per sample, "arg" [S] (int32) the observable of the largest (lowest on ties; omitted
+        with want_arg=False), "gmax" [G, S] the largest over each range [m0, m1) of `ranges` (omitted without ranges), "bad" the
+        int64 device counter [1] the number of samples with an undefined implausibility was ADDED to (`bad`: an earlier call's, to
+        go on counting).  numpy arrays (and "bad" an int), or with on_device torch tensors without a synchronisation."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        ld = self._hm_rows(mu_T, "mu_T")
+        M = int(mu_T.shape[0])
+        S = int(mu_T.shape[1]) if S is None else int(S)
+        if S > mu_T.shape[1]:
+            raise ValueError("S: more samples than mu_T has columns")
+        if var_T is not None:
+            if self._hm_rows(var_T, "var_T", M) != ld or var_T.shape[1] < S:
+                raise ValueError("var_T: expected the shape and row stride of mu_T")
+
+        def vec(a, name):
+            if a is None:
+                return None
+            a = a if _is_torch(a) else torch.as_tensor(nat.f64(a).reshape(-1), device=dev)
+            return self._dev(a, (M,), name, contiguous=False)
+        yexp, vadd = vec(yexp, "yexp"), vec(vadd, "vadd")
+        if yexp is None:
+            raise ValueError("yexp: needed")
+        rg = None if ranges is None else np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 2))
+        G, K = (0 if rg is None else int(rg.shape[0])), int(K)
+        top = torch.empty((K, S), dtype=torch.float64, device=dev) if K > 0 else None
+        arg = torch.empty((S,), dtype=torch.int32, device=dev) if want_arg else None
+        gmax = torch.empty((G, S), dtype=torch.float64, device=dev) if G > 0 else None
+        if bad is None:
+            bad = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._dev(bad, (1,), "bad", dtype="torch.int64")
+        self._ck(self.lib.gpb_hm_implausibility(self.h, nat.ptr(mu_T), nat.ptr(var_T), M, S, ld, nat.ptr(yexp), nat.ptr(vadd), nat.ptr(rg),
+                                                G, K, nat.ptr(top), nat.ptr(arg), nat.ptr(gmax), S, nat.ptr(bad)))
+        out = {"top": top, "bad": bad}
+        if want_arg:
+            out["arg"] = arg
+        if G > 0:
+            out["gmax"] = gmax
+        if on_device:
+            return out
+        return {k: (int(v.item()) if k == "bad" else v.cpu().numpy()) for k, v in out.items()}
+
+    def hm_maps(self, X, score, cutoff, edges, pairs=None, into=None, outputs=("1d", "2d"), on_device=False):
+        """Minimum-score and count maps of rows over the bins of every parameter and parameter pair (gpb_hm_maps): X a cuda view
+        [S, >= d] with unit stride along the parameters, score [S] cuda (no NaN), edges [d, B + 1] (B <= 64; chain_marginals' bin
+        rule), pairs [npairs, 2] (default all i < j).  Returns a dict with, for "1d" in outputs, "min1" (float64), "cnt1", "nroy1"
+        (int64) [d, B] and, for "2d", "min2", "cnt2", "nroy2" [npairs, B, B]: per bin the smallest score, the number of rows and the
+        number of rows with score < cutoff (strict); an empty bin reads +inf, 0, 0.  into: the device dict of an earlier call, to
+        accumulate onto (slabs add up; integer minima and adds only, so the result does not depend on the slabs).  numpy arrays, or
+        with on_device (and always with `into`) the device tensors, without a synchronisation."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        edges = nat.f64(edges)
+        if edges.ndim != 2 or edges.shape[1] < 2:
+            raise ValueError("edges: expected [d, B + 1]")
+        d, B = int(edges.shape[0]), int(edges.shape[1]) - 1
+        row_stride = self._hm_rows(X, "X")
+        S = int(X.shape[0])
+        if X.shape[1] < d:
+            raise ValueError("X: expected [S, >= %d]" % d)
+        if S == 1:
+            row_stride = max(row_stride, d)
+        score = self._dev(score, (S,), "score", contiguous=False)
+        if pairs is None:
+            npairs = d * (d - 1) // 2
+        else:
+            pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+            npairs = int(pairs.shape[0])
+        outputs = tuple(outputs)
+        if not outputs or any(k not in ("1d", "2d") for k in outputs):
+            raise ValueError("outputs: '1d' and / or '2d'")
+        shapes = {"1": (d, B), "2": (npairs, B, B)}
+        names = [n + o[0] for o in outputs for n in ("min", "cnt", "nroy")]
+        if into is None:
+            out = {k: torch.empty(shapes[k[-1]], dtype=torch.float64 if k[:3] == "min" else torch.int64, device=dev) for k in names}
+        else:
+            out = into
+            for k in names:
+                self._dev(out[k], shapes[k[-1]], "into[%r]" % k, dtype="torch.float64" if k[:3] == "min" else "torch.int64")
+        self._ck(self.lib.gpb_hm_maps(self.h, nat.ptr(X), S, d, row_stride, nat.ptr(score), float(cutoff), nat.ptr(edges), B, nat.ptr(pairs),
+                                      npairs, 1 if into is None else 0, *[nat.ptr(out.get(k)) for k in
+                                                                          ("min1", "cnt1", "nroy1", "min2", "cnt2", "nroy2")]))
+        if on_device or into is not None:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     MAXPRO_N, MAXPRO_D, MAXPRO_MAX_RESTARTS, MAXPRO_MAX_BLOCK =(4, 4096), (2, 64), 16, 64
 
     def _maxpro_shape(self, n, d):

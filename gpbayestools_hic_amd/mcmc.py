@@ -446,6 +446,26 @@ class Chain:
 
     ppd_slab_rows = None                         # most rows of one posterior_predictive slab (None: _log_prob's rule); same bits
 
+    def _predict_slab_rows(self, override=None):
+        """rows of one predict slab: _log_prob's rule (the K*^T workspace is P x N x rows doubles per emulator), or the override"""
+        per_row = max(8 * e._ngp * e._X_train.shape[0] for e in self.emuList)
+        slab = int(min(max((8 << 30) // per_row, 1024), 1 << 17)) // 128 * 128
+        return slab if override is None else max(int(override), 1)
+
+    def _predict_diag_slab(self, engs, X_host, Xd, esd, mu_T, var_T):
+        """One slab of rows (X_host on the host, Xd the same rows on the device) through every emulator: gpb_emu_predict_diag into
+        the emulator's rows of the [nobs, rows] device views mu_T, var_T — _predict's mean and np.diagonal(cov), bit for bit."""
+        import torch
+        r0 = 0
+        for emu, eng in zip(self.emuList, engs):
+            # parameterTrafoPCA emulators: the HOST map, as Emulator.predict applies it — the device pre-pass agrees with it
+            # to ~1e-12, not to the bit, and these arrays are _predict's bits
+            Xg = Xd
+            if getattr(emu, "parameterTrafoPCA_", False):
+                Xg = torch.as_tensor(np.ascontiguousarray(emu._map_parameters(X_host() if callable(X_host) else X_host)), device=Xd.device)
+            eng.emu_predict_diag(Xg, extra_std=esd, out=(mu_T[r0:r0 + emu.nobs], var_T[r0:r0 + emu.nobs]))
+            r0 += emu.nobs
+
     def _ppd_arrays(self, X, extra_std=0.0):
         """(engines, mu_T, var_T): the emulators' means and covariance diagonals at the rows X [S, ndim], observable-major
         device arrays [nobs, S] in emuList order — what _predict(X, extra_std) returns as mean and np.diagonal(cov), bit for
@@ -460,10 +480,7 @@ class Chain:
         S = X.shape[0]
         if sum(e.nobs for e in self.emuList) != self.nobs:
             raise ValueError("emulators provide %d observables, experiment has %d" % (sum(e.nobs for e in self.emuList), self.nobs))
-        per_row = max(8 * e._ngp * e._X_train.shape[0] for e in self.emuList)
-        slab = int(min(max((8 << 30) // per_row, 1024), 1 << 17)) // 128 * 128
-        if self.ppd_slab_rows is not None:
-            slab = max(int(self.ppd_slab_rows), 1)
+        slab = self._predict_slab_rows(self.ppd_slab_rows)
         mu_T = torch.empty((self.nobs, S), dtype=torch.float64, device=dev)
         var_T = torch.empty((self.nobs, S), dtype=torch.float64, device=dev)
         es = np.ascontiguousarray(extra_std * X[:, -1])               # as _predict forms it (src/mcmc.py:153-166)
@@ -471,15 +488,7 @@ class Chain:
             i1 = min(i0 + slab, S)
             Xd = torch.as_tensor(np.ascontiguousarray(X[i0:i1]), device=dev)
             esd = torch.as_tensor(es[i0:i1], device=dev)
-            r0 = 0
-            for emu, eng in zip(self.emuList, engs):
-                # parameterTrafoPCA emulators: the HOST map, as Emulator.predict applies it — the device pre-pass agrees with it
-                # to ~1e-12, not to the bit, and these arrays are _predict's bits
-                Xg = Xd
-                if getattr(emu, "parameterTrafoPCA_", False):
-                    Xg = torch.as_tensor(np.ascontiguousarray(emu._map_parameters(X[i0:i1])), device=dev)
-                eng.emu_predict_diag(Xg, extra_std=esd, out=(mu_T[r0:r0 + emu.nobs, i0:i1], var_T[r0:r0 + emu.nobs, i0:i1]))
-                r0 += emu.nobs
+            self._predict_diag_slab(engs, X[i0:i1], Xd, esd, mu_T[:, i0:i1], var_T[:, i0:i1])
         return engs, mu_T, var_T
 
     def posterior_predictive(self, samples, quantiles=(0.05, 0.16, 0.5, 0.84, 0.95), extra_std=0.0):
@@ -522,6 +531,42 @@ class Chain:
         return PosteriorPredictive(q, mom[:, 0], np.sqrt(mom[:, 1]), np.sqrt(mom[:, 2]), np.sqrt(mom[:, 1] + mom[:, 2]),
                                    np.ascontiguousarray(percentile_from_order(out["order"], q, S).T),
                                    np.ascontiguousarray(out["mixq"].T), pit, S)
+
+    hm_slab_rows = None                          # most rows of one history_match / implausibility slab (None: _log_prob's rule); same bits
+
+    def implausibility(self, X, kth=2, discrepancy=None, rel_discrepancy=0.0, observable_mask=None):
+        """The univariate implausibility of explicit rows X [S, ndim]: I_m = |expdata_m - mean_m(x)| / sqrt(var_m(x) + V_m) with
+        V = diag(expdata_cov) + discrepancy + (rel_discrepancy expdata)^2 (discrepancy, rel_discrepancy: scalars or [nobs]) and
+        the observables where observable_mask is False left out.  Returns a dict of numpy arrays: "top" [kth, S] the kth largest
+        per row (a row is not ruled out yet iff top[kth - 1] < cutoff), "arg" [S] the observable of the largest, "gmax" [E, S]
+        the largest per emulator, "bad" the number of rows with an undefined implausibility.  Predict and reduction run on the
+        device slab by slab (gpb_emu_predict_diag, gpb_hm_implausibility).  Errors as history_match."""
+        from .history import chain_implausibility
+        return chain_implausibility(self, X, kth, discrepancy, rel_discrepancy, observable_mask)
+
+    def history_match(self, n_samples=1 << 20, X=None, cutoff=3.0, kth=2, discrepancy=None, rel_discrepancy=0.0, observable_mask=None,
+                      bins=20, bounds=None, pairs=None, keep=100000, seed=0):
+        """How much of the box do the data already rule out, which observable or data set does it, and where should the next wave
+        of model runs go: history matching (history.py) with the trained emulators, BEFORE any sampling.  n_samples candidates are
+        drawn uniformly in `bounds` [ndim, 2] (default the prior box) on the device (gpb_hm_uniform, keyed by `seed` and the row),
+        or X [S, ndim] is judged as given (posterior draws, a design).  Slab by slab (hm_slab_rows; the workspace does not grow
+        with n_samples): the predict pass of posterior_predictive, emulator by emulator, into one [nobs, slab] pair; the
+        implausibility I_m = |expdata_m - mean_m| / sqrt(var_m + V_m), V = diag(expdata_cov) + discrepancy + (rel_discrepancy
+        expdata)^2, masked observables (observable_mask False) left out (gpb_hm_implausibility: the kth largest, the observable
+        of the largest, the largest per emulator); the maps of the kth largest over `bins` (<= 64) equal bins per parameter
+        and the parameter pairs `pairs` (default all) (gpb_hm_maps).  A candidate is not ruled out yet (NROY) iff its kth largest
+        implausibility is < cutoff.  Returns a HistoryMatch: NROY fraction, ruled_out_by, dataset_nroy_fraction, minimum-
+        implausibility and optical-depth maps, the NROY box and the first `keep` NROY rows — candidates for propose_design —
+        and .refocus() for the next wave's bounds.  Integer reductions only: equal inputs give equal results whatever the slabs.
+
+        The measure is the UNIVARIATE one: correlations between observables in expdata_cov are ignored (history.py shows the way
+        to a multivariate score).  n_bad > 0 — candidates whose implausibility is undefined — raises a RuntimeWarning.  A
+        nroy_fraction of 0 means that nothing survives: look at ruled_out_by and the discrepancy; it is not an error.
+        NotImplementedError for foreign emulators and a chain sharded over several ranks; ValueError for kth above the number
+        of unmasked observables (or 4), wrong shapes and bounds."""
+        from .history import history_match
+        return history_match(self, n_samples, X, cutoff, kth, discrepancy, rel_discrepancy, observable_mask, bins, bounds, pairs, keep,
+                             seed)
 
     def convergence(self, chain=None, discard=0, c=5, tol=50):
         """Is the chain long enough?  ChainDiagnostics (diagnostics.py) of a stored [nwalkers, nsteps, ndim] array — self.chain

@@ -790,6 +790,49 @@ GPB_API int gpb_eig_lse(gpb_ctx* ctx, const double* mu_T, const double* var_T /*
                 const int32_t* outer_idx_dev /*[S_out]*/, int64_t S_out, int64_t ld_out, const int32_t* ranges_host /*[G,2]*/, int G,
                 int splits /*0: automatic*/, int on_device, double* lse_excl /*[G,S_out]*/, double* self /*[G,S_out]*/);
 
+/* ---- history matching: implausibility, NROY space, maps ----------------------------------------------------------------------- *
+ * gpb_hm_uniform, gpb_hm_implausibility, gpb_hm_maps <- nothing in the reference project: its `predict` returns [S, nobs, nobs]
+ *                  arrays and nothing asks how much of the prior box the data already rule out (Craig et al. 1997; Vernon, Goldstein &
+ *                  Bower 2010; gpbayestools_hic_amd/history.py).
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  Every array but lo_host, hi_host,
+ *   ranges_host, edges_host and pairs_host is DEVICE memory; the calls enqueue on the context's stream and do not synchronise.
+ *   gpb_hm_uniform: candidate rows r < S of X_dev [S][ld], x[r][j] = lo_j + (hi_j - lo_j) u, two roundings after the subtraction (no
+ *   fused multiply-add), u = u01(p.x, p.y) of p = philox(seed, (uint32) R, (uint32) (R >> 32), j, 16) (csrc/philox.h) with R = row0 + r
+ *   the ABSOLUTE row: a row's bits do not depend on how a call is cut into slabs.  Columns >= d are not touched.
+ *   Errors (GPB_E_ARG): d outside 1 .. 512; S < 1 or above 2^31 - 1; bounds that are not finite or hi_j <= lo_j; ld < d.
+ *   gpb_hm_implausibility: mu_T, var_T [M][ld] OBSERVABLE-MAJOR as gpb_emu_predict_diag writes them.  Per sample s < S and observable m:
+ *     r = |yexp_m - mu_T[m][s]|,  v = var_T[m][s] + vadd_m  (var_T == NULL: 0; vadd_dev == NULL: 0)
+ *     I_m = r / sqrt(v) when v > 0 and r is not NaN (inf / inf, a non-finite mean under vadd_m = +inf, counts as 0); otherwise,
+ *     a NaN v included, I_m = 0 if r == 0, else +inf — and the sample is BAD.  *bad_dev (int64, device) is ADDED the number of bad
+ *     samples, each once.  vadd_m = +inf gives I_m = 0 exactly: the way to mask an observable.  No output is ever NaN.
+ *     top_T[k][s], k < K: the (k + 1)-th largest I_m over all observables; arg[s] (int32, or NULL): the observable of the largest,
+ *     the lowest index on ties; gmax_T[g][s] (or NULL), g < G: the largest I_m over [ranges_host[2g], ranges_host[2g + 1]).  top_T and
+ *     gmax_T have the leading dimension ldo; columns >= S are not touched.  One lane per sample, the K largest kept in registers; a
+ *     sample's outputs depend on its own column alone (no floating-point atomics).
+ *   Errors (GPB_E_ARG): M outside 1 .. 4096; K outside 1 .. min(4, M); G outside 0 .. 64; a range that is empty or not inside [0, M);
+ *     ld or ldo below S; S < 1 or above 2^31 - 1; a NULL mu_T, yexp_dev, top_T or bad_dev.
+ *   gpb_hm_maps: rows x_dev [S][row_stride] with a score per row.  Over the bin edges edges_host [d][B + 1] — gpb_chain_marginals' BIN
+ *     RULE: bin b iff e[b] <= x < e[b + 1], the last bin closed, NaN and the rest outside — for every bin of every parameter
+ *     (min1, cnt1, nroy1 [d][B]) and every bin pair of every pair of parameters (min2, cnt2, nroy2 [npairs][B][B]; pairs_host
+ *     [npairs][2], NULL = all i < j in lexicographic order) that a row falls into: cnt += 1; nroy += 1 if score < cutoff (strict);
+ *     min = min(min, score).  init = 1 first sets the minima to +inf and the counts to 0 (an empty bin reads +inf, 0, 0), init = 0
+ *     accumulates onto what the arrays hold: slabs add up.  Either triple may be NULL (as a whole).  The minimum is an integer minimum
+ *     of order-preserving 64-bit keys (csrc/order_key.h), the counts are integer adds: the result does not depend on arrival order or
+ *     on the slabs.  Scores must not be NaN; +inf counts and never lowers a minimum.  While the call is in flight min1 / min2 hold keys.
+ *   Errors (GPB_E_ARG): B outside 1 .. 64; row_stride < d; edges not finite or not strictly increasing; a pair index outside [0, d)
+ *     or a pair (i, i); without a pair list npairs != d (d - 1) / 2; npairs B^2 above 2^31 - 1; S < 1 or above 2^31 - 1; a cutoff
+ *     that is not finite; init not 0 / 1; a triple of which only a part is given. */
+GPB_API int gpb_hm_uniform(gpb_ctx* ctx, const double* lo_host /*[d]*/, const double* hi_host /*[d]*/, int64_t d, uint64_t row0, int64_t S,
+                   uint64_t seed, double* X_dev /*[S,ld]*/, int64_t ld);
+GPB_API int gpb_hm_implausibility(gpb_ctx* ctx, const double* mu_T, const double* var_T /*or NULL*/, int64_t M, int64_t S, int64_t ld,
+                          const double* yexp_dev /*[M]*/, const double* vadd_dev /*[M] or NULL*/, const int32_t* ranges_host /*[G,2] or NULL*/,
+                          int G, int K, double* top_T /*[K,ldo]*/, int32_t* arg /*[S] or NULL*/, double* gmax_T /*[G,ldo] or NULL*/,
+                          int64_t ldo, int64_t* bad_dev /*[1], added to*/);
+GPB_API int gpb_hm_maps(gpb_ctx* ctx, const double* x_dev /*[S,row_stride]*/, int64_t S, int64_t d, int64_t row_stride,
+                const double* score_dev /*[S]*/, double cutoff, const double* edges_host /*[d,B+1]*/, int B,
+                const int32_t* pairs_host /*[npairs,2] or NULL*/, int64_t npairs, int init, double* min1 /*[d,B]*/, int64_t* cnt1,
+                int64_t* nroy1, double* min2 /*[npairs,B,B]*/, int64_t* cnt2, int64_t* nroy2);
+
 /* ---- maximum-projection Latin-hypercube designs -------------------------------------------------------------------------------- *
  * gpb_maxpro_lhd, gpb_maxpro_run_order <- src/design.py:64-74, R's `MaxProRunOrder(MaxProLHD(npoints, ndim)$Design)`;
  * gpb_maxpro_criterion: the criterion that generator minimises, for any design.
