@@ -12,7 +12,7 @@ __all__ = ["Emulator", "Chain", "mvn_loglike", "GPEngine", "StretchSampler", "Lo
            "posterior_clusters", "Design", "generate_lhs", "MaxProDesign", "maxpro_design", "GoodnessOfFit", "posterior_gof",
            "InformationGain", "PosteriorComparison", "information_gain", "posterior_divergence", "knn_distances",
            "HMCSampler", "EIGResult", "expected_information_gain", "LooResult", "PsisResult", "posterior_loo", "psis",
-           "HistoryMatch", "implausibility", "implausibility_maps"]
+           "HistoryMatch", "implausibility", "implausibility_maps", "SteinThinning", "SteinDiscrepancy", "stein_thin", "ksd"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the built library
@@ -53,6 +53,9 @@ def __getattr__(name):   # lazy: importing the package must not need torch / the
     if name in ("HistoryMatch", "implausibility", "implausibility_maps"):
         from . import history
         return getattr(history, name)
+    if name in ("SteinThinning", "SteinDiscrepancy", "stein_thin", "ksd"):
+        from . import thinning
+        return getattr(thinning, name)
     if name in ("EIGResult", "expected_information_gain"):
         from . import eig
         return getattr(eig, name)

@@ -87,6 +87,8 @@ BOUNDARY = {
                                    VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gpb_chain_knn": (C.c_int, [VP, VP, c_i64, c_i64, c_i64, c_i64, VP, c_i64, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int,
                                 C.c_int, VP, VP, VP, VP]),
+    "gpb_stein_thin": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_i64, c_i64, VP, c_i64, C.c_int, VP, VP, VP, VP]),
+    "gpb_stein_ksd": (C.c_int, [VP, VP, VP, c_i64, c_i64, c_i64, c_i64, VP, C.c_int, C.c_int, VP, VP, VP]),
     "gpb_eig_simulate": (C.c_int, [VP, VP, VP, VP, c_i64, c_i64, c_i64, VP, c_i64, c_u64, VP, VP, c_i64]),
     "gpb_eig_lse": (C.c_int, [VP, VP, VP, VP, VP, c_i64, c_i64, c_i64, VP, VP, c_i64, c_i64, VP, C.c_int, C.c_int, C.c_int, VP, VP]),
     "gpb_hm_uniform": (C.c_int, [VP, VP, VP, c_i64, c_u64, c_i64, c_u64, VP, c_i64]),

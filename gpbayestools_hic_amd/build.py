@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpbayes.so")
 LIB_DEBUG = os.path.join(HERE, "libgpbayes_debug.so")
 SOURCES = ["gpb_api.hip", "gpb_fit.hip", "gpb_chol.hip", "gpb_predict.hip", "gpb_sliced.hip", "gpb_like.hip", "gpb_coupled.hip", "gpb_chain.hip", "gpb_stretch.hip", "gpb_sets.hip", "gpb_cov.hip", "gpb_pmap.hip", "gpb_pool.hip",
-           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_rank.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip", "gpb_curves.hip", "gpb_sens.hip", "gpb_gof.hip", "gpb_knn.hip", "gpb_hmc.hip", "gpb_eig.hip", "gpb_loo.hip", "gpb_psis.hip", "gpb_hm.hip"]
+           "gpb_grad.hip", "gpb_ptlmc.hip", "gpb_smc.hip", "gpb_cv.hip", "gpb_sobol.hip", "gpb_design.hip", "gpb_ppd.hip", "gpb_diag.hip", "gpb_rank.hip", "gpb_marg.hip", "gpb_kmeans.hip", "gpb_maxpro.hip", "gpb_curves.hip", "gpb_sens.hip", "gpb_gof.hip", "gpb_knn.hip", "gpb_hmc.hip", "gpb_eig.hip", "gpb_loo.hip", "gpb_psis.hip", "gpb_hm.hip", "gpb_stein.hip"]
 # per-source compiler flags.  gpb_sens.hip: its two-double dot products and its bit-for-bit R / I formulas hold only if no product
 # is fused into a sum (hipcc's default -ffp-contract=fast fuses in the backend, past pragmas and the __d*_rn intrinsics);
 # gpb_gof.hip carries the same two-double dot products; gpb_knn.hip's squared distance is acc = acc + t * t, two roundings, which
@@ -16,11 +16,12 @@ SOURCES = ["gpb_api.hip", "gpb_fit.hip", "gpb_chol.hip", "gpb_predict.hip", "gpb
 # gpb_eig.hip: the simulated data y = mu + sqrt(s) z, two roundings, which numpy reproduces from the returned z;
 # gpb_rank.hip: np.quantile's interpolation lo + (hi - lo) g, two roundings; gpb_loo.hip carries gpb_gof.hip's two-double dot
 # products; gpb_psis.hip: the fit of psis_fit.h, whose host check runs the same operations in the same order; gpb_hm.hip: the candidate
-# rows x = lo + (hi - lo) u, two roundings after the subtraction, and I = |y - mu| / sqrt(var + vadd), which numpy reproduces bit for bit
+# rows x = lo + (hi - lo) u, two roundings after the subtraction, and I = |y - mu| / sqrt(var + vadd), which numpy reproduces bit for bit;
+# gpb_stein.hip: the four sums of a pair, q = q + r * h and its like, and kp's polynomial in 1 / sqrt(q), one rounding per operation
 SOURCE_FLAGS = {"gpb_sens.hip": ["-ffp-contract=off"], "gpb_gof.hip": ["-ffp-contract=off"], "gpb_knn.hip": ["-ffp-contract=off"],
                 "gpb_hmc.hip": ["-ffp-contract=off"], "gpb_eig.hip": ["-ffp-contract=off"], "gpb_rank.hip": ["-ffp-contract=off"],
-                "gpb_loo.hip": ["-ffp-contract=off"], "gpb_psis.hip": ["-ffp-contract=off"], "gpb_hm.hip": ["-ffp-contract=off"]}
-HEADERS = ["gpb_internal.h", "dispatch.h", "dev_buf.h", "ws_carve.h", "ws_layout.h", "coupled_setup.h", "lowrank_setup.h", "stretch_move.h", "sl_index.h", "gemm_tile.h", "block_reduce.h", "chol_block.h", "fast_math.h", "philox.h", "maxpro_index.h", "curve_fn.h", "order_key.h", "diag_gram.h", "ndtri.h", "chi2_sf.h", "knn_plan.h", "hmc_step.h", "eig_plan.h", "psis_fit.h", os.path.join("..", "..", "include", "gpbayes.h"),
+                "gpb_loo.hip": ["-ffp-contract=off"], "gpb_psis.hip": ["-ffp-contract=off"], "gpb_hm.hip": ["-ffp-contract=off"], "gpb_stein.hip": ["-ffp-contract=off"]}
+HEADERS = ["gpb_internal.h", "dispatch.h", "dev_buf.h", "ws_carve.h", "ws_layout.h", "coupled_setup.h", "lowrank_setup.h", "stretch_move.h", "sl_index.h", "gemm_tile.h", "block_reduce.h", "chol_block.h", "fast_math.h", "philox.h", "maxpro_index.h", "curve_fn.h", "order_key.h", "diag_gram.h", "ndtri.h", "chi2_sf.h", "knn_plan.h", "hmc_step.h", "eig_plan.h", "psis_fit.h", "stein_plan.h", os.path.join("..", "..", "include", "gpbayes.h"),
            os.path.join("..", "..", "include", "gpbayes_debug.h")]
 
 

@@ -281,6 +281,19 @@ class ClosureResult:
         return information_gain(self._set_samples(int(k_set))[:, int(discard)::int(thin)], self.prior_ranges[:, 0],
                                 self.prior_ranges[:, 1], layout="walkers", **kw)
 
+    def stein_thin(self, chain, k_set, m=100, discard=0, thin=1, **kw):
+        """SteinThinning (thinning.py) of data set k_set's samples, without the first `discard` stored steps and thinned by
+        `thin`.  `chain`: the Chain the sets were calibrated with, holding data set k_set as its experimental data — a result
+        holds arrays only, and the score is that of the chain's installed likelihood; kw as Chain.stein_thin takes them"""
+        kw.setdefault("names", self.names)
+        x = self._set_samples(int(k_set))[:, int(discard)::int(thin)]
+        return chain.stein_thin(x.reshape(-1, x.shape[-1]), m=m, **kw)
+
+    def ksd(self, chain, k_set, discard=0, thin=1, **kw):
+        """SteinDiscrepancy (thinning.py) of data set k_set's samples; `chain` as stein_thin takes it"""
+        x = self._set_samples(int(k_set))[:, int(discard)::int(thin)]
+        return chain.ksd(x.reshape(-1, x.shape[-1]), **kw)
+
     def expected_information_gain(self, chain, k_set, discard=0, thin=1, **kw):
         """EIGResult (eig.py) over data set k_set's samples, without the first `discard` stored steps and thinned by `thin`: what a
         planned measurement is expected to add to that set's posterior.  `chain`: the Chain the sets were calibrated with (a

@@ -164,6 +164,7 @@ struct gpb_ctx {
     gpb::DevBuf<int64_t> curves_ws;  // posterior curves and trace histograms (gpb_curves.hip): CurvesWs of ws_layout.h
     gpb::DevBuf<int64_t> kmeans_ws;  // posterior clusters (gpb_kmeans.hip): KmeansWs of ws_layout.h
     gpb::DevBuf<int64_t> knn_ws;     // nearest-neighbour distances (gpb_knn.hip): KnnWs of ws_layout.h
+    gpb::DevBuf<int64_t> stein_ws;   // Stein thinning and discrepancy (gpb_stein.hip): SteinThinWs / SteinKsdWs of stein_plan.h
     gpb::DevBuf<double> eig_ws;      // expected information gain (gpb_eig.hip): EigWs of ws_layout.h
     gpb::DevBuf<int64_t> maxpro_ws;  // MaxPro Latin-hypercube designs (gpb_maxpro.hip): MaxproWs of ws_layout.h
     gpb::DevBuf<double> sens_ws;     // gpb_sens_accumulate (gpb_sens.hip): per-row F | diag Cw | L^-1 J (large rows) | chunk sums | flags

@@ -1228,6 +1228,83 @@ class GPEngine:
         out["n_skipped"] = (int(nskip[0]), int(nskip[1]))
         return out
 
+    STEIN_MAX_M, STEIN_MAX_SPLITS = 1 << 20, 64
+
+    def _stein_inputs(self, x, g, ginv):
+        """the shared arguments of stein_thin / stein_ksd: x, g float64 cuda tensors [n, d] with unit stride along d (a [::k] view
+        of a longer array is fine: its row stride goes to the library), ginv [d, d] on the host"""
+        for name, a in (("x", x), ("g", g)):
+            if not (_is_torch(a) and a.is_cuda and a.device.index == self.device and str(a.dtype) == "torch.float64" and a.dim() == 2):
+                raise ValueError("%s: a float64 tensor [n, d] on cuda:%d" % (name, self.device))
+        n, d = int(x.shape[0]), int(x.shape[1])
+        if tuple(g.shape) != (n, d):
+            raise ValueError("g: expected the shape of x, %s" % ((n, d),))
+        if d > 64:
+            raise ValueError("x: %d parameters, at most 64" % d)
+        for name, a in (("x", x), ("g", g)):
+            if d > 1 and a.stride(1) != 1:
+                raise ValueError("%s: expected unit stride along the parameters" % name)
+        xs, gs = (int(a.stride(0)) if n > 1 else max(int(a.stride(0)), d) for a in (x, g))
+        ginv = nat.f64(np.asarray(ginv, dtype=np.float64))
+        if ginv.shape != (d, d):
+            raise ValueError("ginv: expected [%d, %d]" % (d, d))
+        return n, d, xs, gs, ginv
+
+    def stein_thin(self, x, g, ginv, m, on_device=False, return_obj=False):
+        """Stein thinning of the rows x [n, d] with scores g [n, d] (float64 cuda tensors; d <= 64) under the inverse
+        multiquadric kernel with the preconditioner ginv = Gamma^-1 [d, d] (host, SPD): greedily the m rows whose empirical
+        measure has the smallest kernel Stein discrepancy (gpb_stein_thin; the rule is in include/gpbayes.h and
+        tests/stein_reference.py reproduces it bit for bit).  Returns a dict: "idx" [m] (int32 row numbers; rows may repeat; -1
+        when no row can be picked), "ksd" [m] (ksd[t - 1]: the discrepancy of the first t picks), "n_skipped" (rows with a
+        non-finite x, g or Gamma^-1 x: never picked, left out of every sum) and, with return_obj, "obj" [n] (the objective after
+        the last update; NaN for a skipped row).  numpy out, or torch tensors with on_device.  All m iterations are enqueued
+        in one call.  The engine lends its device, stream and buffer cache only."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        n, d, xs, gs, ginv = self._stein_inputs(x, g, ginv)
+        m = int(m)
+        mm = min(max(m, 0), self.STEIN_MAX_M)
+        if on_device:
+            out = {"idx": torch.empty(mm, dtype=torch.int32, device=dev), "ksd": torch.empty(mm, dtype=torch.float64, device=dev)}
+            if return_obj:
+                out["obj"] = torch.empty(n, dtype=torch.float64, device=dev)
+        else:
+            out = {"idx": np.empty(mm, dtype=np.int32), "ksd": np.empty(mm)}
+            if return_obj:
+                out["obj"] = np.empty(n)
+        nskip = np.zeros(1, dtype=np.int64)
+        self._ck(self.lib.gpb_stein_thin(self.h, nat.ptr(x), nat.ptr(g), n, d, xs, gs, nat.ptr(ginv), m, 1 if on_device else 0,
+                                         nat.ptr(out["idx"]), nat.ptr(out["ksd"]), nat.ptr(out.get("obj")), nat.ptr(nskip)))
+        out["n_skipped"] = int(nskip[0])
+        return out
+
+    def stein_ksd(self, x, g, ginv, splits=0, on_device=False, return_rows=False):
+        """The kernel Stein discrepancy of ALL rows x [n, d] with scores g [n, d] (as stein_thin takes them): n^2 pair
+        evaluations in fp64 (gpb_stein_ksd).  Returns a dict: "ksd2" (the squared discrepancy sum_ij kp(i, j) / n_valid^2; a
+        float, or a one-element tensor with on_device), "ksd" (its square root; host mode only), "n_skipped" and, with
+        return_rows, "row_sum" [n] (sum_j kp(i, j); NaN for a skipped row).  The summation order is fixed by the header: splits
+        (0: automatic) and the library's slabs change no bit."""
+        import torch
+        self._track_stream()
+        dev = torch.device("cuda", self.device)
+        n, d, xs, gs, ginv = self._stein_inputs(x, g, ginv)
+        if on_device:
+            ksd2 = torch.empty(1, dtype=torch.float64, device=dev)
+            rows = torch.empty(n, dtype=torch.float64, device=dev) if return_rows else None
+        else:
+            ksd2 = np.empty(1)
+            rows = np.empty(n) if return_rows else None
+        nskip = np.zeros(1, dtype=np.int64)
+        self._ck(self.lib.gpb_stein_ksd(self.h, nat.ptr(x), nat.ptr(g), n, d, xs, gs, nat.ptr(ginv), int(splits), 1 if on_device else 0,
+                                        nat.ptr(rows), nat.ptr(ksd2), nat.ptr(nskip)))
+        out = {"ksd2": ksd2 if on_device else float(ksd2[0]), "n_skipped": int(nskip[0])}
+        if not on_device:
+            out["ksd"] = float(np.sqrt(ksd2[0]))
+        if return_rows:
+            out["row_sum"] = rows
+        return out
+
     EIG_MAX_M, EIG_MAX_GROUPS, EIG_MAX_SPLITS = 4096, 64, 64
 
     def _eig_inputs(self, mu_T, var_T, vadd, outer_idx):

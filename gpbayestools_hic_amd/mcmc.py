@@ -861,6 +861,71 @@ class Chain:
             x = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
         return x[:, discard::thin], "walkers"
 
+    def _score_device(self, rows):
+        """grad log posterior at the rows [n, ndim] (a float64 cuda tensor), as a device tensor: gpb_chain_logpost_grad in slabs
+        of grad_slab_rows, nothing brought to the host.  A row's numbers are those of log_posterior(rows, return_grad=True)."""
+        if not self._native():
+            raise NotImplementedError("log-posterior gradients need every emulator of the chain to be this package's Emulator "
+                                      "(foreign emulators have no device derivatives)")
+        import torch
+        from . import _native as nat
+        if rows.dim() != 2 or rows.shape[1] != self.ndim:
+            raise ValueError("the rows have %d columns, the chain has %d parameters" % (rows.shape[-1], self.ndim))
+        dev = torch.device("cuda", self.device)
+        engs, arr, nemu = self._contexts()
+        e0 = engs[0]
+        lo_dev, hi_dev = self._box(dev)
+        per_row = max(8 * e._ngp * e._X_train.shape[0] for e in self.emuList)
+        slab = int(min(max((4 << 30) // per_row, 1024), self.grad_slab_rows)) // 128 * 128
+        n = int(rows.shape[0])
+        grad = torch.empty((n, self.ndim), dtype=torch.float64, device=dev)
+        ll = torch.empty(min(n, slab), dtype=torch.float64, device=dev)
+        for i0 in range(0, n, slab):
+            Xd = rows[i0:i0 + slab].contiguous()
+            k = int(Xd.shape[0])
+            e0._ck(e0.lib.gpb_chain_logpost_grad(arr, nemu, nat.ptr(Xd), k, nat.ptr(ll), nat.ptr(grad[i0:i0 + k]), nat.ptr(lo_dev),
+                                                 nat.ptr(hi_dev), float(-np.inf), EXTRA_STD_CONST))
+        return grad
+
+    def _stein_rows(self, who, chain, discard, thin):
+        """the rows [S, ndim] (a float64 cuda tensor, memory order of the chain argument) and their scores"""
+        import torch
+        x, _ = self._stored_for_knn(who, chain, discard, thin)
+        if x.shape[-1] > 64:
+            raise ValueError("%s: %d parameters, at most 64" % (who, x.shape[-1]))
+        if not hasattr(x, "data_ptr"):
+            x = torch.as_tensor(np.require(x, requirements=["C"]), device=torch.device("cuda", self.device or 0))
+        rows = x.to(torch.float64).reshape(-1, x.shape[-1])
+        return rows, self._score_device(rows)
+
+    def stein_thin(self, chain=None, m=100, discard=0, thin=1, **kw):
+        """The m parameter sets at which to run the full model again: SteinThinning (thinning.py) of a stored [nwalkers, nsteps,
+        ndim] array — self.chain (default; read from mcmc_path when it is not in memory), an array, a tensor or a chain pickle's
+        path — without its first `discard` steps and thinned by `thin`, or of a flat [S, ndim] set (SMC or pocoMC particles: no
+        weights are needed).  Greedily the m rows whose empirical measure has the smallest kernel Stein discrepancy to the
+        posterior: burn-in is dropped by itself, the points are rows of the chain, `.savetxt()` writes the format of the
+        reference's cluster_centers.txt.  The scores come from gpb_chain_logpost_grad in slabs of grad_slab_rows and stay on the
+        device, where the m passes run (gpb_stein_thin).  The prior box self.min / self.max is taken out by the logit
+        transform; kw (preconditioner, transform) as thinning.stein_thin takes them.  ValueError for more than 64 parameters."""
+        from .thinning import stein_thin
+        rows, g = self._stein_rows("stein_thin", chain, discard, thin)
+        kw.setdefault("names", list(self.pardict) if len(getattr(self, "pardict", ())) == rows.shape[-1] else None)
+        kw.setdefault("lo", self.min)
+        kw.setdefault("hi", self.max)
+        return stein_thin(rows, g, m, **kw)
+
+    def ksd(self, chain=None, discard=0, thin=1, **kw):
+        """How well does a point set represent the posterior?  SteinDiscrepancy (thinning.py) of a chain as stein_thin takes it,
+        or of ARBITRARY rows [S, ndim] — posterior_clusters(...).centers, a SteinThinning's points, another sampler's chain: the
+        kernel Stein discrepancy needs only the rows and the score at them, so sets of any origin are compared on one scale
+        (give them the same explicit preconditioner=).  n^2 pair evaluations on the device (gpb_stein_ksd); kw (preconditioner,
+        transform, splits, return_rows) as thinning.ksd takes them."""
+        from .thinning import ksd
+        rows, g = self._stein_rows("ksd", chain, discard, thin)
+        kw.setdefault("lo", self.min)
+        kw.setdefault("hi", self.max)
+        return ksd(rows, g, **kw)
+
     def information_gain(self, chain=None, discard=0, thin=1, k=8, **kw):
         """How much did the data teach us?  InformationGain (divergence.py) of a stored [nwalkers, nsteps, ndim] array —
         self.chain (default; read from mcmc_path when it is not in memory), a loaded pickle's — without its first `discard`

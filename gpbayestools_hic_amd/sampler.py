@@ -183,6 +183,18 @@ class StoredChainAccessors:
         x, _ = self._stored_view(discard, thin)
         return self.chain_obj.expected_information_gain(x.reshape(-1, x.shape[-1]).cpu().numpy(), **kw)
 
+    def stein_thin(self, m=100, discard=0, thin=1, **kw):
+        """SteinThinning of chain[discard::thin] (thinning.py; Chain.stein_thin on the resident chain, rows numbered step-major):
+        the m rows whose empirical measure has the smallest kernel Stein discrepancy to the posterior"""
+        x, _ = self._stored_view(discard, thin)
+        return self.chain_obj.stein_thin(x.reshape(-1, x.shape[-1]), m=m, **kw)
+
+    def ksd(self, discard=0, thin=1, **kw):
+        """SteinDiscrepancy of chain[discard::thin] (thinning.py; Chain.ksd on the resident chain): how well the stored chain
+        represents the posterior, on a scale that chains of any sampler share"""
+        x, _ = self._stored_view(discard, thin)
+        return self.chain_obj.ksd(x.reshape(-1, x.shape[-1]), **kw)
+
     def divergence_from(self, other, discard=0, thin=1, **kw):
         """PosteriorComparison of chain[discard::thin] (A) against `other` (B: another sampler — its stored chain, cut the same
         way —, a torch tensor or an array, [nsteps, nwalkers, ndim] with kw layout_b="steps", [nwalkers, nsteps, ndim] with

@@ -151,6 +151,15 @@ class SMCSampler:
         kw.setdefault("names", list(getattr(self.chain, "pardict", ())) or None)
         return information_gain(self.x[:self.N], self.chain.min, self.chain.max, **kw)
 
+    def stein_thin(self, m=100, **kw):
+        """SteinThinning of the resident particles (thinning.py; Chain.stein_thin): the thinning corrects a biased sample, so
+        no weights are needed"""
+        return self.chain.stein_thin(self.x[:self.N], m=m, **kw)
+
+    def ksd(self, **kw):
+        """SteinDiscrepancy of the resident particles (thinning.py; Chain.ksd)"""
+        return self.chain.ksd(self.x[:self.N], **kw)
+
     def divergence_from(self, other, **kw):
         """PosteriorComparison of the resident particles (A) against `other` (B: another SMCSampler's particles, a tensor or an
         array as divergence.posterior_divergence takes xb) on the chain's prior box"""

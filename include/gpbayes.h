@@ -751,6 +751,53 @@ GPB_API int gpb_chain_knn(gpb_ctx* ctx, const double* a_dev, int64_t a_nsteps, i
                   double* r2 /*[nA,kmax]*/, int32_t* idx /*[nA,kmax] or NULL*/, int32_t* zeros /*[nA] or NULL*/,
                   int64_t* n_skipped /*host, [2]*/);
 
+/* ---- kernel Stein discrepancy and Stein thinning of a resident point set ------------------------------------------------------- *
+ * gpb_stein_thin, gpb_stein_ksd <- nothing in the reference project: examples/generate_posterior_clusters.py picks the parameter
+ *                  sets for further full-model runs by k-means, and no diagnostic says how well a point set represents the
+ *                  posterior.  The kernel Stein discrepancy (Gorham & Mackey 2017) needs only the points and the score
+ *                  grad log p at them (gpb_chain_logpost_grad); Stein thinning (Riabiz et al. 2022) picks, greedily, the m rows
+ *                  whose empirical measure has the smallest discrepancy (gpbayestools_hic_amd/thinning.py).
+ *   The context gives the device, the stream and the buffer cache only; no GP state is touched.  x_dev, g_dev: rows x_i and scores
+ *   g_i, i < n, row i at [i row_stride], d contiguous doubles (device memory).  ginv_host [d][d]: a symmetric positive definite
+ *   Gamma^-1 (host memory; the library checks that it is finite with a positive diagonal, the CALLER that it is SPD).
+ *   THE RULE, which a numpy model reproduces bit for bit (tests/stein_reference.py).  The base kernel is the inverse multiquadric
+ *   k(x, y) = (1 + (x - y)^T Gamma^-1 (x - y))^(-1/2); kp is the Stein kernel of the Langevin operator, one operation per rounding,
+ *   no fused multiply-add, IEEE sqrt and division:
+ *     b_i = Gamma^-1 x_i          once per row: acc = 0; acc = acc + Ginv[j][l] * x[l], l ascending
+ *     tr  = sum_j Ginv[j][j]      from 0, j ascending, on the host
+ *     q = 1; t1 = t3 = t4 = 0
+ *     for l = 0 .. d - 1:  r = x_il - x_jl;  h = b_il - b_jl
+ *                          q = q + r * h;  t1 = t1 + h * h;  t3 = t3 + (g_il - g_jl) * h;  t4 = t4 + g_il * g_jl
+ *     s = sqrt(q); i1 = 1 / s; i2 = 1 / q; i3 = i1 * i2; i5 = i3 * i2
+ *     kp(i, j) = (-3 * t1) * i5 + (tr + t3) * i3 + t4 * i1                        evaluated left to right
+ *   A row with a non-finite entry in x, g or b is SKIPPED: never picked, left out of every sum (it adds +0), counted in
+ *   n_skipped; its obj and its row_sum are NaN.
+ *   gpb_stein_thin: obj_i = kp(i, i); S = 0; for t = 1 .. m: pi_t = the row of smallest obj among the rows that are not skipped
+ *     and whose obj is not NaN, the LOWEST row number on a tie; S = S + obj[pi_t]; ksd[t - 1] = sqrt(S) / t; idx[t - 1] = pi_t;
+ *     obj_i = obj_i + 2 * kp(i, pi_t) for every i.  Rows may repeat and m may exceed n.  ksd[t - 1] is the discrepancy of the
+ *     first t picks.  With no row to pick, idx = -1 and ksd = NaN from there on and obj is left as it is.  obj (optional)
+ *     receives the objective after the last update.  All m iterations are enqueued in one call; the host waits once, at the end.
+ *   gpb_stein_ksd: row_sum_i = sum_j kp(i, j) over all j, j = i included, in THIS order: the columns are cut into chunks of
+ *     GPB_STEIN_CHUNK; a chunk's partial starts at 0 and takes its columns in ascending j; the row sum starts at 0 and takes the
+ *     chunk partials in ascending order.  ksd2 = (sum_i row_sum_i) / (nv * nv), nv = (double)(n - n_skipped): the rows are cut
+ *     into chunks of 256 (a skipped row and the rows behind n count as +0); a chunk's 256 values v are summed as four groups of 64,
+ *     each by the butterfly v[l] = v[l] + v[l ^ o], o = 32, 16, .. 1, then (w0 + w1) + (w2 + w3); the total starts at 0 and takes
+ *     the chunk sums in ascending order.  No output depends on splits (the number of ranges the columns are cut into so that a
+ *     small set still fills the device; 0: chosen from the sizes), on on_device, on the strides or on the slabs of query rows
+ *     the call goes through (their chunk partials are kept under GPB_STEIN_PART_MB megabytes).
+ *   Outputs in host memory when on_device = 0 or device memory when 1; n_skipped always in host memory; the calls synchronise.
+ *   Errors (GPB_E_ARG; nothing is written): a NULL x_dev, g_dev, ginv_host, idx, ksd, ksd2 or n_skipped; n outside 1 .. 2^31 - 1;
+ *   d outside 1 .. 64; m outside 1 .. 2^20; a row stride below d; ginv_host not finite or with a diagonal entry <= 0; splits outside
+ *   0 .. 64; on_device not 0 / 1. */
+#define GPB_STEIN_CHUNK 1024
+#define GPB_STEIN_PART_MB 16
+GPB_API int gpb_stein_thin(gpb_ctx* ctx, const double* x_dev, const double* g_dev, int64_t n, int64_t d, int64_t x_row_stride,
+                  int64_t g_row_stride, const double* ginv_host /*[d,d]*/, int64_t m, int on_device, int32_t* idx /*[m]*/,
+                  double* ksd /*[m]*/, double* obj /*[n] or NULL*/, int64_t* n_skipped /*host*/);
+GPB_API int gpb_stein_ksd(gpb_ctx* ctx, const double* x_dev, const double* g_dev, int64_t n, int64_t d, int64_t x_row_stride,
+                  int64_t g_row_stride, const double* ginv_host /*[d,d]*/, int splits /*0: automatic*/, int on_device,
+                  double* row_sum /*[n] or NULL*/, double* ksd2, int64_t* n_skipped /*host*/);
+
 /* ---- expected information gain of planned measurements ------------------------------------------------------------------------ *
  * gpb_eig_simulate, gpb_eig_lse <- nothing in the reference project: it reports what the data taught (the posterior) and never asks
  *                  what a planned measurement is expected to teach.  The nested Monte Carlo estimator of the mutual information
